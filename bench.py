@@ -9,10 +9,12 @@ Inputs are synthetic and already resident in HBM when the timed region starts (t
 the host like the reference's tokenizer output: 1 MB, copied inside the step).  Weak scaling: each
 rank scores its own 256 outfits; the forward has no data-path collective.
 
-    python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and reports the headline; --full adds everything
+else (live roofline sample inside the timed region, breakdown step, parity against the oracle and the reference's fixture, CPU
+baseline, launch-by-launch and secondary-rung figures, and for N > 1 the CIR leg).
 """
 import argparse
 import ctypes as C
@@ -215,7 +217,7 @@ def main():
     ap.add_argument("--graph", type=int, default=1, help="1 (default): the drop-in call replays - OutfitX._cp_forward captures a repeated eval-mode call into ONE HIP graph on its second "
                     "occurrence (OutfitX.graph_replay, outfitx_amd/graphs.py) and every later call is one graph launch - same kernels, same streams, bit-identical logits; the step that "
                     "carries the live roofline sample is issued launch by launch (events ride on the launches).  0: every step launch by launch (also reported, after the timed "
-                    "region, as `launch_by_launch` in the default run's line)")
+                    "region, as `launch_by_launch` in the --full line)")
     ap.add_argument("--cir-queries", type=int, default=1000, help="N > 1 only: queries of the BASELINE configs[3] retrieval leg run after the timed region (pool row-sharded over the ranks, "
                     "ONE all-gather of the per-shard candidate lists: the only data-path collective the north star names); 0 = skip")
     ap.add_argument("--cir-pool", type=int, default=100_000, help="pool rows of that leg (whole job; sharded over the ranks)")
@@ -223,7 +225,13 @@ def main():
                     "31.85 vs 32.85 ms/step); the ONE step sampled for the roofline and the breakdown step run single-stream so that launch times do not overlap")
     ap.add_argument("--secondary", default="bf16", help="tower scheme of the secondary (non-headline) measurement after the timed region ('' = skip)")
     ap.add_argument("--ln-fold", type=int, default=2, help="2 (product default): towers' LayerNorms folded into the GEMM epilogues and the residual stream kept as a (hi, lo) operand-type pair; 1: folded, fp32 stream; 0: materialised (A/B)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline figure (off by default: see the module docstring); "
+                    "--cpu-outfits, --cpu-cfg2-outfits, --rung, --secondary and --cir-* only act with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the CP logits of the last timed step to DIR/cp_logits.npy (float32; rank r > 0: "
+                    "cp_logits_rank<r>.npy): the same arguments give the same inputs, so two builds can be compared output for output")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", 0)); world = int(os.environ.get("WORLD_SIZE", 1)); local = int(os.environ.get("LOCAL_RANK", 0))
     assert world == a.gpus, f"--gpus {a.gpus} but WORLD_SIZE={world}"
@@ -264,7 +272,7 @@ def main():
     # host-generated (numpy PCG64) so that the build container - where the reference itself can be imported,
     # oracle/gen_bench_golden.py - and this box see the same batch; preprocessing excluded from the timing
     px_np, ids_np, att_np = synth.bench_batch(seed, B, n)                 # [B,n,3,224,224] fp32; BOS + 6 words + EOS, padded to 64
-    in_crc = (synth.checksum(px_np[:2]), synth.checksum(ids_np))
+    in_crc = (synth.checksum(px_np[:2]), synth.checksum(ids_np)) if a.full else None
     px = torch.from_numpy(px_np).to(dev)
     del px_np
     texts = {"input_ids": torch.from_numpy(ids_np).view(B, n, 64).pin_memory(), "attention_mask": torch.from_numpy(att_np).view(B, n, 64).pin_memory()}
@@ -281,6 +289,7 @@ def main():
             torch.cuda.synchronize(dev)
 
     _log("model packed, inputs resident; warm-up")
+    out = None
     for i in range(a.warmup):
         # the first warm-up step runs the towers on one stream, as the sampled step of the timed region does: torch's caching allocator then
         # already holds the blocks that step takes from the main stream's pool (no hipMalloc inside the timed region: `device_allocs_in_timed_region`)
@@ -294,7 +303,7 @@ def main():
     model.graph_replay = bool(a.graph)
     graph_on, graph_note = False, "off (--graph 0): every step launch by launch"
     if a.graph:
-        eager_out = out.clone()
+        eager_out = (out if out is not None else step()).clone()     # --warmup 0: one launch-by-launch step to compare the replay with
         for _ in range(6):
             rp = model._replay
             if rp is not None and rp.stats["replays"] >= 2:
@@ -314,13 +323,14 @@ def main():
         fence()
     _log("timed region")
     lib = L.load()
-    # Live roofline sample: HIP events bracket every GEMM launch of ONE timed step (the middle one) on the launch
+    # --full only - live roofline sample: HIP events bracket every GEMM launch of ONE timed step (the middle one) on the launch
     # stream.  Bracketing all K steps costs ~1 ms/step of serialisation (246 event markers), so it is sampled.
-    sample = a.steps // 2
+    sample = a.steps // 2 if a.full else -1
     allocs0 = torch.cuda.memory_stats(dev).get("num_device_alloc", 0)        # hipMalloc calls of torch's caching allocator so far
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]      # one marker per step on torch's stream: the spread of the K steps
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)] if a.full else None     # one marker per step on torch's stream: the spread of the K steps
     t0 = time.perf_counter()
-    marks[0].record()
+    if a.full:
+        marks[0].record()
     host_t = [time.perf_counter()]
     for i in range(a.steps):
         if i == sample:
@@ -330,24 +340,29 @@ def main():
         if i == sample:
             lib.ofx_profile_enable(0)
             model.item_encoder.overlap_towers = bool(a.overlap_towers)
-        marks[i + 1].record()
-        host_t.append(time.perf_counter())
+        if a.full:
+            marks[i + 1].record()
+            host_t.append(time.perf_counter())
     fence()
     elapsed = time.perf_counter() - t0
-    per_step = [marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps)]
-    allocs_timed = torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - allocs0
-    recs = (L.ProfRecord * 4096)()
-    nrec = lib.ofx_profile_records(recs, 4096)              # per-launch records of the sampled step (before read() clears them)
-    ms, fl, cnt = (C.c_double * 4)(), (C.c_double * 4)(), (C.c_longlong * 4)()
-    L.check(lib.ofx_profile_read(ms, fl, cnt), "ofx_profile_read")
-    # one extra, untimed step with every category bracketed: the per-step breakdown
-    lib.ofx_profile_enable(15)
-    model.item_encoder.overlap_towers = False
-    step(); fence()
-    model.item_encoder.overlap_towers = bool(a.overlap_towers)
-    bms, bfl, bcnt = (C.c_double * 4)(), (C.c_double * 4)(), (C.c_longlong * 4)()
-    L.check(lib.ofx_profile_read(bms, bfl, bcnt), "ofx_profile_read")
-    lib.ofx_profile_enable(0)
+    if a.dump_outputs:                                      # what the caller of the timed path received from its last step
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "cp_logits.npy" if rank == 0 else f"cp_logits_rank{rank}.npy"), out.float().cpu().numpy())
+    if a.full:
+        per_step = [marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps)]
+        allocs_timed = torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - allocs0
+        recs = (L.ProfRecord * 4096)()
+        nrec = lib.ofx_profile_records(recs, 4096)              # per-launch records of the sampled step (before read() clears them)
+        ms, fl, cnt = (C.c_double * 4)(), (C.c_double * 4)(), (C.c_longlong * 4)()
+        L.check(lib.ofx_profile_read(ms, fl, cnt), "ofx_profile_read")
+        # one extra, untimed step with every category bracketed: the per-step breakdown
+        lib.ofx_profile_enable(15)
+        model.item_encoder.overlap_towers = False
+        step(); fence()
+        model.item_encoder.overlap_towers = bool(a.overlap_towers)
+        bms, bfl, bcnt = (C.c_double * 4)(), (C.c_double * 4)(), (C.c_longlong * 4)()
+        L.check(lib.ofx_profile_read(bms, bfl, bcnt), "ofx_profile_read")
+        lib.ofx_profile_enable(0)
     rank_info = None
     if world > 1:
         # whole-job time = the slowest rank's; every rank's own time, batch seed and host thread count travel to rank 0 for the line
@@ -359,7 +374,7 @@ def main():
         t = torch.tensor([elapsed], device="cpu" if rehearsal else dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        if a.cir_queries > 0:
+        if a.full and a.cir_queries > 0:
             rank_info.update(cir_leg(a, rank, world, dev, rehearsal, fence))
 
     if rank == 0:
@@ -367,54 +382,6 @@ def main():
         alg_gemm_outfit = n * (VIT_GEMM + txt_gemm(T_real)) + ot_gemm(n)
         alg_all_outfit = alg_gemm_outfit + n * (VIT_ATTN + txt_attn(T_real)) + ot_attn(n)
         padded_outfit = n * (VIT_GEMM + VIT_ATTN + txt_gemm(64) + txt_attn(64)) + ot_gemm(16) + ot_attn(16)
-        gemm_ms, gemm_launches = ms[0], int(cnt[0])
-        achieved_fixed = alg_gemm_outfit * B / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0   # SURVEY 8(d)'s per-outfit count x outfits, one sampled step
-        executed = fl[0] / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-        # per-shape table of the sampled step: shape -> kernel -> launches, us per launch, useful TF/s (2 M N K_logical) and its
-        # fraction of the dense peak, executed TF/s (x kmul: split weights run 2, three-product GEMMs 3 MFMA products per term),
-        # algorithmic HBM bytes per launch as the launch's own epilogue configuration implies (ofx_prof_record.bytes)
-        KIND = {1: "gemm_128x128_kernel", 2: "gemm_big_kernel<2,4,2>", 3: "gemm_big_kernel<2,2,1>", 4: "gemm_pp_kernel", 6: "gemm_w2_kernel",
-                7: "fused_qkv_attn_kernel (N = q|k|v columns; its attention FLOPs are not in useful_tflops)", 8: "gemm_w2f8_kernel", 9: "gemm_x3_kernel"}
-        shapes = {}
-        for i in range(nrec):
-            r = recs[i]
-            if r.cat != 0:
-                continue
-            e = shapes.setdefault((r.M, r.N, r.K, r.kmul, r.kind), [0, 0.0, 0.0])
-            e[0] += 1; e[1] += r.ms; e[2] += r.bytes
-        table, by_kernel = [], {}
-        launched_flop = 0.0          # useful FLOPs of the shapes actually launched (the pruned last ViT layer runs fewer rows than 8(d) counts)
-        for (M_, N_, K_, km_, kind_), (c_, t_, b_) in sorted(shapes.items(), key=lambda kv: -kv[1][1]):
-            useful = 2.0 * M_ * N_ * K_ * c_ / (t_ * 1e-3) / 1e12
-            launched_flop += 2.0 * M_ * N_ * K_ * c_
-            # matrix-pipe work in f16-rate product equivalents: the fp8 correction product of gemm_w2f8_kernel runs at twice the f16 rate
-            pe_ = 1.5 if kind_ == 8 else float(km_)
-            table.append({"M": M_, "N": N_, "K": K_, "products_per_term": km_, "f16_rate_product_equivalents": pe_, "kernel": KIND.get(kind_, str(kind_)), "launches": c_,
-                          "us_per_launch": round(t_ * 1e3 / c_, 1), "ms_per_step": round(t_, 3), "useful_tflops": round(useful, 1),
-                          "frac_useful": round(useful / PEAK_BF16_TFLOPS, 4), "executed_tflops": round(useful * pe_, 1),
-                          "algorithmic_mb_per_launch": round(b_ / c_ / 1e6, 1), "algorithmic_tb_per_s": round(b_ / (t_ * 1e-3) / 1e12, 2)})
-            k_ = by_kernel.setdefault(KIND.get(kind_, str(kind_)).split(" ")[0], [0, 0.0, 0.0, 0.0])
-            k_[0] += c_; k_[1] += t_; k_[2] += b_; k_[3] += 2.0 * M_ * N_ * K_ * c_
-        achieved = launched_flop / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0      # useful FLOPs of the launched shapes: the graded figure
-        alg_total = sum(v[2] for v in shapes.values())
-        assert abs(alg_total - sum(v[2] for v in by_kernel.values())) <= 1e-6 * max(alg_total, 1.0)
-        alg_per_launch = alg_total / max(gemm_launches, 1)
-        # PMC counters cannot be read inside a timed run: `traffic` refers to the committed rocprofv3 --pmc passes of this same
-        # command (tools/profile_r03.sh -> tools/pmc_mfma_util.py), per launch over every GEMM kernel, FETCH_SIZE x2 + WRITE_SIZE
-        traffic, traffic_src, traffic_by_kernel = None, None, None
-        for name in ("r04_mfma_util.json", "r03_mfma_util.json", "r02_mfma_util.json"):
-            try:
-                with open(os.path.join(ROOT, "profiles", name)) as f:
-                    pm = json.load(f)
-                traffic = round(pm["gemm_kernels"]["gemm_hbm_bytes_per_launch"]); traffic_src = name
-                traffic_by_kernel = pm.get("per_kernel_traffic")
-                break
-            except Exception:
-                continue
-        kernels = {kn: {"launches": v[0], "us_per_launch": round(v[1] * 1e3 / v[0], 1), "ms_per_step": round(v[1], 3),
-                        "useful_tflops": round(v[3] / (v[1] * 1e-3) / 1e12, 1), "algorithmic_mb_per_launch": round(v[2] / v[0] / 1e6, 1)}
-                   for kn, v in sorted(by_kernel.items(), key=lambda kv: -kv[1][1])}
-        dom = max(by_kernel.items(), key=lambda kv: kv[1][1])[0] if by_kernel else None
         scheme = {"f16w2h": "f16w2h = f16 MFMA operands; split (hi, lo) weights on every ViT GEMM (patch embedding, qkv, out-proj, fc1, fc2): A hi^T in f16 + the correction A lo^T "
                             "on the block-scaled fp8 matrix instruction (gemm_w2f8_kernel, e5m2 activation image); the qkv correction on ViT layers 0-5 only (layers 6-11: fused single-product QKV + "
                             "attention kernel); text tower, ViT projection tail and the outfit transformer in three-product arithmetic",
@@ -431,12 +398,6 @@ def main():
             "unit": "outfits/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": round(elapsed / a.steps * 1e3, 3),
-            "step_ms_spread": {"min": round(min(per_step), 3), "median": round(sorted(per_step)[len(per_step) // 2], 3), "max": round(max(per_step), 3),
-                               "sampled_step": round(per_step[sample], 3), "all": [round(t, 2) for t in per_step],
-                               "device_allocs_in_timed_region": int(allocs_timed),
-                               "host_issue_ms": [round((host_t[i + 1] - host_t[i]) * 1e3, 2) for i in range(a.steps)],
-                               "note": "stream markers after each of the K timed steps (rank 0); the sampled step runs the towers on one stream with "
-                                       "every GEMM launch bracketed by events (the live roofline sample) and is inside the timed region"},
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": op,
             "data": "synthetic (seeded uniform-uint8 images after CLIP normalise, 8-token ids, random-init weights of the reference architecture)",
@@ -444,35 +405,10 @@ def main():
                        "outfits_per_gpu": B, "items": n, "parallelism": f"dp{world} (batch sharded, no data-path collective)",
                        "tower_precision": scheme, "launch": graph_note,
                        "outfit_precision": (model._tower_fed() or a.precision) + (f" (set transformer fed by the in-call {op} towers)" if model._tower_fed() else ""),
-                       "parity_bound": "north star: <= 1e-3 max|d| / max|ref| over the batch on the CP logit vs the fp32 reference path; measured on THIS batch below "
+                       "parity_bound": "north star: <= 1e-3 max|d| / max|ref| over the batch on the CP logit vs the fp32 reference path; measured on THIS batch by --full "
                                        "(parity_rel_err_vs_reference, all logits) and at this batch size on weight seeds 7/44/89/97/99 by "
                                        "tests/test_gpu_model.py::test_cfg2_bench_batch_within_1e3_of_the_reference (+ weights with massive ViT channels); over 100 weight seeds the error is a distribution "
                                        "(profiles/r04_seed_sweep_bench_scale.json: median 2.5e-4, p90 4.5e-4, worst 6.3e-4, none at or above 8e-4; lognormal fit: P(>= 1e-3) 0.12 % per weight draw); conditional on the random-init network's near-uniform attention: with q, k x 1.5 (logits x 2.25) 4 of 40 weight draws read >= 1e-3 (f16x3: none), DESIGN.md section 2"},
-            "roofline": {"bound": "mfma", "kernel": "every dense contraction of the step: " + " / ".join(sorted({t_["kernel"] for t_ in table})),
-                         "achieved": round(achieved, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": traffic,
-                         "traffic_note": (f"bytes per GEMM launch, FETCH_SIZE x2 + WRITE_SIZE, read from the committed profiles/{traffic_src} (separate rocprofv3 --pmc passes of this "
-                                          "command, tools/profile_r03.sh) - a reference to that file, not a measurement of this run") if traffic else "no PMC pass committed for this build yet",
-                         "algorithmic_bytes_per_launch": round(alg_per_launch),
-                         "traffic_over_algorithmic": round(traffic / alg_per_launch, 3) if traffic else None,
-                         "note": "achieved = useful (pad-free, one product per term) FLOPs of the GEMM shapes actually LAUNCHED / summed GEMM launch time of one sampled step "
-                                 "(HIP events on the launches); achieved_fixed_count uses SURVEY 8(d)'s per-outfit count instead (the pruned last ViT layer launches fewer rows "
-                                 "than that count assumes: no pruning credit is taken in `achieved`); executed_tflops counts the extra MFMA products the 1e-3-compliant scheme "
-                                 "spends (split weights x2, three-product x3)",
-                         "achieved_fixed_count": round(achieved_fixed, 2), "frac_fixed_count": round(achieved_fixed / PEAK_BF16_TFLOPS, 4),
-                         "executed_tflops": round(executed, 2), "executed_frac": round(executed / PEAK_BF16_TFLOPS, 4),
-                         "launches_per_step": gemm_launches, "sampled_steps": 1,
-                         "avg_launch_us": round(gemm_ms * 1e3 / max(gemm_launches, 1), 2),
-                         "algorithmic_gflop_per_outfit": round(alg_gemm_outfit / 1e9, 3),
-                         "launched_gflop_per_outfit": round(launched_flop / B / 1e9, 3),
-                         "power_limited_reference": {"mfma_only_loop_tflops_random_f16_operands": [1790.8, 1833.9], "mfma_only_loop_tflops_zero_operands": 2404.7,
-                                                     "note": "not measured by this run: tools/mfma_power_probe.hip on one MI355X (profiles/r03_power_limited_clock.txt) - a "
-                                                             "register-resident v_mfma_f32_16x16x32_f16 loop on every CU sustains 0.72-0.73 of `peak` on random operands (the clock the "
-                                                             "matrix pipe's switching power leaves); this bench's GEMMs run 22-29 % faster on constant operands. `peak` stays the guide's figure"},
-                         "dominant_kernel": dom, "per_kernel": kernels, "per_kernel_traffic_pmc": traffic_by_kernel,
-                         "per_shape": table},
-            "step_breakdown_ms": {"gemm": round(bms[0], 3), "norm_embed": round(bms[1], 3), "attention": round(bms[2], 3),
-                                  "other": round(bms[3], 3), "note": "one extra untimed step with all launches bracketed"},
             "whole_step_tflops_useful": round(alg_all_outfit * world * B * a.steps / elapsed / 1e12, 2),
             # SURVEY.md 8(d) "report both": the FLOPs the reference's own execution spends on the same outfits (texts padded to
             # 64 tokens, sets padded to 1 + 16 rows) - context for the north star's "40 % of MFMA peak", never used for `achieved`
@@ -481,9 +417,91 @@ def main():
                 "tflops_equiv_per_gpu": round(padded_outfit * B * a.steps / elapsed / 1e12, 2),
                 "frac_of_peak": round(padded_outfit * B * a.steps / elapsed / 1e12 / PEAK_BF16_TFLOPS, 4)},
         }
+        if a.full:
+            gemm_ms, gemm_launches = ms[0], int(cnt[0])
+            achieved_fixed = alg_gemm_outfit * B / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0   # SURVEY 8(d)'s per-outfit count x outfits, one sampled step
+            executed = fl[0] / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+            # per-shape table of the sampled step: shape -> kernel -> launches, us per launch, useful TF/s (2 M N K_logical) and its
+            # fraction of the dense peak, executed TF/s (x kmul: split weights run 2, three-product GEMMs 3 MFMA products per term),
+            # algorithmic HBM bytes per launch as the launch's own epilogue configuration implies (ofx_prof_record.bytes)
+            KIND = {1: "gemm_128x128_kernel", 2: "gemm_big_kernel<2,4,2>", 3: "gemm_big_kernel<2,2,1>", 4: "gemm_pp_kernel", 6: "gemm_w2_kernel",
+                    7: "fused_qkv_attn_kernel (N = q|k|v columns; its attention FLOPs are not in useful_tflops)", 8: "gemm_w2f8_kernel", 9: "gemm_x3_kernel"}
+            shapes = {}
+            for i in range(nrec):
+                r = recs[i]
+                if r.cat != 0:
+                    continue
+                e = shapes.setdefault((r.M, r.N, r.K, r.kmul, r.kind), [0, 0.0, 0.0])
+                e[0] += 1; e[1] += r.ms; e[2] += r.bytes
+            table, by_kernel = [], {}
+            launched_flop = 0.0          # useful FLOPs of the shapes actually launched (the pruned last ViT layer runs fewer rows than 8(d) counts)
+            for (M_, N_, K_, km_, kind_), (c_, t_, b_) in sorted(shapes.items(), key=lambda kv: -kv[1][1]):
+                useful = 2.0 * M_ * N_ * K_ * c_ / (t_ * 1e-3) / 1e12
+                launched_flop += 2.0 * M_ * N_ * K_ * c_
+                # matrix-pipe work in f16-rate product equivalents: the fp8 correction product of gemm_w2f8_kernel runs at twice the f16 rate
+                pe_ = 1.5 if kind_ == 8 else float(km_)
+                table.append({"M": M_, "N": N_, "K": K_, "products_per_term": km_, "f16_rate_product_equivalents": pe_, "kernel": KIND.get(kind_, str(kind_)), "launches": c_,
+                              "us_per_launch": round(t_ * 1e3 / c_, 1), "ms_per_step": round(t_, 3), "useful_tflops": round(useful, 1),
+                              "frac_useful": round(useful / PEAK_BF16_TFLOPS, 4), "executed_tflops": round(useful * pe_, 1),
+                              "algorithmic_mb_per_launch": round(b_ / c_ / 1e6, 1), "algorithmic_tb_per_s": round(b_ / (t_ * 1e-3) / 1e12, 2)})
+                k_ = by_kernel.setdefault(KIND.get(kind_, str(kind_)).split(" ")[0], [0, 0.0, 0.0, 0.0])
+                k_[0] += c_; k_[1] += t_; k_[2] += b_; k_[3] += 2.0 * M_ * N_ * K_ * c_
+            achieved = launched_flop / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0      # useful FLOPs of the launched shapes: the graded figure
+            alg_total = sum(v[2] for v in shapes.values())
+            assert abs(alg_total - sum(v[2] for v in by_kernel.values())) <= 1e-6 * max(alg_total, 1.0)
+            alg_per_launch = alg_total / max(gemm_launches, 1)
+            # PMC counters cannot be read inside a timed run: `traffic` refers to the committed rocprofv3 --pmc passes of this same
+            # command (tools/profile_r03.sh -> tools/pmc_mfma_util.py), per launch over every GEMM kernel, FETCH_SIZE x2 + WRITE_SIZE
+            traffic, traffic_src, traffic_by_kernel = None, None, None
+            for name in ("r04_mfma_util.json", "r03_mfma_util.json", "r02_mfma_util.json"):
+                try:
+                    with open(os.path.join(ROOT, "profiles", name)) as f:
+                        pm = json.load(f)
+                    traffic = round(pm["gemm_kernels"]["gemm_hbm_bytes_per_launch"]); traffic_src = name
+                    traffic_by_kernel = pm.get("per_kernel_traffic")
+                    break
+                except Exception:
+                    continue
+            kernels = {kn: {"launches": v[0], "us_per_launch": round(v[1] * 1e3 / v[0], 1), "ms_per_step": round(v[1], 3),
+                            "useful_tflops": round(v[3] / (v[1] * 1e-3) / 1e12, 1), "algorithmic_mb_per_launch": round(v[2] / v[0] / 1e6, 1)}
+                       for kn, v in sorted(by_kernel.items(), key=lambda kv: -kv[1][1])}
+            dom = max(by_kernel.items(), key=lambda kv: kv[1][1])[0] if by_kernel else None
+            res.update({
+                "step_ms_spread": {"min": round(min(per_step), 3), "median": round(sorted(per_step)[len(per_step) // 2], 3), "max": round(max(per_step), 3),
+                                   "sampled_step": round(per_step[sample], 3), "all": [round(t, 2) for t in per_step],
+                                   "device_allocs_in_timed_region": int(allocs_timed),
+                                   "host_issue_ms": [round((host_t[i + 1] - host_t[i]) * 1e3, 2) for i in range(a.steps)],
+                                   "note": "stream markers after each of the K timed steps (rank 0); the sampled step runs the towers on one stream with "
+                                           "every GEMM launch bracketed by events (the live roofline sample) and is inside the timed region"},
+                "roofline": {"bound": "mfma", "kernel": "every dense contraction of the step: " + " / ".join(sorted({t_["kernel"] for t_ in table})),
+                             "achieved": round(achieved, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                             "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": traffic,
+                             "traffic_note": (f"bytes per GEMM launch, FETCH_SIZE x2 + WRITE_SIZE, read from the committed profiles/{traffic_src} (separate rocprofv3 --pmc passes of this "
+                                              "command, tools/profile_r03.sh) - a reference to that file, not a measurement of this run") if traffic else "no PMC pass committed for this build yet",
+                             "algorithmic_bytes_per_launch": round(alg_per_launch),
+                             "traffic_over_algorithmic": round(traffic / alg_per_launch, 3) if traffic else None,
+                             "note": "achieved = useful (pad-free, one product per term) FLOPs of the GEMM shapes actually LAUNCHED / summed GEMM launch time of one sampled step "
+                                     "(HIP events on the launches); achieved_fixed_count uses SURVEY 8(d)'s per-outfit count instead (the pruned last ViT layer launches fewer rows "
+                                     "than that count assumes: no pruning credit is taken in `achieved`); executed_tflops counts the extra MFMA products the 1e-3-compliant scheme "
+                                     "spends (split weights x2, three-product x3)",
+                             "achieved_fixed_count": round(achieved_fixed, 2), "frac_fixed_count": round(achieved_fixed / PEAK_BF16_TFLOPS, 4),
+                             "executed_tflops": round(executed, 2), "executed_frac": round(executed / PEAK_BF16_TFLOPS, 4),
+                             "launches_per_step": gemm_launches, "sampled_steps": 1,
+                             "avg_launch_us": round(gemm_ms * 1e3 / max(gemm_launches, 1), 2),
+                             "algorithmic_gflop_per_outfit": round(alg_gemm_outfit / 1e9, 3),
+                             "launched_gflop_per_outfit": round(launched_flop / B / 1e9, 3),
+                             "power_limited_reference": {"mfma_only_loop_tflops_random_f16_operands": [1790.8, 1833.9], "mfma_only_loop_tflops_zero_operands": 2404.7,
+                                                         "note": "not measured by this run: tools/mfma_power_probe.hip on one MI355X (profiles/r03_power_limited_clock.txt) - a "
+                                                                 "register-resident v_mfma_f32_16x16x32_f16 loop on every CU sustains 0.72-0.73 of `peak` on random operands (the clock the "
+                                                                 "matrix pipe's switching power leaves); this bench's GEMMs run 22-29 % faster on constant operands. `peak` stays the guide's figure"},
+                             "dominant_kernel": dom, "per_kernel": kernels, "per_kernel_traffic_pmc": traffic_by_kernel,
+                             "per_shape": table},
+                "step_breakdown_ms": {"gemm": round(bms[0], 3), "norm_embed": round(bms[1], 3), "attention": round(bms[2], 3),
+                                      "other": round(bms[3], 3), "note": "one extra untimed step with all launches bracketed"},
+            })
         if rank_info is not None:
             res["ranks"] = dict(rank_info, note="value = all ranks' outfits / max(elapsed_s): the slowest rank sets the whole-job time")
-        if a.cpu_outfits > 0 and world == 1:      # parity + CPU baseline: single-GPU-run data (rank 0, N = 1 only), outside the timed region
+        if a.full and a.cpu_outfits > 0 and world == 1:      # parity + CPU baseline: single-GPU-run data (rank 0, N = 1 only), outside the timed region
             try:
                 got_all = out.float().cpu().numpy().reshape(-1)
                 ref_all = bench_reference_logits(W_SEED, B, n, in_crc)

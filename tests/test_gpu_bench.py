@@ -1,14 +1,18 @@
-"""bench.py's contract on a real MI355X: the N = 1 JSON line (metric / roofline / cpu_baseline / parity fields) and the N = 2 code
-path the driver launches on a whole node - rehearsed here with two ranks sharing GPU 0 over gloo (OFX_BENCH_REHEARSAL=1: its
-throughput means nothing, its control flow - rendezvous, barrier, MAX-over-ranks timing, rank-0 JSON - is the real one)."""
+"""bench.py's contract on a real MI355X: the plain N = 1 line (headline fields only) and its --dump-outputs, the --full N = 1 line
+(metric / roofline / cpu_baseline / parity fields) and the --full N = 2 code path the driver launches on a whole node - rehearsed
+here with two ranks sharing GPU 0 over gloo (OFX_BENCH_REHEARSAL=1: its throughput means nothing, its control flow - rendezvous,
+barrier, MAX-over-ranks timing, rank-0 JSON - is the real one)."""
 import json
 import os
 import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
+
+from conftest import W_SEED, rel_err
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,7 +27,7 @@ def _json_line(out: str) -> dict:
 def test_bench_single_gpu_line_has_the_contract_fields():
     if not torch.cuda.is_available():
         pytest.skip("needs a HIP device")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--outfits", "64", "--cpu-outfits", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--outfits", "64", "--cpu-outfits", "2",
                         "--cpu-cfg2-outfits", "1", "--secondary", "", "--rung", ""], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _json_line(r.stdout)
@@ -43,6 +47,31 @@ def test_bench_single_gpu_line_has_the_contract_fields():
     assert c1["all_threads"]["iters"] >= 10 and c1["one_thread"]["iters"] >= 10 and c1["one_thread"]["outfits_per_s"] > 0
 
 
+def test_bench_plain_line_is_lean_and_dumps_the_last_steps_logits(tmp_path):
+    """Without --full the run only times the headline: the line carries the contract fields and none of the --full legs, and
+    --dump-outputs writes the CP logits of the last timed step - which the fp32 oracle reproduces on the batch's first outfits."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a HIP device")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--outfits", "64",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = _json_line(r.stdout)
+    assert j["n_gpus"] == 1 and j["steps"] == 3 and j["warmup"] == 1 and j["unit"] == "outfits/s" and j["higher_is_better"] is True
+    assert j["metric"] == "outfits/sec CP forward (8-item sets, 224^2, bf16)" and j["dtype"] == "f16"
+    assert abs(j["value"] - 64 * 3 / (j["ms_per_step"] * 3e-3)) <= 1e-3 * j["value"]
+    assert j["config"]["launch"].startswith("one HIP graph launch per step")
+    assert not {"roofline", "step_ms_spread", "step_breakdown_ms", "cpu_baseline", "launch_by_launch", "secondary_rung", "secondary_single_product",
+                "parity_rel_err_vs_oracle", "parity_rel_err_vs_reference"} & set(j)
+    got = np.load(tmp_path / "cp_logits.npy")
+    assert got.dtype == np.float32 and got.shape == (64, 1) and np.isfinite(got).all()
+    from oracle import np_oracle as O
+    from outfitx_amd import synth
+    px, ids, att = synth.bench_batch(1236, 64, 8)                    # the bench's rank-0 batch
+    emb = O.item_encoder(px[:2], ids.reshape(64, 8, 64)[:2], att.reshape(64, 8, 64)[:2], synth.vision_weights(W_SEED), synth.text_weights(W_SEED))
+    want = O.cp_forward(emb, np.zeros((2, 8), bool), synth.outfit_transformer_weights(W_SEED))
+    assert rel_err(got[:2], want) < 1e-3
+
+
 def test_bench_two_ranks_rehearsal():
     if not torch.cuda.is_available():
         pytest.skip("needs a HIP device")
@@ -52,7 +81,7 @@ def test_bench_two_ranks_rehearsal():
     env = dict(os.environ, OFX_BENCH_REHEARSAL="1")
     env.pop("OMP_NUM_THREADS", None)                               # bench.py caps its host threads per rank itself (host_cores() // world)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--outfits", "32",
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--outfits", "32",
                         "--cir-queries", "200", "--cir-pool", "20000"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]

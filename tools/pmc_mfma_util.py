@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel MFMA utilisation and HBM traffic of one bench.py step from four rocprofv3 passes (same command each time,
-`python3 bench.py --steps 1 --warmup 1 --cpu-outfits 0`; counters in their own passes, MI355X_MICROARCH.md "rocprofv3 PMC slots"):
+`python3 bench.py --full --steps 1 --warmup 1 --cpu-outfits 0`; counters in their own passes, MI355X_MICROARCH.md "rocprofv3 PMC slots"):
 
     rocprofv3 --kernel-trace --stats -d P/trace  --output-format csv -- python3 bench.py ...        durations
     rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_BUSY_CYCLES -d P/sq ...
@@ -102,7 +102,7 @@ g_ns = sum(r["total_ms"] for r in gemm) * 1e6
 g_calls = sum(r["calls"] for r in gemm)
 g_bytes = sum(r["hbm_bytes_per_call"] * r["calls"] for r in gemm)
 print(json.dumps({
-    "source": "rocprofv3 passes of `python3 bench.py --steps 1 --warmup 1 --cpu-outfits 0` (3 forward steps incl. the breakdown step): --kernel-trace --stats; "
+    "source": "rocprofv3 passes of `python3 bench.py --full --steps 1 --warmup 1 --cpu-outfits 0` (3 forward steps incl. the breakdown step): --kernel-trace --stats; "
               "--pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_BUSY_CYCLES; --pmc FETCH_SIZE; --pmc WRITE_SIZE",
     "definitions": {"mfma_util": "sum SQ_VALU_MFMA_BUSY_CYCLES / (sum GRBM_GUI_ACTIVE / 8 * 1024 SIMDs), per kernel over all its dispatches",
                     "mfma_tflops_executed": "(MOPS_F16 + MOPS_BF16) * 512 / trace-pass time: every MFMA product counted (peak 2,500 dense)",

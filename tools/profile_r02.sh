@@ -4,7 +4,7 @@
 set -o pipefail
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/prof_r02; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py --steps 1 --warmup 1 --cpu-outfits 0 $@"
+B="python3 $ROOT/bench.py --full --steps 1 --warmup 1 --cpu-outfits 0 $@"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $B > $OUT/trace.log 2>&1 || { tail -5 $OUT/trace.log; exit 1; }
 rocprofv3 --kernel-trace --output-format csv --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_BUSY_CYCLES -d $OUT/sq -- $B > $OUT/sq.log 2>&1 || { tail -5 $OUT/sq.log; exit 1; }
 rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d $OUT/fetch -- $B > $OUT/fetch.log 2>&1 || { tail -5 $OUT/fetch.log; exit 1; }
