@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define OFX_ABI_VERSION 5
+#define OFX_ABI_VERSION 6
 
 enum { OFX_OK = 0, OFX_EINVAL = -1, OFX_ESHAPE = -2, OFX_EHIP = -3, OFX_EWORKSPACE = -4, OFX_ESTATE = -5 };
 enum ofx_dtype { OFX_F32 = 0, OFX_BF16 = 1, OFX_F16 = 2 };
@@ -249,29 +249,26 @@ int ofx_profile_read(double* ms, double* flops, long long* launches);
 typedef struct ofx_prof_record { int cat, M, N, K, kind, kmul; float ms; double flops; double bytes; } ofx_prof_record;
 int ofx_profile_records(ofx_prof_record* out, int cap);
 
-/* Process-wide tuning knobs (benchmarks / tests only).  knob 0: GEMM rasterisation group (row panels per L2 group, default 8);
+/* Process-wide tuning knobs (benchmarks / tests only).  Unknown knobs return OFX_EINVAL.
+ * knob 2: GEMM kernel, 0 (default) = the automatic choice, 1 = 128x128, 2 = 256x256, 3 = 256x128, 4 = 256x256 ping-pong, 5 = 64x128,
+ *         6 = the dual-weight 256x256 kernel for split weights (every other GEMM keeps the automatic choice);
+ * knob 5: split-K of small GEMMs, 1 (default) = planned, 0 = never, >= 2 = forced (low byte = splits, bit 8 = 64-row tiles);
  * knob 6: 2 (default) folds the CLIP towers' LayerNorms into the neighbouring GEMM epilogues AND keeps their residual stream as an
  * operand-type (hi, lo) pair updated in place (no fp32 stream between the layers), 1 folds with an fp32 stream, 0 materialises them;
+ * knob 7: 1 (default) single-product precisions (training; scoring in bf16 / f16) run the MFMA varlen attention, 0 the fp32 set kernels;
  * knob 8: 1 (default) the ViT's last layer computes queries for the CLS rows only, 0 runs the full QKV GEMM;
  * knob 9: bit 0 (default on) / bit 1 (default off): ViT layers with single-product / split (hi, lo) q | k | v weights run the fused
  *         QKV-projection + attention kernel; cleared: the GEMM -> HBM -> attention-kernel pair;
  * knob 10: 1 (default) small-batch outfit-transformer GEMMs (split-K plans) leave their second pass to the consumer kernel (set
  *          attention sums the q | k | v slabs; reduce + LayerNorm in one launch), 0 the separate reduce and LayerNorm launches;
- * knob 12: 1 (default) split-weight GEMMs with an fp8 copy of their lo halves run the fp8 correction product, 0 = the f16 one;
- * knob 13: log2 of the activation scale of that product (default 0 with the e5m2 activation image of round 4; 2 in an e4m3 build, -DOFX_F8_ABF8=0).
- * knob 15: three-product GEMMs: 1 (default) the operand-tiles-loaded-once kernel from 192 tiles on, 2 always, 0 never.
- * knob 14: 1 = the persistent split-weight GEMMs launch the smallest grid that finishes in the same number of rounds (the CUs left alone
- * serve the side stream's kernels); default 0 = one block per CU (the trimmed grid measured 0.4 ms per step slower).
  * knob 11: grid size of the persistent dual-weight GEMM (default -1 = one block per CU of the device, each walking its tiles and
  *          fetching the next tile's first k-steps under the current epilogue), 0 = one block per tile.
+ * knob 15: three-product GEMMs: 1 (default) the operand-tiles-loaded-once kernel from 192 tiles on, 2 always, 0 never.
  * knob 16: 1 (default) gemm_x3_kernel launches one block per CU walking its tiles, 0 = one block per tile (short-lived blocks).
  * knob 17: 1 (default) ofx_l2_topk on pools of >= 32,768 rows runs sample + filter (the distance matrix is never written), 0 = always
  *          distance matrix + radix select.  Same results either way.
  * knob 18: 1 (default) the split-weight GEMM's f16 outputs (qkv, fc1) are stored straight from the accumulator layout, 0 = through the LDS
- *          transpose of rounds 1-3, 2 = as 1 with whole-line stores (8 rows x 128 B per instruction after a DPP row exchange; measured level
- *          with 1: profiles/r04_epilogue_wide_skew.txt).  Bit-identical results.
- * knob 19: experiment, default 0: start skew of gemm_w2f8_kernel's blocks by XCD (v > 0: odd XCDs start v x ~2,000 cycles late, v < 0:
- *          XCD x starts x |v| x ~2,000 cycles late).  Results unchanged; no setting was faster (same file).
+ *          transpose of rounds 1-3; any other value is OFX_EINVAL.  Bit-identical results.
  * knob 20: validation only, default 0: 1 = a three-product ViT (vit_x3) keeps q | k | v in fp32 and runs the fp32 attention kernel instead of the MFMA attention
  *          on operand-rounded q | k | v (several times slower; tools/parity_selfcheck.py uses it for its reference run). */
 int ofx_tune(int knob, int value);
@@ -284,8 +281,6 @@ int ofx_profile_enabled(void);
  * beside the ViT on the caller's stream, so that its workgroups take CUs only when the caller's stream has none ready.  Caller destroys it. */
 int ofx_stream_create_low_priority(int device, ofx_stream* out);
 int ofx_stream_destroy(ofx_stream stream);
-/* Diagnostics: when buf != NULL the big-tile GEMM writes {shader cycles, 100 MHz ticks} of its main loop per block (16 B each). */
-void ofx_debug_gemm_clock(void* buf);
 
 /* ------------------------------------------------------------------ op level (tests) ------- */
 int ofx_gemm(const void* A, const void* W, void* C, const float* bias, const float* resid, int M, int N, int K,

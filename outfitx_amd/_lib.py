@@ -9,11 +9,11 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# OFX_LIB: an alternative build of the SAME library (tools only: the ablation build `make DIAG=1 LIB=outfitx_amd/libofx_hip_diag.so OBJ=build/obj_diag`)
+# OFX_LIB: an alternative build of the SAME library (tools only, e.g. `make EXTRA=... LIB=outfitx_amd/libofx_hip_alt.so OBJ=build/obj_alt`)
 LIB_PATH = os.environ.get("OFX_LIB") or os.path.join(_HERE, "libofx_hip.so")
 
 OFX_OK = 0
-ABI_VERSION = 5          # include/ofx.h OFX_ABI_VERSION
+ABI_VERSION = 6          # include/ofx.h OFX_ABI_VERSION
 F32, BF16, F16 = 0, 1, 2
 ACT_NONE, ACT_QUICK_GELU, ACT_GELU, ACT_MISH = 0, 1, 2, 3
 PREC_BF16, PREC_F16, PREC_BF16X3 = 0, 1, 2
@@ -161,7 +161,6 @@ SIGNATURES = {
     "ofx_tune": (_i, [_i, _i]),
     "ofx_config_generation": (C.c_uint, []),
     "ofx_profile_enabled": (_i, []),
-    "ofx_debug_gemm_clock": (None, [_vp]),
     "ofx_gemm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ofx_gemm_w2": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ofx_gemm_x3": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -1362,19 +1362,12 @@ extern "C" int ofx_focal_loss_ex(const float* logits, const float* labels, int B
 }
 
 // ------------------------------------------------------------------------------------- tuning
-extern int g_topk_filter, g_epi_direct, g_w2f8_skew;
-extern int g_gemm_group_m, g_gemm_ablate, g_gemm_kernel, g_gemm_skew, g_gemm_pref, g_gemm_splitk, g_w2_persist, g_w2_fp8, g_w2_fp8_ashift, g_w2_trim, g_x3_kernel, g_x3_persist;
-extern unsigned long long* g_gemm_dbg;
-/* diagnostics: per-block {shader cycles, 100 MHz ticks} of the big-tile GEMM main loop go to buf (device, 16 B per block); NULL = off */
-extern "C" void ofx_debug_gemm_clock(void* buf) { g_gemm_dbg = (unsigned long long*)buf; }
+extern int g_topk_filter, g_epi_direct;
+extern int g_gemm_kernel, g_gemm_splitk, g_w2_persist, g_x3_kernel, g_x3_persist;
 extern "C" int ofx_tune(int knob, int value) {
     ++g_config_generation;
     switch (knob) {
-        case 0: g_gemm_group_m = value; return OFX_OK;
-        case 1: g_gemm_ablate = value; return OFX_OK;
         case 2: g_gemm_kernel = value; return OFX_OK;
-        case 3: g_gemm_skew = value; return OFX_OK;
-        case 4: g_gemm_pref = value; return OFX_OK;
         case 5: g_gemm_splitk = value; return OFX_OK;
         case 6: g_ln_fold = value; return OFX_OK;
         case 7: g_train_mfma_attn = value; return OFX_OK;
@@ -1382,15 +1375,11 @@ extern "C" int ofx_tune(int knob, int value) {
         case 9: g_fuse_qkv = value; return OFX_OK;
         case 10: g_set_fuse = value; return OFX_OK;
         case 11: g_w2_persist = value; return OFX_OK;
-        case 12: g_w2_fp8 = value; return OFX_OK;
-        case 14: g_w2_trim = value; return OFX_OK;
         case 15: g_x3_kernel = value; return OFX_OK;
         case 16: g_x3_persist = value != 0; return OFX_OK;
         case 17: g_topk_filter = value != 0; return OFX_OK;
-        case 18: g_epi_direct = value < 0 ? 0 : (value > 2 ? 2 : value); return OFX_OK;
-        case 19: g_w2f8_skew = value; return OFX_OK;
+        case 18: if (value != 0 && value != 1) { ofx_set_error("ofx_tune(18): %d is not 0 or 1", value); return OFX_EINVAL; } g_epi_direct = value; return OFX_OK;
         case 20: g_x3_vit_f32_attn = value != 0; return OFX_OK;
-        case 13: if (value < -8 || value > 8) { ofx_set_error("ofx_tune(13): activation shift out of [-8, 8]"); return OFX_EINVAL; } g_w2_fp8_ashift = value; return OFX_OK;
         default: ofx_set_error("ofx_tune: unknown knob %d", knob); return OFX_EINVAL;
     }
 }

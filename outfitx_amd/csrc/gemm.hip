@@ -22,7 +22,7 @@ int g_gemm_splitk = 1;     // 0 disables split-K
 namespace {
 // MT = MFMA row tiles per wave: 4 -> the 128x128 block tile, 2 -> 64x128 (twice the blocks for grids that leave CUs idle: the
 // training step's M ~ 2k-row GEMMs with N = 1024; 48 KiB of LDS, three blocks per CU)
-template <typename T, int ABL, int MT = 4>   // ABL: 0 product kernel; 1 no LDS-DMA; 2 no MFMA; 3 no LDS fragment reads (diagnostics, wrong results)
+template <typename T, int MT = 4>
 __global__ __launch_bounds__(256, 2) void gemm_128x128_kernel(KArgs p) {
     constexpr int BMT = 32 * MT, STAGE_T = (BMT + BN) * BK * 2, EPI_T = 16 * MT * EPI_STRIDE * 4;
     typedef typename OpT<T>::v8 v8;
@@ -78,7 +78,6 @@ __global__ __launch_bounds__(256, 2) void gemm_128x128_kernel(KArgs p) {
     const int a_dst = wave * MT * 1024, w_dst = BMT * BK * 2 + wave * 4 * 1024;
 
     auto issue = [&](int kt, int stage) {
-        if (ABL == 1) return;
         OFX_LDS char* base = lds + stage * STAGE_T;
         const size_t koff = (size_t)kt * BK * 2, koff_a = (size_t)(kt % p.ka_tiles) * BK * 2;
 #pragma unroll
@@ -121,9 +120,9 @@ __global__ __launch_bounds__(256, 2) void gemm_128x128_kernel(KArgs p) {
         for (int ks = 0; ks < 2; ++ks) {
             const int chk = ((ks * 4 + fq) ^ fsw) * 16;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) if (ABL != 3 || kt == kt0) wf[ks][j] = *(OFX_LDS v8*)(base + w_frag + j * 16 * 128 + chk);
+            for (int j = 0; j < 4; ++j) wf[ks][j] = *(OFX_LDS v8*)(base + w_frag + j * 16 * 128 + chk);
 #pragma unroll
-            for (int i = 0; i < MT; ++i) if (ABL != 3 || kt == kt0) af[ks][i] = *(OFX_LDS v8*)(base + a_frag + i * 16 * 128 + chk);
+            for (int i = 0; i < MT; ++i) af[ks][i] = *(OFX_LDS v8*)(base + a_frag + i * 16 * 128 + chk);
         }
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -131,10 +130,7 @@ __global__ __launch_bounds__(256, 2) void gemm_128x128_kernel(KArgs p) {
 #pragma unroll
             for (int i = 0; i < MT; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (ABL == 2) { asm volatile("" :: "v"(wf[ks][j]), "v"(af[ks][i])); }
-                    else acc[i][j] = OpT<T>::mfma16(wf[ks][j], af[ks][i], acc[i][j]);
-                }
+                for (int j = 0; j < 4; ++j) acc[i][j] = OpT<T>::mfma16(wf[ks][j], af[ks][i], acc[i][j]);
         __builtin_amdgcn_s_setprio(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -208,22 +204,11 @@ size_t ofx_gemm_splitk_bytes(int M, int N, int K) {
 }
 
 
-int g_w2f8_skew = 0;      // ofx_tune(19, v): start skew of gemm_w2f8_kernel's blocks by XCD (experiment; KArgs::skew)
 int g_epi_direct = 1;     // ofx_tune(18, v): 1 (default) gemm_w2f8_kernel's operand-type outputs leave straight from the accumulator layout (epilogue_direct), 0 = through LDS
-int g_gemm_group_m = 0;   // 0 = adaptive
-int g_gemm_ablate = 0;    // diagnostics only (tools/gemm_bench.py)
-unsigned long long* g_gemm_dbg = nullptr;   // diagnostics only
-int g_gemm_pref = 2;      // short-K big GEMMs: 0 -> 256x128 kernel, 1 -> 256x256, 2 -> 256x256 ping-pong
-int g_w2_fp8 = 1;         // split-weight GEMMs that carry an fp8 copy of their lo halves run the fp8 correction product (gemm_w2f8.hip); 0 = the f16 one, ofx_tune(12, v)
-int ofx_w2f8_act_is_bf8();
-int g_w2_fp8_ashift = -99; // activations enter the fp8 product as fp8(a 2^shift), ofx_tune(13, v); -99 = the build's default: 0 for the e5m2 image (f16's exponent
-                          // range, nothing to choose), 2 for the e4m3 build (-DOFX_F8_ABF8=0: keeps |a| >= 2^-8 out of the subnormal step and saturates at 112)
 int g_x3_persist = 1;     // ofx_tune(16, v): 1 (default) gemm_x3_kernel launches one block per CU walking its tiles (when it has more tiles than CUs), 0 = one block per tile
 int g_x3_kernel = 1;      // three-product GEMMs (k_mult == 3: A rows [hi | lo | hi], W rows [hi | hi | lo]): 1 = the operand-tiles-loaded-once 256x128 kernel
                           // (gemm_x3.hip) from 192 tiles on, 2 = always, 0 = the K-concatenated single-product kernels; ofx_tune(15, v)
-int g_w2_trim = 0;        // 1: persistent split-weight GEMMs shrink their grid to the smallest one with the same round count (measured: +0.4 ms per step), ofx_tune(14, v)
 int g_w2_persist = -1;    // dual-weight kernel: persistent grid size (blocks walk tiles b, b + grid, ...): -1 = one block per CU of the device, 0 = one block per tile, ofx_tune(11, v)
-int g_gemm_skew = 0;      // start skew of the second co-resident block (x 8128 cycles), 256x128 kernel only
 int g_gemm_kernel = 0;    // 0 auto, 1 force 128x128, 2 force 256x256 (8 waves, 2 stages), 3 force 256x128 (4 waves, register-resident k-tile), 4 force 256x256 ping-pong, 6 force the dual-weight 256x256 kernel for split weights
 
 int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
@@ -238,13 +223,10 @@ int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
     OFX_REQUIRE(((uintptr_t)g.A % 16 == 0) && ((uintptr_t)g.W % 16 == 0) && ((uintptr_t)g.C % 16 == 0), OFX_EINVAL,
                 "gemm: operands must be 16-byte aligned");
     OFX_REQUIRE(op_dtype == OFX_BF16 || op_dtype == OFX_F16, OFX_EINVAL, "gemm: operand dtype must be bf16 or f16");
-#ifndef OFX_DIAG
-    OFX_REQUIRE(g_gemm_ablate == 0, OFX_ESTATE, "gemm: the ablation kernels are only built with `make DIAG=1`");
-#endif
     if (g.defer_splits) *g.defer_splits = 1;
     if (g.ln_done) *g.ln_done = false;
     KArgs k;
-    k.A = (const char*)g.A; k.W = (const char*)g.W; k.C = (char*)g.C; k.bias = g.bias; k.resid = g.resid; k.aux_out = g.aux_out; k.m_dev = g.m_dev; k.dbg = g_gemm_dbg; k.skew = g_gemm_skew; k.splits = 1; k.slab = nullptr; k.m_slab = g.M; k.kt_per_split = 0;
+    k.A = (const char*)g.A; k.W = (const char*)g.W; k.C = (char*)g.C; k.bias = g.bias; k.resid = g.resid; k.aux_out = g.aux_out; k.m_dev = g.m_dev; k.splits = 1; k.slab = nullptr; k.m_slab = g.M; k.kt_per_split = 0;
     k.ka_tiles = ka / BK;
     k.M = g.M; k.N = g.N; k.K = g.K; k.lda = g.lda; k.ldc = g.ldc; k.ldr = g.ldr; k.act = g.act; k.out_kind = g.out_kind; k.drop = g.drop; k.n_valid = g.N;
     k.xb_out = (char*)g.xb_out; k.stat_part = g.stat_part; k.row_stat = g.row_stat; k.col_sum = g.col_sum; k.stat_ld = g.stat_ld > 0 ? g.stat_ld : 1; k.xlo = (char*)g.xlo;
@@ -258,15 +240,10 @@ int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
     OFX_REQUIRE(!(g.xb_out || g.stat_part) || g.act == OFX_ACT_NONE, OFX_EINVAL, "gemm: a LayerNorm-fold producer has no activation");
     static DeviceOnce attr_set;
     TRY(attr_set.run([]() -> int {
-        OFX_HIP(hipFuncSetAttribute((const void*)gemm_128x128_kernel<bf16_t, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES));
-        OFX_HIP(hipFuncSetAttribute((const void*)gemm_128x128_kernel<f16_t, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES));
-        OFX_HIP(hipFuncSetAttribute((const void*)gemm_128x128_kernel<bf16_t, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM64_LDS_BYTES));
-        OFX_HIP(hipFuncSetAttribute((const void*)gemm_128x128_kernel<f16_t, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM64_LDS_BYTES));
-#ifdef OFX_DIAG
-        OFX_HIP(hipFuncSetAttribute((const void*)gemm_128x128_kernel<bf16_t, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES));
-        OFX_HIP(hipFuncSetAttribute((const void*)gemm_128x128_kernel<bf16_t, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES));
-        OFX_HIP(hipFuncSetAttribute((const void*)gemm_128x128_kernel<bf16_t, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES));
-#endif
+        OFX_HIP(hipFuncSetAttribute((const void*)gemm_128x128_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES));
+        OFX_HIP(hipFuncSetAttribute((const void*)gemm_128x128_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES));
+        OFX_HIP(hipFuncSetAttribute((const void*)gemm_128x128_kernel<bf16_t, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM64_LDS_BYTES));
+        OFX_HIP(hipFuncSetAttribute((const void*)gemm_128x128_kernel<f16_t, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM64_LDS_BYTES));
         return OFX_OK;
     }));
     // big tiles when they still fill the chip, else the 128^2 kernel
@@ -274,11 +251,11 @@ int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
     if (g.a_wrap) {        // split weights: the dual-weight 256x256 kernel when its grid fills the chip, else the 128x128 kernel with a wrapping A index
         const long t2 = (long)((g.M + 255) / 256) * (g.N / 256);
         kind = (g.K == 2 * g.a_wrap && g.a_wrap % 32 == 0 && g.a_wrap >= 64 && g.N % 256 == 0 && (t2 >= 256 || g_gemm_kernel == 6) && g_gemm_kernel != 1) ? 6 : 1;
-        // the correction product on the fp8 matrix instruction (ofx_tune(12, 0) keeps the f16 one)
-        if (kind == 6 && g.W8 && g.w8_scale && g_w2_fp8 && op_dtype == OFX_F16 && g.a_wrap % 128 == 0) kind = 8;
+        // the correction product on the fp8 matrix instruction
+        if (kind == 6 && g.W8 && g.w8_scale && op_dtype == OFX_F16 && g.a_wrap % 128 == 0) kind = 8;
     } else if (kind == 0) {   // measured crossover points (tools/gemm_bench.py, profiles/r01_gemm_variants.txt)
         const long t2 = (long)((g.M + 255) / 256) * (g.N / 256), t3 = (long)((g.M + 255) / 256) * (g.N / 128);
-        if (g.N % 256 == 0 && t2 >= 1024 && (g.K > 1024 || g_gemm_pref >= 1)) kind = g_gemm_pref == 2 && g.K <= 1024 ? 4 : 2;   // 256x256, one block per CU
+        if (g.N % 256 == 0 && t2 >= 1024) kind = g.K <= 1024 ? 4 : 2;   // 256x256, one block per CU (short K: the ping-pong kernel)
         else if (g.N % 128 == 0 && t3 >= 512) kind = 3;                    // short K / mid-size M: 256x128, two blocks per CU
         else kind = 1;
     }
@@ -304,22 +281,21 @@ int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
     // executed FLOPs in f16-rate equivalents: the fp8 correction product of kind 8 runs at twice the f16 rate (1.5 products, not 2)
     ProfScope prof(PROF_GEMM, s, 2.0 * g.M * g.N * g.K * (kind == 8 ? 0.75 : 1.0), true);      // events ride on the launches (OFX_PLAUNCH)
     if (kind == 2 || kind == 3 || kind == 4 || kind == 6 || kind == 8 || kind == 9) {
-        k.group_m = g_gemm_group_m > 0 ? g_gemm_group_m : (kind == 3 ? 4 : 8);
+        k.group_m = kind == 3 ? 4 : 8;
         int rc;
         if (kind == 8) {
-            const int ash = g_w2_fp8_ashift == -99 ? (ofx_w2f8_act_is_bf8() ? 0 : 2) : g_w2_fp8_ashift;
-            k.W8 = (const char*)g.W8; k.w8_scale = (const char*)g.w8_scale; k.a8_scale = ldexpf(1.0f, -ash); k.a8_e8m0 = 127 - ash; rc = ofx_gemm_launch_w2f8(&k, g.M, g.N, s);
+            k.W8 = (const char*)g.W8; k.w8_scale = (const char*)g.w8_scale; rc = ofx_gemm_launch_w2f8(&k, g.M, g.N, s);
         }
         else if (kind == 9) rc = ofx_gemm_launch_x3(&k, op_dtype, g.M, g.N, s);
         else if (kind == 6) rc = ofx_gemm_launch_w2(&k, op_dtype, g.M, g.N, s);
         else if (kind == 4) rc = ofx_gemm_launch_pp(&k, op_dtype, g.M, g.N, s);
-        else rc = ofx_gemm_launch_big(&k, kind, g_gemm_ablate, op_dtype, g.M, g.N, s);
+        else rc = ofx_gemm_launch_big(&k, kind, op_dtype, g.M, g.N, s);
         if (rc != OFX_OK) return rc;
     } else {
         k.tiles_n = g.N / BN; k.tiles_m = (g.M + BM - 1) / BM; k.nwg = k.tiles_m * k.tiles_n;
         // row panels per L2 group: (group_m + 64/group_m) panels of 128 x K operands should fit ~3 MiB of the XCD's L2
-        int gm = g_gemm_group_m;
-        if (gm <= 0) { gm = (int)((3u << 20) / ((size_t)BM * g.K * 2) / 2); gm = gm < 1 ? 1 : (gm > 8 ? 8 : gm); }
+        int gm = (int)((3u << 20) / ((size_t)BM * g.K * 2) / 2);
+        gm = gm < 1 ? 1 : (gm > 8 ? 8 : gm);
         k.group_m = gm;
         const bool can_split = g.slab && !g.xb_out && !g.stat_part && !g.row_stat;
         const bool can64 = (kind == 5) || (kind == 1 && g_gemm_kernel == 0 && g.M > 64 && (long)k.tiles_m * k.tiles_n <= 384);
@@ -349,21 +325,16 @@ int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
             k.tiles_m = (g.M + 63) / 64; k.nwg = k.tiles_m * k.tiles_n; k.group_m = 2 * gm;
             const dim3 grid64(k.nwg, splits);
             const bool one64 = splits <= 1 || g.defer_splits;      // the launch that carries the profile record's stop event
-            if (op_dtype == OFX_F16) OFX_PLAUNCH(one64, (gemm_128x128_kernel<f16_t, 0, 2>), grid64, dim3(256), GEMM64_LDS_BYTES, s, k);
-            else OFX_PLAUNCH(one64, (gemm_128x128_kernel<bf16_t, 0, 2>), grid64, dim3(256), GEMM64_LDS_BYTES, s, k);
+            if (op_dtype == OFX_F16) OFX_PLAUNCH(one64, (gemm_128x128_kernel<f16_t, 2>), grid64, dim3(256), GEMM64_LDS_BYTES, s, k);
+            else OFX_PLAUNCH(one64, (gemm_128x128_kernel<bf16_t, 2>), grid64, dim3(256), GEMM64_LDS_BYTES, s, k);
             if (splits > 1) TRY(second_pass());
             OFX_LAUNCH_CHECK();
             return OFX_OK;
         }
         const dim3 grid(k.nwg, splits > 1 ? splits : 1);
         const bool one = splits <= 1 || g.defer_splits;
-        if (op_dtype == OFX_F16) OFX_PLAUNCH(one, (gemm_128x128_kernel<f16_t, 0>), grid, dim3(256), GEMM_LDS_BYTES, s, k);
-#ifdef OFX_DIAG
-        else if (g_gemm_ablate == 1) OFX_PLAUNCH(one, (gemm_128x128_kernel<bf16_t, 1>), grid, dim3(256), GEMM_LDS_BYTES, s, k);
-        else if (g_gemm_ablate == 2) OFX_PLAUNCH(one, (gemm_128x128_kernel<bf16_t, 2>), grid, dim3(256), GEMM_LDS_BYTES, s, k);
-        else if (g_gemm_ablate == 3) OFX_PLAUNCH(one, (gemm_128x128_kernel<bf16_t, 3>), grid, dim3(256), GEMM_LDS_BYTES, s, k);
-#endif
-        else OFX_PLAUNCH(one, (gemm_128x128_kernel<bf16_t, 0>), grid, dim3(256), GEMM_LDS_BYTES, s, k);
+        if (op_dtype == OFX_F16) OFX_PLAUNCH(one, gemm_128x128_kernel<f16_t>, grid, dim3(256), GEMM_LDS_BYTES, s, k);
+        else OFX_PLAUNCH(one, gemm_128x128_kernel<bf16_t>, grid, dim3(256), GEMM_LDS_BYTES, s, k);
         if (splits > 1) TRY(second_pass());
     }
     OFX_LAUNCH_CHECK();

@@ -24,8 +24,7 @@ struct KArgs {
     const float* resid;
     float* aux_out;     // optional fp32 [M, N] pre-activation copy
     const int* m_dev;   // optional device-side row count (pad-free varlen sets); M is then the upper bound
-    unsigned long long* dbg;   // diagnostics only (tools/gemm_bench.py --clock): per block {shader cycles, 100 MHz ticks} of the main loop
-    int M, N, K, lda, ldc, ldr, act, out_kind, tiles_n, tiles_m, nwg, group_m, skew;
+    int M, N, K, lda, ldc, ldr, act, out_kind, tiles_n, tiles_m, nwg, group_m;
     int m_slab;                 // rows per slab plane (the host-side M, never the clamped live count)
     int splits, kt_per_split;   // 128x128 kernel only: blockIdx.y owns k-tiles [y*kt_per_split, ...) and writes a raw fp32 slab
     float* slab;                // [splits, M, N] partial sums when splits > 1
@@ -34,9 +33,8 @@ struct KArgs {
     int n_valid;                // columns >= n_valid are computed but not stored (fp32 outputs of the TN kernel; = N elsewhere)
     int ka_tiles;               // A's k-tile index wraps modulo ka_tiles (K-concatenated weights against ONE copy of A: GemmArgs::a_wrap); = K / BK otherwise
     // fp8 weight-correction product (gemm_w2f8.hip): e4m3 copy of the weights' lo half, [N, K] bytes, k-permuted inside 128-blocks,
-    // and its per-row E8M0 scale bytes laid out 8 per (128-column block, lane & 15); a8_scale / a8_e8m0: activations are converted as
-    // fp8(a / a8_scale) in registers and enter the product with the scale byte a8_e8m0 (= 127 + log2 a8_scale)
-    const char* W8 = nullptr; const char* w8_scale = nullptr; float a8_scale = 0.25f; int a8_e8m0 = 125;
+    // and its per-row E8M0 scale bytes laid out 8 per (128-column block, lane & 15)
+    const char* W8 = nullptr; const char* w8_scale = nullptr;
     int epi_direct = 0;         // operand-type outputs without residual / tape leave straight from the accumulator layout (epilogue_direct), no LDS round trip
 };
 
@@ -247,10 +245,7 @@ __device__ __forceinline__ void epilogue2(const KArgs& p, OFX_LDS char* ep, f32x
         }
         // FOLD 3: the residual stream is the operand-type pair (hi at xb_out == C, lo at xlo), 16 bytes of each per lane and row,
         // fetched two passes ahead and rewritten in place (every element is owned by exactly one lane of one block)
-#ifndef OFX_EP3_DEPTH
-#define OFX_EP3_DEPTH 2
-#endif
-        constexpr int D3 = OFX_EP3_DEPTH < NP ? OFX_EP3_DEPTH : NP;        // passes of the (hi, lo) stream in flight ahead of the one being rewritten
+        constexpr int D3 = NP < 2 ? NP : 2;        // passes of the (hi, lo) stream in flight ahead of the one being rewritten
         v8 rh[FOLD == 3 ? D3 + 1 : 1][2], rl[FOLD == 3 ? D3 + 1 : 1][2];
         auto fetch_hl = [&](int pass, v8 (&dh)[2], v8 (&dl)[2]) {
 #pragma unroll
@@ -274,23 +269,14 @@ __device__ __forceinline__ void epilogue2(const KArgs& p, OFX_LDS char* ep, f32x
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
             if (FOLD == 3 && i + D3 < NP) fetch_hl(i + D3, rh[FOLD == 3 ? (i + D3) % (D3 + 1) : 0], rl[FOLD == 3 ? (i + D3) % (D3 + 1) : 0]);
-#ifndef OFX_EP3_NOLDS
-#define OFX_EP3_NOLDS 0          // experiment build only (WRONG results): the (hi, lo) epilogue without its LDS transposition - same loads, stores and arithmetic
-#endif
-            if (!(OFX_EP3_NOLDS && FOLD == 3)) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) *(OFX_LDS f32x4*)(ep + fr * 256 + (((j * 4 + fq) ^ (fr & 7)) << 4)) = acc[i][J0 + j];
-            }
+            for (int j = 0; j < 4; ++j) *(OFX_LDS f32x4*)(ep + fr * 256 + (((j * 4 + fq) ^ (fr & 7)) << 4)) = acc[i][J0 + j];
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
                 const int row = it * 8 + rsub;
                 const int gm = gm0 + i * 16 + row;
-                f32x4 v0, v1;
-                if (OFX_EP3_NOLDS && FOLD == 3) { v0 = acc[i][J0 + 2 * it]; v1 = acc[i][J0 + 2 * it + 1]; }
-                else {
-                    v0 = *(OFX_LDS f32x4*)(ep + row * 256 + (((2 * c8) ^ (row & 7)) << 4));
-                    v1 = *(OFX_LDS f32x4*)(ep + row * 256 + (((2 * c8 + 1) ^ (row & 7)) << 4));
-                }
+                f32x4 v0 = *(OFX_LDS f32x4*)(ep + row * 256 + (((2 * c8) ^ (row & 7)) << 4));
+                f32x4 v1 = *(OFX_LDS f32x4*)(ep + row * 256 + (((2 * c8 + 1) ^ (row & 7)) << 4));
                 if (gm < p.M) {
                     if (FOLD == 2) {
                         float mu, rs;
@@ -364,11 +350,7 @@ __device__ __forceinline__ void epilogue2(const KArgs& p, OFX_LDS char* ep, f32x
 // bytes; the two column-block pairs of a 64-column half complete every 128-byte line back to back.  Stores go through a buffer resource sized to the M
 // valid rows: rows past M fall outside it and are dropped by the hardware (no per-row predicate, no clamping).  FOLD: 0 bias (+ activation), 2 LayerNorm-fold
 // consumer ((acc - colsum mean) rstd + bias', row statistics through the wave's 1 KiB LDS slot `st` as in epilogue2).
-// WIDE (ofx_tune(18, 2)): the two registers of a 64-column half trade their upper / lower eight rows through DPP row_ror:8 (lane fr <-> fr ^ 8, 8 moves per pair of
-// stores), so that a store instruction covers 8 rows x 128 contiguous bytes - whole cache lines - and leaves as a plain global store predicated on row < M.
-// tools/store_shape_probe.hip: with a quarter of the chip storing, 16 rows x 64 B per instruction leave at 33 GB/s per CU whatever the instruction, 8 rows x 128 B
-// at > 80 GB/s (HBM-bound at 64 CUs); with all 256 CUs storing at once every shape is HBM-bound (5.1-6.9 TB/s).
-template <typename T, int ACT, int FOLD, int NP, int JW, bool WIDE = false>
+template <typename T, int ACT, int FOLD, int NP, int JW>
 __device__ __forceinline__ void epilogue_direct(const KArgs& p, f32x4 (&acc)[NP][JW], int gm0, int gn0, int lane, OFX_LDS float* st) {
     static_assert(JW % 4 == 0 && (FOLD == 0 || FOLD == 2), "whole 64-column halves; bias or LayerNorm-fold consumer");
     typedef T t2 __attribute__((ext_vector_type(2)));
@@ -391,8 +373,6 @@ __device__ __forceinline__ void epilogue_direct(const KArgs& p, f32x4 (&acc)[NP]
     // this lane's bytes of pass 0, column-block pair 0: row gm0 + fr, column gn0 + (fq & 1) 16 + (fq >> 1) 8
     const unsigned vo = ((unsigned)(gm0 + fr) * (unsigned)p.ldc + (unsigned)(gn0 + (fq & 1) * 16 + (fq >> 1) * 8)) * 2u;
     const unsigned pass_bytes = 16u * (unsigned)p.ldc * 2u;
-    // WIDE: row gm0 + (fr & 7) (+ 8 for the second store), bytes (fr >> 3) 64 + (fq & 1) 32 + (fq >> 1) 16 of the 128-byte half
-    const unsigned wo = ((unsigned)(gm0 + (fr & 7)) * (unsigned)p.ldc + (unsigned)(gn0 + (fr >> 3) * 32 + (fq & 1) * 16 + (fq >> 1) * 8)) * 2u;
 #pragma unroll
     for (int h = 0; h < JW / 4; ++h) {          // 64-column halves: the per-column constants of one half (32 registers) at a time
         f32x4 bb[4], cs[4];
@@ -406,7 +386,6 @@ __device__ __forceinline__ void epilogue_direct(const KArgs& p, f32x4 (&acc)[NP]
         for (int i = 0; i < NP; ++i) {
             float mu = 0.f, rs = 1.f;
             if (FOLD == 2) { const f32x2 ms = *(OFX_LDS f32x2*)(st + 2 * (i * 16 + fr)); mu = ms[0]; rs = ms[1]; }
-            u32x4 d[2];
 #pragma unroll
             for (int jp = 0; jp < 2; ++jp) {
                 f32x4 va = acc[i][h * 4 + 2 * jp], vb = acc[i][h * 4 + 2 * jp + 1];
@@ -421,21 +400,7 @@ __device__ __forceinline__ void epilogue_direct(const KArgs& p, f32x4 (&acc)[NP]
                 const u32x2 s0 = __builtin_amdgcn_permlane16_swap(a_lo, b_lo, false, false), s1 = __builtin_amdgcn_permlane16_swap(a_hi, b_hi, false, false);
                 // (the pass offset rides in the per-lane offset, NOT in the instruction's scalar offset: with a non-zero soffset on this resource the second and
                 //  fourth dword of rows 12-15 of every pass but the first came out wrong - tools/dbg_direct.py; everything in voffset is correct)
-                if (!WIDE) __builtin_amdgcn_raw_buffer_store_b128(u32x4{s0[0], s1[0], s0[1], s1[1]}, rc, (int)(vo + (unsigned)i * pass_bytes + (unsigned)(h * 128 + jp * 64)), 0, 0);
-                else d[jp] = u32x4{s0[0], s1[0], s0[1], s1[1]};
-            }
-            if (WIDE) {
-                // d[0] = bytes [0, 64) of this lane's row in the half, d[1] = bytes [64, 128).  x: rows 0-7 whole (lanes fr >= 8 take row fr - 8's d[1]),
-                // y: rows 8-15 whole (lanes fr < 8 take row fr + 8's d[0]); row_ror:8 = 0x128, bank mask = the four-lane banks written
-                u32x4 x = d[0], y = d[1];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    x[e] = (unsigned)__builtin_amdgcn_update_dpp((int)x[e], (int)d[1][e], 0x128, 0xf, 0xc, false);
-                    y[e] = (unsigned)__builtin_amdgcn_update_dpp((int)y[e], (int)d[0][e], 0x128, 0xf, 0x3, false);
-                }
-                const unsigned o = wo + (unsigned)i * pass_bytes + (unsigned)(h * 128);
-                if (gm0 + i * 16 + (fr & 7) < p.M) *(u32x4*)((char*)p.C + (size_t)o) = x;
-                if (gm0 + i * 16 + 8 + (fr & 7) < p.M) *(u32x4*)((char*)p.C + (size_t)(o + 8u * (unsigned)p.ldc * 2u)) = y;
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{s0[0], s1[0], s0[1], s1[1]}, rc, (int)(vo + (unsigned)i * pass_bytes + (unsigned)(h * 128 + jp * 64)), 0, 0);
             }
         }
     }
@@ -445,8 +410,7 @@ template <typename T, int NP, int JW>
 __device__ __forceinline__ bool epilogue_direct_dispatch(const KArgs& p, f32x4 (&acc)[NP][JW], int gm0, int gn0, int lane, OFX_LDS float* st) {
     if (!p.epi_direct || p.out_kind != 1 || p.resid || p.xb_out || p.stat_part || p.aux_out || p.drop.thresh || p.n_valid != p.N) return false;
     if ((size_t)p.M * p.ldc * 2 >= 0x7fffffff) return false;
-    const bool wide = p.epi_direct == 2;
-#define OFX_EPD(ACT_, FOLD_) { if (wide) epilogue_direct<T, ACT_, FOLD_, NP, JW, true>(p, acc, gm0, gn0, lane, st); else epilogue_direct<T, ACT_, FOLD_, NP, JW, false>(p, acc, gm0, gn0, lane, st); return true; }
+#define OFX_EPD(ACT_, FOLD_) { epilogue_direct<T, ACT_, FOLD_, NP, JW>(p, acc, gm0, gn0, lane, st); return true; }
     if (p.row_stat) {
         if (!st) return false;
         switch (p.act) {
@@ -543,7 +507,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(KArgs p) {
 }  // namespace
 
 // launchers implemented by the other translation units (KArgs travels as an opaque pointer: each unit sees the same definition)
-int ofx_gemm_launch_big(void* kargs, int kind, int ablate, int op_dtype, int M, int N, hipStream_t s);
+int ofx_gemm_launch_big(void* kargs, int kind, int op_dtype, int M, int N, hipStream_t s);
 int ofx_gemm_launch_pp(void* kargs, int op_dtype, int M, int N, hipStream_t s);
 int ofx_gemm_launch_w2(void* kargs, int op_dtype, int M, int N, hipStream_t s);
 int ofx_gemm_launch_w2f8(void* kargs, int M, int N, hipStream_t s);

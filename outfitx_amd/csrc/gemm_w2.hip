@@ -23,10 +23,10 @@
 // conflict-free for the hardware's lane groups of ds_read_b128 (MI355X_MICROARCH.md, LDS table).
 #include "gemm_common.h"
 
-extern int g_w2_persist, g_w2_trim;
+extern int g_w2_persist;
 namespace {
 
-template <typename T, int ABL = 0>      // ABL (make DIAG=1; wrong results): 1 no LDS-DMA in the loop, 2 no fragment reads after step 0, 3 both
+template <typename T>
 __global__ __launch_bounds__(512, 2) void gemm_w2_kernel(KArgs p) {
     typedef typename OpT<T>::v8 v8;
     constexpr int TM = 256, TN = 256, BK2 = 32, PART = TM * BK2 * 2, STAGE = 3 * PART, NST = 3;      // 16 KiB per operand, 48 KiB per stage
@@ -165,8 +165,8 @@ __global__ __launch_bounds__(512, 2) void gemm_w2_kernel(KArgs p) {
         // iterations of a tile are peeled so that the steady-state body carries no next-tile logic.
 #define OFX_W2_ITER_G0(T_, ISSUE)                                                                                \
         {                                                                                                        \
-            if (ABL == 0 || ABL == 2) { ISSUE; }                                                                 \
-            if (ABL < 2 || (T_) == 0) OFX_W2_READ(T_)                                                            \
+            ISSUE;                                                                                               \
+            OFX_W2_READ(T_)                                                                                      \
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                   \
             __builtin_amdgcn_sched_barrier(0);                                                                   \
             __builtin_amdgcn_s_barrier();                                                                        \
@@ -176,8 +176,8 @@ __global__ __launch_bounds__(512, 2) void gemm_w2_kernel(KArgs p) {
         }
 #define OFX_W2_ITER_G1(T_, ISSUE)                                                                                \
         {                                                                                                        \
-            if (ABL == 0 || ABL == 2) { ISSUE; }                                                                 \
-            if (ABL < 2 || (T_) == 0) OFX_W2_READ(T_)                                                            \
+            ISSUE;                                                                                               \
+            OFX_W2_READ(T_)                                                                                      \
             asm volatile("s_waitcnt vmcnt(6)" ::: "memory");    /* my pieces of step t+1 landed: group 0 reads them in slot 2t+3 */ \
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                   \
             __builtin_amdgcn_sched_barrier(0);                                                                   \
@@ -215,12 +215,12 @@ __global__ __launch_bounds__(512, 2) void gemm_w2_kernel(KArgs p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // the last tile's redundant fills have landed before the wave ends
 }
 
-template <typename T, int ABL = 0>
+template <typename T>
 static int launch_w2(KArgs& k, int M, int N, hipStream_t s) {
     constexpr int LDSB = 3 * 3 * 256 * 32 * 2;          // 144 KiB
     static DeviceOnce attr;
     TRY(attr.run([]() -> int {
-        OFX_HIP(hipFuncSetAttribute((const void*)gemm_w2_kernel<T, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
+        OFX_HIP(hipFuncSetAttribute((const void*)gemm_w2_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
         return OFX_OK;
     }));
     k.tiles_n = N / 256; k.tiles_m = (M + 255) / 256; k.nwg = k.tiles_m * k.tiles_n;
@@ -234,23 +234,14 @@ static int launch_w2(KArgs& k, int M, int N, hipStream_t s) {
         if (c == 0) { int v = 0; c = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256; }
         persist = c;
     }
-    int grid = (persist && !k.m_dev && k.nwg > persist) ? persist : k.nwg;
-    // ofx_tune(14, 1): the smallest grid that still finishes in the same number of rounds (1,200 or 3,600 tiles take 5 / 15 rounds on 256
-    // blocks and on 240 alike; the 16 CUs left alone would serve the side stream's text tower) - measured 0.4 ms per step SLOWER, off
-    if (g_w2_trim && grid < k.nwg) { const int rounds = (k.nwg + grid - 1) / grid; grid = (k.nwg + rounds - 1) / rounds; }
-    OFX_PLAUNCH(true, (gemm_w2_kernel<T, ABL>), dim3(grid), dim3(512), LDSB, s, k);
+    const int grid = (persist && !k.m_dev && k.nwg > persist) ? persist : k.nwg;
+    OFX_PLAUNCH(true, (gemm_w2_kernel<T>), dim3(grid), dim3(512), LDSB, s, k);
     return OFX_OK;
 }
 
 }  // namespace
 
-extern int g_gemm_ablate;
 int ofx_gemm_launch_w2(void* kargs, int op_dtype, int M, int N, hipStream_t s) {
     KArgs& k = *(KArgs*)kargs;
-#ifdef OFX_DIAG
-    if (g_gemm_ablate == 1) return launch_w2<f16_t, 1>(k, M, N, s);
-    if (g_gemm_ablate == 2) return launch_w2<f16_t, 2>(k, M, N, s);
-    if (g_gemm_ablate == 3) return launch_w2<f16_t, 3>(k, M, N, s);
-#endif
     return op_dtype == OFX_F16 ? launch_w2<f16_t>(k, M, N, s) : launch_w2<bf16_t>(k, M, N, s);
 }

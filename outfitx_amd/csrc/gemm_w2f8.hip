@@ -1,6 +1,6 @@
 // Split-weight 256x256 tile kernel with the weight-correction product on the block-scaled fp8 matrix instruction:
 //
-//     C = A . W_hi^T  (f16 x f16, v_mfma_f32_16x16x32_f16)  +  fp8(A) . fp8(W_lo)^T  (v_mfma_scale_f32_16x16x128_f8f6f4, e4m3 x e4m3)
+//     C = A . W_hi^T  (f16 x f16, v_mfma_f32_16x16x32_f16)  +  fp8(A) . fp8(W_lo)^T  (v_mfma_scale_f32_16x16x128_f8f6f4, e4m3 x e5m2)
 //
 // W = W_hi + W_lo with W_hi = f16(W) as in gemm_w2.hip.  The correction term A . W_lo^T is 2^-11 of the product, so 4 significant
 // bits of each of its operands keep the result at ~2^-15 - below the activation rounding the scheme leaves anyway (DESIGN.md section 2,
@@ -19,12 +19,12 @@
 //     FP16_OVFL = 1 clamps the f16 values above that instead of producing infinities).  The e4m3 image of rounds 3 (4 significant
 //     bits, x4 scale) saturated at |a| > 112 and then corrected only part of such a channel.  Price: the activation side of the
 //     2^-11 correction term is kept to 2^-4 instead of 2^-5 relative - still far below the f16 rounding of the main product
-//     (tests/studies/fp8_correction_cpu.py); same instruction rate (tools/mfma_power_probe.hip).  -DOFX_F8_ABF8=0 builds the e4m3 form.
+//     (tests/studies/fp8_correction_cpu.py); same instruction rate (tools/mfma_power_probe.hip).
 //   * the wave tile is 64 x 128 (8 waves as 4 x 2), so only 4 activation fragments = 32 VGPRs are held; the 8 weight fragments of the
 //     fp8 step stream through a 3-deep register ring loaded two fragments ahead of their use (128 accumulators + 32 + 24, in the
 //     registers the f16 fragments have just left);
 //   * per-row weight scales (E8M0, max |lo| 2^sw in [128, 256)) ride in as the instruction's per-lane scale operand, the activation
-//     scale (2^0 for the e5m2 image; the e4m3 build used x4: values below 2^-8 would otherwise fall under its subnormal step) as the other one.
+//     scale (2^0: the e5m2 image needs none) as the other one.
 //
 // Structure: gemm_w2.hip's ping-pong (two wave groups one barrier slot apart, BK = 32, counted vmcnt, persistent over tiles) with FOUR
 // 32 KiB stages [A | W_hi] and ONE 32 KiB buffer for the current super-step's fp8 weights (160 KiB in all).  The kernels of this
@@ -45,20 +45,7 @@
 // LayerNorm-fold statistics slots sit in the fp8 buffer, which is idle between the tile's last fp8 slot and the next tile's refill.
 #include "gemm_common.h"
 
-extern int g_w2_persist, g_w2_trim, g_epi_direct, g_w2f8_skew;
-#ifndef OFX_F8_ABF8
-#define OFX_F8_ABF8 1
-#endif
-#ifndef OFX_F8_PRIO
-#define OFX_F8_PRIO 1
-// f16 MFMA order: 1 = the weight fragment (the instruction's FIRST operand) stays over 4 consecutive MFMAs while the activation fragment cycles.
-// Bit-identical results (every accumulator sees the same sequence); 242 VGPRs and no scratch instead of 256 + 16 B; in back-to-back launches
-// qkv 560 -> 536 us, fc1 760 -> 740 (the part is power-limited and a changing first operand costs more: tools/mfma_power_probe.hip), level in the step.
-#ifndef OFX_MFMA_WKEEP
-#define OFX_MFMA_WKEEP 1
-#endif
-#endif
-#define OFX_F8_PRIO_HI __builtin_amdgcn_s_setprio(OFX_F8_PRIO)
+extern int g_w2_persist, g_epi_direct;
 namespace {
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
@@ -76,11 +63,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const char* base, si
     return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)(bytes < 0x7fffffff ? bytes : 0x7fffffff), 0x00020000);
 }
 
-// ABL (make DIAG=1; wrong results): 1 no LDS-DMA in the loop, 2 no fragment reads after step 0, 3 both, 4 no fp8 product, 5 LDS-DMA + barriers only (no reads, no MFMA: the
-// fill rate of this slot structure), 6 the same with the fragment reads, 7 the full kernel with s_memtime stamps around its slots and epilogues (tools/w2f8_slots.py);
-// round 4, the fill wall split into L2-hit rate and miss cost: 8 = 5 and 9 = the full kernel, both with every block LOADING from one of four operand tiles (two A
-// panels x two W panels: 1.9 MiB at K = 768, resident in every XCD's 4 MiB L2 after the first touch) while the epilogue still writes the block's own tile
-template <int ABL = 0>
 __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
     typedef f16_t T;
     typedef OpT<T>::v8 v8;
@@ -114,26 +96,12 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
     };
     const int nk = Kh / BK2, nsup = nk >> 2;
     const int dst0 = wave * 2 * 1024;
-    const float a_scale = p.a8_scale;
-    const int a_e8 = p.a8_e8m0;
+    const float a_scale = 1.0f;                        // the e5m2 activation image: f16's exponent range, unscaled (E8M0 byte 127 = 2^0)
+    const int a_e8 = 127;
 
-    // DIAG (ABL 7): per wave, cycles summed over all iterations, [long slot (s = 3) ? 1 : 0][read+issue, wait at the mid barrier, MFMA slot, wait at the end barrier]
-    unsigned slot_cyc[2][4] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
-    unsigned long long st0_ = 0, st1_ = 0;
-    unsigned epi_cyc = 0, epi_tiles = 0, gap_cyc = 0;       // epilogue cycles summed over tiles; cycles from the end of an epilogue to the next tile's first barrier
-#define OFX_F8_STAMP(V) if (ABL == 7) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(V) :: "memory");
-#define OFX_F8_ACC(S_, I) if (ABL == 7) { OFX_F8_STAMP(st1_) slot_cyc[(S_) == 3][I] += (unsigned)(st1_ - st0_); st0_ = st1_; }
     int vb = blockIdx.x, m0, n0;
     map_tile(vb, m0, n0);
     if (m0 >= p.M) return;
-    // Experiment knob (ofx_tune(19, v), default 0): a one-time start skew by XCD, so that the chip's CUs are not in their epilogues at the same moments of every
-    // round.  With the 16 rows x 64 B stores every ViT shape got monotonically slower with the skew (profiles/r04_epilogue_skew.txt); with whole-line stores
-    // (ofx_tune(18, 2)), whose per-CU rate is 2.5x higher (tools/store_shape_probe.hip), two-phase and eight-phase skews measure level within +-1 %
-    // (profiles/r04_epilogue_wide_skew.txt): neither the instruction's shape nor the phase of the other CUs sets the epilogue's time.
-    if (p.skew) {
-        const int x = blockIdx.x & 7, units = p.skew > 0 ? (x & 1) * p.skew : x * -p.skew;
-        for (int i = 0; i < units; ++i) __builtin_amdgcn_s_sleep(32);       // ~2,048 cycles each
-    }
     int base = 0;                                       // (global index of the current tile's step 0) mod 4
     bool first = true, full_prev = false;
     // per-row E8M0 scale bytes of this wave's 128 columns: 8 bytes per lane (fragment j -> byte j); the NEXT tile's are requested before
@@ -158,17 +126,14 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
         // fp8 weight fragment j: row wc * 128 + j * 16 + fr, logical chunks 2 fq, 2 fq + 1
         const int x8 = (((fr >> 1) & 3) << 1) | (fr >> 3);
         const int w8_frag0 = (wc * 128 + fr) * 128 + (((2 * fq) ^ x8) << 4), w8_frag1 = (wc * 128 + fr) * 128 + (((2 * fq + 1) ^ x8) << 4);
-        constexpr bool L2RES = ABL == 8 || ABL == 9;         // DIAG: operand loads come from four L2-resident tiles
-        const int lm0 = L2RES ? (vb & 1) * TM : m0, ln0 = L2RES ? ((vb >> 1) & 1) * TN : n0;
-        const char* a_base = p.A + (size_t)lm0 * p.lda * 2;
-        const char* w_base = p.W + (size_t)ln0 * (2 * Kh) * 2;
-        const char* w8_base = p.W8 + (size_t)ln0 * Kh;
+        const char* a_base = p.A + (size_t)m0 * p.lda * 2;
+        const char* w_base = p.W + (size_t)n0 * (2 * Kh) * 2;
+        const char* w8_base = p.W8 + (size_t)n0 * Kh;
         unsigned a_off[2];                                  // tile-independent too: rows past M read zeros through the sized resource
 #pragma unroll
         for (int i = 0; i < 2; ++i) a_off[i] = ((unsigned)((wave * 2 + i) * 16 + prow) * p.lda + pchk * 8) * 2;
         int m1 = m0, n1 = n0;                               // the next tile (the block's last tile re-fills its own first steps: nobody reads them)
         if (has_next) map_tile(vb + (int)gridDim.x, m1, n1);
-        const int lm1 = L2RES ? ((vb + (int)gridDim.x) & 1) * TM : m1, ln1 = L2RES ? (((vb + (int)gridDim.x) >> 1) & 1) * TN : n1;
         int sc_lo = (int)(unsigned)sc8, sc_hi = (int)(unsigned)(sc8 >> 32);
 
         // LDS-DMA pieces: the two A and two W_hi pieces of a k-step (KOFF = its byte offset in the k-contiguous rows) and quarter Q of
@@ -181,8 +146,8 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
 #define OFX_F8_ISSUE_W8(SUP, Q)                                                                                            \
     bload16(r_w8, w8_off ^ (((Q) & 1) << 4), (unsigned)(SUP) * 128u + (unsigned)(Q) * 8u * (unsigned)Kh, lds + W8BASE + (wave * 4 + (Q)) * 1024);
         const size_t a_row = (size_t)p.lda * 2;
-        const __amdgpu_buffer_rsrc_t r_a = make_rsrc(a_base, (size_t)(p.M - lm0) * a_row), r_w = make_rsrc(w_base), r_w8 = make_rsrc(w8_base);
-        const __amdgpu_buffer_rsrc_t r_a1 = make_rsrc(p.A + (size_t)lm1 * a_row, (size_t)(p.M - lm1) * a_row), r_w1 = make_rsrc(p.W + (size_t)ln1 * (2 * Kh) * 2);
+        const __amdgpu_buffer_rsrc_t r_a = make_rsrc(a_base, (size_t)(p.M - m0) * a_row), r_w = make_rsrc(w_base), r_w8 = make_rsrc(w8_base);
+        const __amdgpu_buffer_rsrc_t r_a1 = make_rsrc(p.A + (size_t)m1 * a_row, (size_t)(p.M - m1) * a_row), r_w1 = make_rsrc(p.W + (size_t)n1 * (2 * Kh) * 2);
         // k-step x of the tile walk: a step of this tile, or (x >= nk) step x - nk of the next one - a scalar select of resource and offset
         auto issue_step = [&](int x) {
             OFX_LDS char* stg = lds + ((base + x) % NST) * STAGE;
@@ -208,35 +173,25 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
         _Pragma("unroll") for (int i = 0; i < 4; ++i) af[i] = *(OFX_LDS v8*)(base_ + a_frag + i * 16 * 64);    \
     }
         // 32 f16 MFMAs + the conversion of the four A fragments into bytes 8 S .. 8 S + 7 of their fp8 images (S = step & 3, static)
-#if OFX_F8_ABF8
-#define OFX_F8_CVT_PK __builtin_amdgcn_cvt_scalef32_pk_bf8_f16
-#define OFX_F8_BLGP 1
-#else
-#define OFX_F8_CVT_PK __builtin_amdgcn_cvt_scalef32_pk_fp8_f16
-#define OFX_F8_BLGP 0
-#endif
 #define OFX_F8_CVT1(I, S)                                                                                      \
     {                                                                                                         \
         i16x2 lo_ = __builtin_bit_cast(i16x2, a8[I][2 * (S)]), hi_ = __builtin_bit_cast(i16x2, a8[I][2 * (S) + 1]); \
-        lo_ = OFX_F8_CVT_PK(lo_, f16x2{af[I][0], af[I][1]}, a_scale, false);                                  \
-        lo_ = OFX_F8_CVT_PK(lo_, f16x2{af[I][2], af[I][3]}, a_scale, true);                                   \
-        hi_ = OFX_F8_CVT_PK(hi_, f16x2{af[I][4], af[I][5]}, a_scale, false);                                  \
-        hi_ = OFX_F8_CVT_PK(hi_, f16x2{af[I][6], af[I][7]}, a_scale, true);                                   \
+        lo_ = __builtin_amdgcn_cvt_scalef32_pk_bf8_f16(lo_, f16x2{af[I][0], af[I][1]}, a_scale, false);       \
+        lo_ = __builtin_amdgcn_cvt_scalef32_pk_bf8_f16(lo_, f16x2{af[I][2], af[I][3]}, a_scale, true);        \
+        hi_ = __builtin_amdgcn_cvt_scalef32_pk_bf8_f16(hi_, f16x2{af[I][4], af[I][5]}, a_scale, false);       \
+        hi_ = __builtin_amdgcn_cvt_scalef32_pk_bf8_f16(hi_, f16x2{af[I][6], af[I][7]}, a_scale, true);        \
         a8[I][2 * (S)] = __builtin_bit_cast(int, lo_); a8[I][2 * (S) + 1] = __builtin_bit_cast(int, hi_);      \
     }
+// f16 MFMA order: the weight fragment (the instruction's FIRST operand) stays over 4 consecutive MFMAs while the activation fragment cycles.
+// Bit-identical to the activation-outer order (every accumulator sees the same sequence); 242 VGPRs and no scratch instead of 256 + 16 B; in
+// back-to-back launches qkv 560 -> 536 us, fc1 760 -> 740 (the part is power-limited and a changing first operand costs more:
+// tools/mfma_power_probe.hip), level in the step.
 #define OFX_F8_MFMA16(S)                                                                                      \
-    if (ABL < 5 || ABL == 7 || ABL == 9) {                                                                                             \
-        OFX_F8_PRIO_HI;                                                                      \
-        if (OFX_MFMA_WKEEP) {       /* weight fragment (the instruction's first operand) kept over 4 consecutive MFMAs: tools/mfma_power_probe.hip */ \
-            _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                   \
-                _Pragma("unroll") for (int i = 0; i < 4; ++i) acc[i][j] = OpT<T>::mfma16(wh[j], af[i], acc[i][j]); \
-                if (ABL != 4 && (j & 1)) OFX_F8_CVT1(j >> 1, S)                                               \
-            }                                                                                                 \
-        } else {                                                                                              \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                       \
-            _Pragma("unroll") for (int j = 0; j < 8; ++j) acc[i][j] = OpT<T>::mfma16(wh[j], af[i], acc[i][j]); \
-            if (ABL != 4) OFX_F8_CVT1(i, S)                                                                   \
-        }                                                                                                     \
+    {                                                                                                         \
+        __builtin_amdgcn_s_setprio(1);                                                                        \
+        _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                       \
+            _Pragma("unroll") for (int i = 0; i < 4; ++i) acc[i][j] = OpT<T>::mfma16(wh[j], af[i], acc[i][j]); \
+            if (j & 1) OFX_F8_CVT1(j >> 1, S)                                                                 \
         }                                                                                                     \
         __builtin_amdgcn_s_setprio(0);                                                                        \
     }
@@ -251,14 +206,14 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
 #define OFX_F8_MF(J, SEL, SC)                                                                                 \
     if ((J) + 2 < 8) { OFX_F8_LD((J) + 2) __builtin_amdgcn_sched_barrier(0); }     /* keep the load two fragments ahead of its use */ \
     _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                             \
-        acc[i][J] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(w8_[(J) % 3], a8[i], acc[i][J], 0, OFX_F8_BLGP, SEL, SC, 0, a_e8);
-#define OFX_F8_MFMA8()                                                                                      \
-    if (ABL != 4 && (ABL < 5 || ABL == 7 || ABL == 9)) {                                                                                \
+        acc[i][J] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(w8_[(J) % 3], a8[i], acc[i][J], 0, 1, SEL, SC, 0, a_e8);
+#define OFX_F8_MFMA8()                                                                                        \
+    {                                                                                                         \
         __builtin_amdgcn_sched_barrier(0);      /* the fp8 fragments take the registers the f16 fragments leave: no hoisting above */ \
         OFX_LDS char* b8_ = lds + W8BASE;                                                                     \
         i32x8 w8_[3];                                                                                         \
         OFX_F8_LD(0) OFX_F8_LD(1)                                                                             \
-        OFX_F8_PRIO_HI;                                                                      \
+        __builtin_amdgcn_s_setprio(1);                                                                        \
         OFX_F8_MF(0, 0, sc_lo) OFX_F8_MF(1, 1, sc_lo) OFX_F8_MF(2, 2, sc_lo) OFX_F8_MF(3, 3, sc_lo)           \
         OFX_F8_MF(4, 0, sc_hi) OFX_F8_MF(5, 1, sc_hi) OFX_F8_MF(6, 2, sc_hi) OFX_F8_MF(7, 3, sc_hi)           \
         __builtin_amdgcn_s_setprio(0);                                                                        \
@@ -280,48 +235,33 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
         asm volatile("" : "+v"(sc_lo), "+v"(sc_hi));                  // the scale load is waited for HERE, not inside the counted-vmcnt loop
         asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1");     // MODE.FP16_OVFL: the f16 -> fp8 conversion clamps at the format's largest finite value (e5m2: 57,344; e4m3: 448) instead of inf / NaN
         __builtin_amdgcn_s_barrier();                               // ---- end of slot 0
-        if (ABL == 7 && !first) { OFX_F8_STAMP(st1_) gap_cyc += (unsigned)(st1_ - st0_); }
         // One iteration of group 0 (slots 2t+1, 2t+2) / group 1 (slots 2t+2, 2t+3), as in gemm_w2.hip; NV = the LDS-DMA pieces the
         // iteration issues: its counted wait leaves exactly those in flight (everything issued by earlier iterations has landed: an
         // iteration t fills steps t + 2 / t + 3, read from iteration t + 2 on, and the fp8 quarters are read two iterations later at
         // the earliest).  The fp8 product of a super-step runs at the end of the MFMA slot of its fourth k-step.
 #define OFX_F8_ITER_G0(T_, S_, NV, ISSUE, TAIL)                                                                  \
         {                                                                                                        \
-            OFX_F8_STAMP(st0_)                                                                                   \
-            if (ABL == 0 || ABL == 2 || ABL >= 4) { ISSUE; }                                                     \
-            if (ABL == 0 || ABL == 1 || ABL == 4 || ABL == 6 || ABL == 7 || ABL == 9 || (T_) == 0) OFX_F8_READ(T_)           \
+            ISSUE;                                                                                               \
+            OFX_F8_READ(T_)                                                                                      \
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                   \
-            OFX_F8_ACC(S_, 0)                                                                                    \
-            if (ABL == 6) { _Pragma("unroll") for (int j = 0; j < 8; ++j) asm volatile("" :: "v"(wh[j])); _Pragma("unroll") for (int i = 0; i < 4; ++i) asm volatile("" :: "v"(af[i])); } \
             __builtin_amdgcn_sched_barrier(0);                                                                   \
             __builtin_amdgcn_s_barrier();                                                                        \
-            OFX_F8_ACC(S_, 1)                                                                                    \
             OFX_F8_MFMA16(S_)                                                                                    \
             TAIL                                                                                                 \
-            OFX_F8_ACC(S_, 2)                                                                                    \
-            if (ABL == 0 || ABL == 2 || ABL >= 4) asm volatile("s_waitcnt vmcnt(" #NV ")" ::: "memory");         \
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                \
+            asm volatile("s_waitcnt vmcnt(" #NV ")" ::: "memory");                                               \
             __builtin_amdgcn_s_barrier();                                                                        \
-            OFX_F8_ACC(S_, 3)                                                                                    \
         }
 #define OFX_F8_ITER_G1(T_, S_, NV, ISSUE, TAIL)                                                                  \
         {                                                                                                        \
-            OFX_F8_STAMP(st0_)                                                                                   \
-            if (ABL == 0 || ABL == 2 || ABL >= 4) { ISSUE; }                                                     \
-            if (ABL == 0 || ABL == 1 || ABL == 4 || ABL == 6 || ABL == 7 || ABL == 9 || (T_) == 0) OFX_F8_READ(T_)           \
-            if (ABL == 0 || ABL == 2 || ABL >= 4) asm volatile("s_waitcnt vmcnt(" #NV ")" ::: "memory");         \
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                \
+            ISSUE;                                                                                               \
+            OFX_F8_READ(T_)                                                                                      \
+            asm volatile("s_waitcnt vmcnt(" #NV ")" ::: "memory");                                               \
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                   \
-            OFX_F8_ACC(S_, 0)                                                                                    \
-            if (ABL == 6) { _Pragma("unroll") for (int j = 0; j < 8; ++j) asm volatile("" :: "v"(wh[j])); _Pragma("unroll") for (int i = 0; i < 4; ++i) asm volatile("" :: "v"(af[i])); } \
             __builtin_amdgcn_sched_barrier(0);                                                                   \
             __builtin_amdgcn_s_barrier();                                                                        \
-            OFX_F8_ACC(S_, 1)                                                                                    \
             OFX_F8_MFMA16(S_)                                                                                    \
             TAIL                                                                                                 \
-            OFX_F8_ACC(S_, 2)                                                                                    \
             __builtin_amdgcn_s_barrier();                                                                        \
-            OFX_F8_ACC(S_, 3)                                                                                    \
         }
 #define OFX_F8_W8_ALL(U) OFX_F8_ISSUE_W8(U, 0) OFX_F8_ISSUE_W8(U, 1) OFX_F8_ISSUE_W8(U, 2) OFX_F8_ISSUE_W8(U, 3)
         if (grp == 0) {
@@ -354,8 +294,6 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
 #undef OFX_F8_MF
 #undef OFX_F8_LD
 #undef OFX_F8_CVT1
-#undef OFX_F8_CVT_PK
-#undef OFX_F8_BLGP
 #undef OFX_F8_ISSUE_AW
 #undef OFX_F8_ISSUE_W8
         asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 0");     // the epilogue's f32 -> f16 casts keep the default overflow behaviour
@@ -367,55 +305,16 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
         OFX_LDS float* st = nullptr;
         if (p.row_stat && p.out_kind != 0) st = (OFX_LDS float*)(lds + W8BASE + wave * 1024);
         sc8 = *(const unsigned long long*)(p.w8_scale + ((size_t)((n1 >> 7) + wc) * 16 + (ln & 15)) * 8);     // the next tile's scale bytes (this tile's own again on the last one)
-        OFX_F8_STAMP(st0_)
         OFX_LDS float* st2 = (p.row_stat && p.out_kind != 0) ? st : nullptr;
         if (!epilogue_direct_dispatch<T, 4, 8>(p, acc, gm0, gn0, ln, st2)) {
             epilogue2_dispatch<T, 4, 8, 0>(p, ep, acc, gm0, gn0, ln, st);
             epilogue2_dispatch<T, 4, 8, 4>(p, ep, acc, gm0, gn0 + 64, ln, st);
         }
-        if (ABL == 7) { OFX_F8_STAMP(st1_) epi_cyc += (unsigned)(st1_ - st0_); ++epi_tiles; st0_ = st1_; }
         if (!has_next) break;
         full_prev = m0 + TM <= p.M;
         vb += gridDim.x; map_tile(vb, m0, n0); base = (base + nk) % NST; first = false;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // the last tile's redundant fills have landed before the wave ends
-    if (ABL == 7 && p.dbg && (wave == 0 || wave == 4) && lane == 0) {
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) p.dbg[(size_t)blockIdx.x * 32 + grp * 16 + a * 4 + b] = slot_cyc[a][b];
-        p.dbg[(size_t)blockIdx.x * 32 + grp * 16 + 8] = epi_cyc; p.dbg[(size_t)blockIdx.x * 32 + grp * 16 + 9] = epi_tiles; p.dbg[(size_t)blockIdx.x * 32 + grp * 16 + 10] = gap_cyc;
-    }
-#undef OFX_F8_STAMP
-#undef OFX_F8_ACC
-}
-
-template <int ABL = 0>
-static int launch_w2f8(KArgs& k, int M, int N, hipStream_t s) {
-    constexpr int LDSB = 4 * 2 * 256 * 32 * 2 + 256 * 128;              // 128 KiB of stages + the 32 KiB fp8 weight buffer = 160 KiB
-    static DeviceOnce attr;
-    TRY(attr.run([]() -> int {
-        OFX_HIP(hipFuncSetAttribute((const void*)gemm_w2f8_kernel<ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-        return OFX_OK;
-    }));
-    k.tiles_n = N / 256; k.tiles_m = (M + 255) / 256; k.nwg = k.tiles_m * k.tiles_n;
-    k.epi_direct = g_epi_direct;
-    k.skew = g_w2f8_skew;
-    int persist = g_w2_persist;
-    if (persist < 0) {
-        static int cus[64] = {0};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        int& c = cus[dev & 63];
-        if (c == 0) { int v = 0; c = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256; }
-        persist = c;
-    }
-    int grid = (persist && !k.m_dev && k.nwg > persist) ? persist : k.nwg;
-    // ofx_tune(14, 1): the smallest grid that still finishes in the same number of rounds (1,200 or 3,600 tiles take 5 / 15 rounds on 256
-    // blocks and on 240 alike; the 16 CUs left alone would serve the side stream's text tower) - measured 0.4 ms per step SLOWER, off
-    if (g_w2_trim && grid < k.nwg) { const int rounds = (k.nwg + grid - 1) / grid; grid = (k.nwg + rounds - 1) / rounds; }
-    OFX_PLAUNCH(true, (gemm_w2f8_kernel<ABL>), dim3(grid), dim3(512), LDSB, s, k);
-    return OFX_OK;
 }
 
 // fp8 copy of the lo half of split-weight rows: src row n = [hi(K) | lo(K)] in f16 (row stride 2 K); dst row n = K bytes, e4m3 of
@@ -458,23 +357,28 @@ __global__ __launch_bounds__(256) void pack_lo8_kernel(const f16_t* src, unsigne
 
 }  // namespace
 
-int ofx_w2f8_act_is_bf8() { return OFX_F8_ABF8; }
-
-extern int g_gemm_ablate;
 int ofx_gemm_launch_w2f8(void* kargs, int M, int N, hipStream_t s) {
     KArgs& k = *(KArgs*)kargs;
-#ifdef OFX_DIAG
-    if (g_gemm_ablate == 1) return launch_w2f8<1>(k, M, N, s);
-    if (g_gemm_ablate == 2) return launch_w2f8<2>(k, M, N, s);
-    if (g_gemm_ablate == 3) return launch_w2f8<3>(k, M, N, s);
-    if (g_gemm_ablate == 4) return launch_w2f8<4>(k, M, N, s);
-    if (g_gemm_ablate == 5) return launch_w2f8<5>(k, M, N, s);
-    if (g_gemm_ablate == 6) return launch_w2f8<6>(k, M, N, s);
-    if (g_gemm_ablate == 7) return launch_w2f8<7>(k, M, N, s);
-    if (g_gemm_ablate == 8) return launch_w2f8<8>(k, M, N, s);
-    if (g_gemm_ablate == 9) return launch_w2f8<9>(k, M, N, s);
-#endif
-    return launch_w2f8<0>(k, M, N, s);
+    constexpr int LDSB = 4 * 2 * 256 * 32 * 2 + 256 * 128;              // 128 KiB of stages + the 32 KiB fp8 weight buffer = 160 KiB
+    static DeviceOnce attr;
+    TRY(attr.run([]() -> int {
+        OFX_HIP(hipFuncSetAttribute((const void*)gemm_w2f8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
+        return OFX_OK;
+    }));
+    k.tiles_n = N / 256; k.tiles_m = (M + 255) / 256; k.nwg = k.tiles_m * k.tiles_n;
+    k.epi_direct = g_epi_direct;
+    int persist = g_w2_persist;
+    if (persist < 0) {
+        static int cus[64] = {0};
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+        int& c = cus[dev & 63];
+        if (c == 0) { int v = 0; c = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256; }
+        persist = c;
+    }
+    const int grid = (persist && !k.m_dev && k.nwg > persist) ? persist : k.nwg;
+    OFX_PLAUNCH(true, gemm_w2f8_kernel, dim3(grid), dim3(512), LDSB, s, k);
+    return OFX_OK;
 }
 
 int ofx_launch_pack_lo8(const void* w2_rows, void* dst8, void* scale8, int N, int K, hipStream_t s) {

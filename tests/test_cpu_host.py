@@ -20,7 +20,9 @@ from outfitx_amd import synth
 warnings.simplefilter("ignore")
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_declared_symbol_at_abi_6():
+    """Every symbol include/ofx.h declares is exported and bound, and library, header and Python binding agree on ABI version 6
+    (6 retired the GEMM experiment hooks: ofx_debug_gemm_clock is no longer exported)."""
     from outfitx_amd import _lib
     lib = _lib.load()
     hdr = open(os.path.join(ROOT, "include", "ofx.h")).read()
@@ -30,7 +32,9 @@ def test_library_exports_every_declared_symbol():
     missing = [s for s in sorted(declared) if not hasattr(lib, s)]
     assert not missing, missing
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
-    assert lib.ofx_abi_version() == 5
+    hdr_abi = int(re.search(r"#define OFX_ABI_VERSION (\d+)", hdr).group(1))
+    assert lib.ofx_abi_version() == _lib.ABI_VERSION == hdr_abi == 6
+    assert not hasattr(lib, "ofx_debug_gemm_clock")
     d = _lib.default_desc()
     assert (d.d_model, d.n_head, d.d_ffn, d.n_layers, d.vit_width, d.txt_width, d.proj_dim) == (1024, 16, 2024, 6, 768, 512, 512)
 

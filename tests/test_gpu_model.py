@@ -399,6 +399,9 @@ def test_c_abi_error_codes():
     bad = L.default_desc(); bad.d_model = 1000
     assert not lib.ofx_create(0, C.byref(bad)) and b"d_model" in lib.ofx_last_error()
     assert lib.ofx_tune(99, 0) == -1
+    for knob in (0, 1, 3, 4, 12, 13, 14, 19):                                     # retired experiment knobs are unknown knobs now
+        assert lib.ofx_tune(knob, 0) == -1
+    assert lib.ofx_tune(18, 2) == -1                                              # knob 18 is 0 (LDS epilogue) or 1 (default)
     lib.ofx_destroy(h)
     # too-small workspace on a packed model
     from outfitx_amd.engine import Engine

@@ -17,7 +17,7 @@ SHAPES = [("vit qkv", 102400, 2304, 768, "b"), ("vit out", 102400, 768, 768, "r"
 
 def main():
     lib = L.load()
-    variants = [dict(kv.split("=") for kv in v.split(",")) for v in sys.argv[1:] if "=" in v] or [{"0": "1"}, {"0": "8"}]
+    variants = [dict(kv.split("=") for kv in v.split(",")) for v in sys.argv[1:] if "=" in v] or [{"2": "0"}, {"2": "1"}]      # default: automatic kernel vs 128x128
     only = [v for v in sys.argv[1:] if "=" not in v]
     s = torch.cuda.current_stream().cuda_stream
     g = torch.Generator(device="cuda"); g.manual_seed(0)
@@ -35,7 +35,7 @@ def main():
         for rnd in range(6):
             for i, v in enumerate(variants):
                 for k, val in v.items():
-                    lib.ofx_tune(int(k), int(val))
+                    L.check(lib.ofx_tune(int(k), int(val)))
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 reps = 5
                 e0.record()

@@ -40,31 +40,10 @@ def main():
         bias = torch.randn(N, device="cuda", generator=g)
         resid = C.data_ptr() if ep == "r" else None
         act, okind = (1 if ep == "g" else 0), (1 if ep in "bg" else 0)
-        abl = [int(v) for v in os.environ.get("OFX_W2_ABLATE", "").split(",") if v]
-        def ablated(a):
-            def f():
-                lib.ofx_tune(1, a)
-                try:
-                    return lib.ofx_gemm_w2(A.data_ptr(), W2.data_ptr(), C.data_ptr(), bias.data_ptr(), resid, M, N, K, K, N, N, act, okind, 2, s)
-                finally:
-                    lib.ofx_tune(1, 0)
-            return f
         runs = {"x1": lambda: lib.ofx_gemm(A.data_ptr(), W.data_ptr(), C.data_ptr(), bias.data_ptr(), resid, M, N, K, K, N, N, act, okind, 2, s),
                 "w2": lambda: lib.ofx_gemm_w2(A.data_ptr(), W2.data_ptr(), C.data_ptr(), bias.data_ptr(), resid, M, N, K, K, N, N, act, okind, 2, s)}
-        if f8:         # the fp8 correction product (gemm_w2f8_kernel); OFX_F8_ABLATE=1,2,3,4 adds its DIAG ablations
+        if f8:         # the fp8 correction product (gemm_w2f8_kernel)
             runs["w2f8"] = lambda: lib.ofx_gemm_w2f8(A.data_ptr(), W2.data_ptr(), W8.data_ptr(), sc8.data_ptr(), C.data_ptr(), bias.data_ptr(), resid, M, N, K, K, N, N, act, okind, s)
-            def f8_ablated(a):
-                def f():
-                    lib.ofx_tune(1, a)
-                    try:
-                        return runs["w2f8"]()
-                    finally:
-                        lib.ofx_tune(1, 0)
-                return f
-            for a_ in [int(v) for v in os.environ.get("OFX_F8_ABLATE", "").split(",") if v]:
-                runs[f"w2f8 abl{a_}"] = f8_ablated(a_)
-        for a_ in abl:
-            runs[f"abl{a_}"] = ablated(a_)
         if os.environ.get("OFX_KNOB"):                  # A/B of an ofx_tune knob on the dual-weight kernel: OFX_KNOB=11:0:256 (knob:value:restore)
             kn, kv, kr = [int(v) for v in os.environ["OFX_KNOB"].split(":")]
             def knobbed():
@@ -74,16 +53,6 @@ def main():
                 finally:
                     lib.ofx_tune(kn, kr)
             runs[f"w2 knob{kn}={kv}"] = knobbed
-        def x1_ablated(a):
-            def f():
-                lib.ofx_tune(1, a)
-                try:
-                    return runs["x1"]()
-                finally:
-                    lib.ofx_tune(1, 0)
-            return f
-        for a_ in [int(v) for v in os.environ.get("OFX_X1_ABLATE", "").split(",") if v]:        # single-product kernel's ablations (DIAG build)
-            runs[f"x1 abl{a_}"] = x1_ablated(a_)
         res = {k: [] for k in runs}
         for rnd in range(6):
             for k, fn in runs.items():

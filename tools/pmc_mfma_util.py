@@ -77,7 +77,7 @@ for k, s in sorted(stats.items(), key=lambda kv: -kv[1]["total_ns"]):
            "mfma_util": round(busy / (gui * 1024.0), 4) if gui else None,
            "mfma_tflops_executed": round(mops * scale / t / 1e12, 1) if mops else 0.0,
            "hbm_bytes_per_call": round(byts / max(s["calls"], 1)), "hbm_gb_s": round(byts / t / 1e9, 1) if byts else 0.0}
-    def same_kernel(bench_name, prof_name):          # bench: gemm_big_kernel<2,2,1>, gemm_w2f8_kernel; profiler: gemm_big_kernel<f16,2,2,1,0>, gemm_w2f8_kernel<0>
+    def same_kernel(bench_name, prof_name):          # bench: gemm_big_kernel<2,2,1>, gemm_w2f8_kernel; profiler: gemm_big_kernel<f16,2,2,1>, gemm_w2f8_kernel
         bb, _, ba = bench_name.partition("<"); pb, _, pa = prof_name.partition("<")
         if bb.strip() != pb.strip():
             return False
