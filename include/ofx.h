@@ -253,8 +253,9 @@ int ofx_profile_records(ofx_prof_record* out, int cap);
  * knob 2: GEMM kernel, 0 (default) = the automatic choice, 1 = 128x128, 2 = 256x256, 3 = 256x128, 4 = 256x256 ping-pong, 5 = 64x128,
  *         6 = the dual-weight 256x256 kernel for split weights (every other GEMM keeps the automatic choice);
  * knob 5: split-K of small GEMMs, 1 (default) = planned, 0 = never, >= 2 = forced (low byte = splits, bit 8 = 64-row tiles);
- * knob 6: 2 (default) folds the CLIP towers' LayerNorms into the neighbouring GEMM epilogues AND keeps their residual stream as an
- * operand-type (hi, lo) pair updated in place (no fp32 stream between the layers), 1 folds with an fp32 stream, 0 materialises them;
+ * knob 6: accepts only 2, the one tower form (a no-op kept for callers that set it): the CLIP towers' LayerNorms are folded into the
+ *         neighbouring GEMM epilogues and their residual stream is an operand-type (hi, lo) pair updated in place; 0 and 1 (fp32 stream,
+ *         materialised LayerNorms) are retired and return OFX_EINVAL;
  * knob 7: 1 (default) single-product precisions (training; scoring in bf16 / f16) run the MFMA varlen attention, 0 the fp32 set kernels;
  * knob 8: 1 (default) the ViT's last layer computes queries for the CLS rows only, 0 runs the full QKV GEMM;
  * knob 9: bit 0 (default on) / bit 1 (default off): ViT layers with single-product / split (hi, lo) q | k | v weights run the fused

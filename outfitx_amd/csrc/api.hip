@@ -178,15 +178,15 @@ static void use_split(GemmArgs& g, const void* w2, int K, const F8Pair& f8) {
     g.W = w2; g.K = 2 * K; g.a_wrap = K;
     g.W8 = f8.w8; g.w8_scale = f8.s8;
 }
-struct ClipLayer { void *w_qkv, *w_o, *w_fc1, *w_fc2; float *b_qkv, *b_o, *b_fc1, *b_fc2, *g1, *be1, *g2, *be2;
-                   // LayerNorm-folded copies: W . gamma (rounded), column sums of the rounded rows, bias + W beta
-                   void *w_qkv_f, *w_fc1_f; float *cs_qkv, *bf_qkv, *cs_fc1, *bf_fc1;
-                   // split-weight copies [hi | lo] (GemmArgs::a_wrap) of the GEMMs in the tower's w2 mask; null otherwise
-                   void *w_o2 = nullptr, *w_fc22 = nullptr;
-                   // ... of the LayerNorm consumers: folded (W . gamma split, column sums of hi + lo) and plain (LayerNorms materialised)
-                   void *w_qkv_f2 = nullptr, *w_fc1_f2 = nullptr, *w_qkv2 = nullptr, *w_fc12 = nullptr; float *cs_qkv2 = nullptr, *cs_fc12 = nullptr;
-                   // fp8 companions of the six split copies above (null pair: the f16 lo product runs)
-                   F8Pair f8_o2, f8_fc22, f8_qkv_f2, f8_fc1_f2, f8_qkv2, f8_fc12; };
+// One tower GEMM as its launch reads it: the weight rows in ONE form - plain [N, K], split [N, hi(K) | lo(K)] (GemmArgs::a_wrap; with
+// the fp8 companion of the lo halves, a null pair where the shape / type has none) or three-product [N, hi | hi | lo] -, the bias, and
+// for a LayerNorm-folded weight (W . gamma rounded) the column sums of the rounded rows, its bias being bias + W beta (null: not folded)
+struct ClipGemm { void* w = nullptr; float* bias = nullptr; float* col_sum = nullptr; bool split = false; F8Pair f8; };
+static void use_gemm(GemmArgs& g, const ClipGemm& c, int K) {
+    g.W = c.w; g.K = K; g.bias = c.bias; g.col_sum = c.col_sum;
+    if (c.split) use_split(g, c.w, K, c.f8);
+}
+struct ClipLayer { ClipGemm qkv, o, fc1, fc2; float *g1, *be1, *g2, *be2; };
 
 }  // namespace
 
@@ -201,7 +201,7 @@ struct ofx_handle {
     // towers
     int tw_dtype;
     int vit_w2_mask = 0, txt_x3 = 0, proj_x3 = 0, vit_x3 = 0, txt_w2_mask = 0;    // operand scheme (ofx_model_desc); x3 towers hold ONLY the K-concatenated [hi | hi | lo] weight copies
-    void* v_patch_w2 = nullptr; void* v_proj_w3 = nullptr; F8Pair f8_patch;
+    F8Pair f8_patch;        // fp8 companion of v_patch_w when it is split (OFX_W2_PATCH)
     // training: events armed for the NEXT backward call (ofx_train_arm_layer_events), one per outfit-transformer layer
     std::vector<hipEvent_t> bwd_events;
     Arena a_vis; bool vis_ready = false;
@@ -345,82 +345,65 @@ extern "C" int ofx_pack_outfit_weights(ofx_handle* h, const void* const* P, int 
 }
 
 // fp8 copy of a split-weight matrix's lo halves (f16 towers, shapes gemm_w2f8 takes) -> `out` (a null pair where the shape / type has none)
+static bool has_f8(size_t N, size_t K, int dt) { return dt == OFX_F16 && N % 128 == 0 && K % 128 == 0 && K >= 256; }
 static int pack_f8(Arena& A, const void* w2, size_t N, size_t K, int dt, hipStream_t s, F8Pair& out) {
     out = F8Pair{};
-    if (dt != OFX_F16 || N % 128 || K % 128 || K < 256) return OFX_OK;
+    if (!has_f8(N, K, dt)) return OFX_OK;
     char* w8 = A.take<char>(N * K); char* s8 = A.take<char>(N);
     TRY(ofx_launch_pack_lo8(w2, w8, s8, (int)N, (int)K, s));
     out = F8Pair{w8, s8};
     return OFX_OK;
 }
 
-// q/k/v Linear weights -> one [3W, W] operand matrix in q|k|v order (+ fused bias).  `q` points at
-// the 16 per-layer tensors in HF order: k.w,k.b,v.w,v.b,q.w,q.b,out.w,out.b,ln1.w,ln1.b,fc1.w,fc1.b,fc2.w,fc2.b,ln2.w,ln2.b
-static int pack_clip_layer(Arena& A, ClipLayer& L, const void* const* q, size_t W, size_t MLP, int dt, hipStream_t s, int w2_mask = 0, bool x3 = false) {
-    const size_t km = x3 ? 3 : 1;
-    const int mode = x3 ? 2 : 0;                    // x3: every weight row is [hi | hi | lo] (K' = 3K), no single-product / folded copy exists
-    char* wq = A.take<char>(2 * km * 3 * W * W);
-    L.w_qkv = wq;
-    TRY(ofx_launch_pack_rows((const float*)q[4], wq, W, W, W, W, W, mode, dt, s));
-    TRY(ofx_launch_pack_rows((const float*)q[0], wq + 2 * km * W * W, W, W, W, W, W, mode, dt, s));
-    TRY(ofx_launch_pack_rows((const float*)q[2], wq + 4 * km * W * W, W, W, W, W, W, mode, dt, s));
-    L.b_qkv = A.take<float>(3 * W);
-    TRY(copy_f32(L.b_qkv, q[5], W, s)); TRY(copy_f32(L.b_qkv + W, q[1], W, s)); TRY(copy_f32(L.b_qkv + 2 * W, q[3], W, s));
-    L.w_o = A.take<char>(2 * km * W * W); TRY(ofx_launch_pack_rows((const float*)q[6], L.w_o, W, W, W, W, W, mode, dt, s));
-    L.b_o = A.take<float>(W); TRY(copy_f32(L.b_o, q[7], W, s));
-    L.g1 = A.take<float>(W); TRY(copy_f32(L.g1, q[8], W, s));
-    L.be1 = A.take<float>(W); TRY(copy_f32(L.be1, q[9], W, s));
-    L.w_fc1 = A.take<char>(2 * km * MLP * W); TRY(ofx_launch_pack_rows((const float*)q[10], L.w_fc1, MLP, MLP, W, W, W, mode, dt, s));
-    L.b_fc1 = A.take<float>(MLP); TRY(copy_f32(L.b_fc1, q[11], MLP, s));
-    L.w_fc2 = A.take<char>(2 * km * W * MLP); TRY(ofx_launch_pack_rows((const float*)q[12], L.w_fc2, W, W, MLP, MLP, MLP, mode, dt, s));
-    L.b_fc2 = A.take<float>(W); TRY(copy_f32(L.b_fc2, q[13], W, s));
-    L.g2 = A.take<float>(W); TRY(copy_f32(L.g2, q[14], W, s));
-    L.be2 = A.take<float>(W); TRY(copy_f32(L.be2, q[15], W, s));
-    L.w_qkv_f = L.w_fc1_f = nullptr; L.cs_qkv = L.bf_qkv = L.cs_fc1 = L.bf_fc1 = nullptr; L.w_o2 = L.w_fc22 = nullptr;
-    L.w_qkv_f2 = L.w_fc1_f2 = L.w_qkv2 = L.w_fc12 = nullptr; L.cs_qkv2 = L.cs_fc12 = nullptr;
-    L.f8_o2 = L.f8_fc22 = L.f8_qkv_f2 = L.f8_fc1_f2 = L.f8_qkv2 = L.f8_fc12 = F8Pair{};
-    if (x3) return OFX_OK;
-    // folded copies (q, k, v order as above: HF stores k, v, q, out in q[0..7])
-    char* wf = A.take<char>(2 * 3 * W * W);
-    L.w_qkv_f = wf; L.cs_qkv = A.take<float>(3 * W); L.bf_qkv = A.take<float>(3 * W);
-    const int Wi = (int)W;
-    TRY(ofx_launch_fold_pack((const float*)q[4], (const float*)q[8], (const float*)q[9], (const float*)q[5], wf, L.cs_qkv, L.bf_qkv, Wi, Wi, dt, s));
-    TRY(ofx_launch_fold_pack((const float*)q[0], (const float*)q[8], (const float*)q[9], (const float*)q[1], wf + 2 * W * W, L.cs_qkv + W, L.bf_qkv + W, Wi, Wi, dt, s));
-    TRY(ofx_launch_fold_pack((const float*)q[2], (const float*)q[8], (const float*)q[9], (const float*)q[3], wf + 4 * W * W, L.cs_qkv + 2 * W, L.bf_qkv + 2 * W, Wi, Wi, dt, s));
-    L.w_fc1_f = A.take<char>(2 * MLP * W); L.cs_fc1 = A.take<float>(MLP); L.bf_fc1 = A.take<float>(MLP);
-    TRY(ofx_launch_fold_pack((const float*)q[10], (const float*)q[14], (const float*)q[15], (const float*)q[11], L.w_fc1_f, L.cs_fc1, L.bf_fc1, (int)MLP, Wi, dt, s));
-    // split-weight copies: row n = [hi(K) | lo(K)]
-    if (w2_mask & OFX_W2_OUT) { L.w_o2 = A.take<char>(4 * W * W); TRY(ofx_launch_pack_rows((const float*)q[6], L.w_o2, W, W, W, W, W, 3, dt, s)); TRY(pack_f8(A, L.w_o2, W, W, dt, s, L.f8_o2)); }
-    if (w2_mask & OFX_W2_FC2) { L.w_fc22 = A.take<char>(4 * W * MLP); TRY(ofx_launch_pack_rows((const float*)q[12], L.w_fc22, W, W, MLP, MLP, MLP, 3, dt, s)); TRY(pack_f8(A, L.w_fc22, W, MLP, dt, s, L.f8_fc22)); }
-    if (w2_mask & OFX_W2_QKV) {        // q | k | v blocks of [hi | lo] rows (row stride 2 W), folded and plain
-        char* f2 = A.take<char>(4 * 3 * W * W); L.w_qkv_f2 = f2; L.cs_qkv2 = A.take<float>(3 * W);
-        float* bf_scratch = A.take<float>(3 * W);       // bias + W beta is the same as the single copy's: recomputed into scratch
-        char* p2 = A.take<char>(4 * 3 * W * W); L.w_qkv2 = p2;
-        const int src[3] = {4, 0, 2}, bsrc[3] = {5, 1, 3};
-        for (int i = 0; i < 3; ++i) {
-            TRY(ofx_launch_fold_pack((const float*)q[src[i]], (const float*)q[8], (const float*)q[9], (const float*)q[bsrc[i]], f2 + (size_t)i * 4 * W * W,
-                                     L.cs_qkv2 + i * W, bf_scratch + i * W, Wi, Wi, dt, s, 1));
-            TRY(ofx_launch_pack_rows((const float*)q[src[i]], p2 + (size_t)i * 4 * W * W, W, W, W, W, W, 3, dt, s));
+// The one copy of a tower GEMM that its launch reads.  `q` points at the 16 per-layer tensors in HF order: k.w,k.b,v.w,v.b,q.w,q.b,
+// out.w,out.b,ln1.w,ln1.b,fc1.w,fc1.b,fc2.w,fc2.b,ln2.w,ln2.b; `blocks` lists the weights (their biases follow them) stacked as row
+// blocks of Nb rows each (q | k | v: {4, 0, 2}).  mode: 0 plain, 3 split, 2 three-product (ofx_launch_pack_rows); ln >= 0 folds the
+// LayerNorm whose gamma / beta sit at q[ln], q[ln + 1] into the weight (plain or split).
+static int clip_gemm_mode(int w2_mask, int bit, bool x3) { return x3 ? 2 : ((w2_mask & bit) ? 3 : 0); }
+static size_t clip_gemm_bytes(size_t N, size_t K, int mode, bool folded, int dt) {      // the arena bytes pack_clip_gemm takes
+    const size_t km = mode == 2 ? 3 : (mode == 3 ? 2 : 1);
+    return align_up(2 * km * N * K, 256) + (folded ? 2 : 1) * align_up(4 * N, 256) + (mode == 3 && has_f8(N, K, dt) ? align_up(N * K, 256) + align_up(N, 256) : 0);
+}
+static int pack_clip_gemm(Arena& A, ClipGemm& c, const void* const* q, std::initializer_list<int> blocks, size_t Nb, size_t K, int mode, int ln,
+                          int dt, hipStream_t s) {
+    const size_t N = Nb * blocks.size(), km = mode == 2 ? 3 : (mode == 3 ? 2 : 1);
+    c = ClipGemm{};
+    char* w = A.take<char>(2 * km * N * K);
+    c.w = w; c.split = mode == 3; c.bias = A.take<float>(N);
+    if (ln >= 0) c.col_sum = A.take<float>(N);
+    size_t r = 0;
+    for (int i : blocks) {
+        const float* src = (const float*)q[i];
+        if (ln >= 0)
+            TRY(ofx_launch_fold_pack(src, (const float*)q[ln], (const float*)q[ln + 1], (const float*)q[i + 1], w + 2 * km * r * K, c.col_sum + r, c.bias + r,
+                                     (int)Nb, (int)K, dt, s, c.split));
+        else {
+            TRY(ofx_launch_pack_rows(src, w + 2 * km * r * K, (int)Nb, (int)Nb, (int)K, (int)K, (int)K, mode, dt, s));
+            TRY(copy_f32(c.bias + r, q[i + 1], Nb, s));
         }
-        TRY(pack_f8(A, f2, 3 * W, W, dt, s, L.f8_qkv_f2)); TRY(pack_f8(A, p2, 3 * W, W, dt, s, L.f8_qkv2));       // one [3W, W] matrix each: q | k | v row blocks
+        r += Nb;
     }
-    if (w2_mask & OFX_W2_FC1) {
-        L.w_fc1_f2 = A.take<char>(4 * MLP * W); L.cs_fc12 = A.take<float>(MLP);
-        float* bf_scratch = A.take<float>(MLP);
-        TRY(ofx_launch_fold_pack((const float*)q[10], (const float*)q[14], (const float*)q[15], (const float*)q[11], L.w_fc1_f2, L.cs_fc12, bf_scratch, (int)MLP, Wi, dt, s, 1));
-        L.w_fc12 = A.take<char>(4 * MLP * W); TRY(ofx_launch_pack_rows((const float*)q[10], L.w_fc12, MLP, MLP, W, W, W, 3, dt, s));
-        TRY(pack_f8(A, L.w_fc1_f2, MLP, W, dt, s, L.f8_fc1_f2)); TRY(pack_f8(A, L.w_fc12, MLP, W, dt, s, L.f8_fc12));
-    }
+    if (c.split) TRY(pack_f8(A, w, N, K, dt, s, c.f8));       // one [N, K] matrix: q | k | v row blocks
     return OFX_OK;
 }
-static size_t clip_layer_bytes(size_t W, size_t MLP, int w2_mask = 0, bool x3 = false) {
-    if (x3) return 6 * (4 * W * W + 2 * W * MLP) + 4 * (9 * W + MLP) + 32 * 256;
-    return 2 * (4 * W * W + 2 * W * MLP) + 4 * (9 * W + MLP) + 2 * (3 * W * W + W * MLP) + 4 * (6 * W + 2 * MLP) +
-           ((w2_mask & OFX_W2_OUT) ? 4 * W * W : 0) + ((w2_mask & OFX_W2_FC2) ? 4 * W * MLP : 0) +
-           ((w2_mask & OFX_W2_QKV) ? 24 * W * W + 24 * W : 0) + ((w2_mask & OFX_W2_FC1) ? 8 * W * MLP + 8 * MLP : 0) + 44 * 256 +
-           // fp8 companions (N K bytes + N scale bytes per split matrix)
-           ((w2_mask & OFX_W2_OUT) ? W * W + W : 0) + ((w2_mask & OFX_W2_FC2) ? W * MLP + W : 0) + ((w2_mask & OFX_W2_QKV) ? 6 * W * W + 6 * W : 0) +
-           ((w2_mask & OFX_W2_FC1) ? 2 * W * MLP + 2 * MLP : 0) + 12 * 256;
+
+// Folded towers (x3 = false): qkv folds LayerNorm 1 in every layer; fc1 folds LayerNorm 2 except in the pooled last layer, which
+// materialises it on the pooled rows.  Three-product towers materialise every LayerNorm.  Split copies where the layer's mask says so.
+static int pack_clip_layer(Arena& A, ClipLayer& L, const void* const* q, size_t W, size_t MLP, int dt, hipStream_t s, int w2_mask, bool x3, bool last) {
+    TRY(pack_clip_gemm(A, L.qkv, q, {4, 0, 2}, W, W, clip_gemm_mode(w2_mask, OFX_W2_QKV, x3), x3 ? -1 : 8, dt, s));
+    TRY(pack_clip_gemm(A, L.o, q, {6}, W, W, clip_gemm_mode(w2_mask, OFX_W2_OUT, x3), -1, dt, s));
+    TRY(pack_clip_gemm(A, L.fc1, q, {10}, MLP, W, clip_gemm_mode(w2_mask, OFX_W2_FC1, x3), x3 || last ? -1 : 14, dt, s));
+    TRY(pack_clip_gemm(A, L.fc2, q, {12}, W, MLP, clip_gemm_mode(w2_mask, OFX_W2_FC2, x3), -1, dt, s));
+    L.g1 = A.take<float>(W); TRY(copy_f32(L.g1, q[8], W, s));
+    L.be1 = A.take<float>(W); TRY(copy_f32(L.be1, q[9], W, s));
+    L.g2 = A.take<float>(W); TRY(copy_f32(L.g2, q[14], W, s));
+    L.be2 = A.take<float>(W); TRY(copy_f32(L.be2, q[15], W, s));
+    return OFX_OK;
+}
+static size_t clip_layer_bytes(size_t W, size_t MLP, int w2_mask, bool x3, bool last, int dt) {
+    return clip_gemm_bytes(3 * W, W, clip_gemm_mode(w2_mask, OFX_W2_QKV, x3), !x3, dt) + clip_gemm_bytes(W, W, clip_gemm_mode(w2_mask, OFX_W2_OUT, x3), false, dt) +
+           clip_gemm_bytes(MLP, W, clip_gemm_mode(w2_mask, OFX_W2_FC1, x3), !x3 && !last, dt) + clip_gemm_bytes(W, MLP, clip_gemm_mode(w2_mask, OFX_W2_FC2, x3), false, dt) +
+           4 * align_up(4 * W, 256);
 }
 
 extern "C" int ofx_pack_vision_weights(ofx_handle* h, const void* const* P, int n, ofx_stream stream) {
@@ -430,33 +413,35 @@ extern "C" int ofx_pack_vision_weights(ofx_handle* h, const void* const* P, int 
     for (int i = 0; i < n; ++i) OFX_REQUIRE(P[i], OFX_EINVAL, "pack_vision: tensor %d is NULL", i);
     hipStream_t s = (hipStream_t)stream;
     const size_t W = d.vit_width, MLP = d.vit_mlp, KP = 3 * (size_t)d.vit_patch * d.vit_patch, g = d.vit_image / d.vit_patch, S = g * g + 1, PD = d.proj_dim;
-    const bool vx3 = h->vit_x3 != 0;
-    TRY(h->a_vis.reserve(clip_layer_bytes(W, MLP, h->vit_w2_mask, vx3) * d.vit_layers + 6 * W * KP + (W * KP + W + 512) + 8 * PD * W + 4 * (W + S * W + 4 * W) + 18 * 256));
-    Arena& A = h->a_vis;
-    CopyBatch copies;
+    const bool vx3 = h->vit_x3 != 0, psplit = (h->vit_w2_mask & OFX_W2_PATCH) != 0;
     const int dt = h->tw_dtype;
-    h->v_cls = A.take<float>(W); TRY(copy_f32(h->v_cls, P[0], W, s));
-    h->v_patch_w = A.take<char>(2 * W * KP); TRY(ofx_launch_pack_rows((const float*)P[1], h->v_patch_w, W, W, KP, KP, KP, 0, dt, s));
-    h->v_patch_w2 = nullptr; h->f8_patch = F8Pair{};
-    if (h->vit_w2_mask & OFX_W2_PATCH) { h->v_patch_w2 = A.take<char>(4 * W * KP); TRY(ofx_launch_pack_rows((const float*)P[1], h->v_patch_w2, W, W, KP, KP, KP, 3, dt, s)); TRY(pack_f8(A, h->v_patch_w2, W, KP, dt, s, h->f8_patch)); }
-    h->v_pos = A.take<float>(S * W); TRY(copy_f32(h->v_pos, P[2], S * W, s));
-    h->v_pre_g = A.take<float>(W); TRY(copy_f32(h->v_pre_g, P[3], W, s));
-    h->v_pre_b = A.take<float>(W); TRY(copy_f32(h->v_pre_b, P[4], W, s));
-    h->vl.resize(d.vit_layers);
+    std::vector<int> masks(d.vit_layers);
+    size_t layer_bytes = 0;
     for (int l = 0; l < d.vit_layers; ++l) {       // per-layer rungs: a layer outside vit_w2_qkv_layers / vit_w2_fc1_layers keeps the single-product copy of that GEMM
         int m = h->vit_w2_mask;
         if (d.vit_w2_qkv_layers && !((d.vit_w2_qkv_layers >> l) & 1)) m &= ~OFX_W2_QKV;
         if (d.vit_w2_fc1_layers && !((d.vit_w2_fc1_layers >> l) & 1)) m &= ~OFX_W2_FC1;
         if (d.vit_w2_out_layers && !((d.vit_w2_out_layers >> l) & 1)) m &= ~OFX_W2_OUT;
         if (d.vit_w2_fc2_layers && !((d.vit_w2_fc2_layers >> l) & 1)) m &= ~OFX_W2_FC2;
-        TRY(pack_clip_layer(A, h->vl[l], P + 5 + 16 * l, W, MLP, dt, s, m, vx3));
+        masks[l] = m;
+        layer_bytes += clip_layer_bytes(W, MLP, m, vx3, l + 1 == d.vit_layers, dt);
     }
+    TRY(h->a_vis.reserve(layer_bytes + (psplit ? 5 * W * KP + W : 2 * W * KP) + (h->proj_x3 ? 6 : 2) * PD * W + 4 * (W + S * W + 4 * W) + 12 * 256));
+    Arena& A = h->a_vis;
+    CopyBatch copies;
+    h->v_cls = A.take<float>(W); TRY(copy_f32(h->v_cls, P[0], W, s));
+    h->v_patch_w = A.take<char>((psplit ? 4 : 2) * W * KP); TRY(ofx_launch_pack_rows((const float*)P[1], h->v_patch_w, W, W, KP, KP, KP, psplit ? 3 : 0, dt, s));
+    h->f8_patch = F8Pair{};
+    if (psplit) TRY(pack_f8(A, h->v_patch_w, W, KP, dt, s, h->f8_patch));
+    h->v_pos = A.take<float>(S * W); TRY(copy_f32(h->v_pos, P[2], S * W, s));
+    h->v_pre_g = A.take<float>(W); TRY(copy_f32(h->v_pre_g, P[3], W, s));
+    h->v_pre_b = A.take<float>(W); TRY(copy_f32(h->v_pre_b, P[4], W, s));
+    h->vl.resize(d.vit_layers);
+    for (int l = 0; l < d.vit_layers; ++l) TRY(pack_clip_layer(A, h->vl[l], P + 5 + 16 * l, W, MLP, dt, s, masks[l], vx3, l + 1 == d.vit_layers));
     const void* const* t = P + 5 + 16 * d.vit_layers;
     h->v_post_g = A.take<float>(W); TRY(copy_f32(h->v_post_g, t[0], W, s));
     h->v_post_b = A.take<float>(W); TRY(copy_f32(h->v_post_b, t[1], W, s));
-    h->v_proj_w = A.take<char>(2 * PD * W); TRY(ofx_launch_pack_rows((const float*)t[2], h->v_proj_w, PD, PD, W, W, W, 0, dt, s));
-    h->v_proj_w3 = nullptr;
-    if (h->proj_x3) { h->v_proj_w3 = A.take<char>(6 * PD * W); TRY(ofx_launch_pack_rows((const float*)t[2], h->v_proj_w3, PD, PD, W, W, W, 2, dt, s)); }
+    h->v_proj_w = A.take<char>(2 * (h->proj_x3 ? 3 : 1) * PD * W); TRY(ofx_launch_pack_rows((const float*)t[2], h->v_proj_w, PD, PD, W, W, W, h->proj_x3 ? 2 : 0, dt, s));
     OFX_REQUIRE(A.off <= A.cap, OFX_ESTATE, "pack_vision: arena overflow");
     TRY(copies.flush(s));
     h->vis_ready = true;
@@ -472,14 +457,15 @@ extern "C" int ofx_pack_text_weights(ofx_handle* h, const void* const* P, int n,
     const size_t W = d.txt_width, MLP = d.txt_mlp, V = d.txt_vocab, NP = d.txt_max_pos, PD = d.proj_dim;
     const bool x3 = h->txt_x3 != 0, x3p = x3 || h->proj_x3;          // x3p: the final LayerNorm + text_projection tail in three products
     const int tmask = x3 ? 0 : h->txt_w2_mask;
-    TRY(h->a_txt.reserve(clip_layer_bytes(W, MLP, tmask, x3) * d.txt_layers + 4 * (V * W + NP * W + 2 * W) + 6 * PD * W + 16 * 256));
+    const int dt = h->tw_dtype;
+    TRY(h->a_txt.reserve(clip_layer_bytes(W, MLP, tmask, x3, false, dt) * (d.txt_layers - 1) + clip_layer_bytes(W, MLP, tmask, x3, true, dt) +
+                         4 * (V * W + NP * W + 2 * W) + 6 * PD * W + 16 * 256));
     Arena& A = h->a_txt;
     CopyBatch copies;
-    const int dt = h->tw_dtype;
     h->t_tok = A.take<float>(V * W); TRY(copy_f32(h->t_tok, P[0], V * W, s));
     h->t_pos = A.take<float>(NP * W); TRY(copy_f32(h->t_pos, P[1], NP * W, s));
     h->tl.resize(d.txt_layers);
-    for (int l = 0; l < d.txt_layers; ++l) TRY(pack_clip_layer(A, h->tl[l], P + 2 + 16 * l, W, MLP, dt, s, tmask, x3));
+    for (int l = 0; l < d.txt_layers; ++l) TRY(pack_clip_layer(A, h->tl[l], P + 2 + 16 * l, W, MLP, dt, s, tmask, x3, l + 1 == d.txt_layers));
     const void* const* t = P + 2 + 16 * d.txt_layers;
     h->t_fin_g = A.take<float>(W); TRY(copy_f32(h->t_fin_g, t[0], W, s));
     h->t_fin_b = A.take<float>(W); TRY(copy_f32(h->t_fin_b, t[1], W, s));
@@ -516,12 +502,14 @@ size_t carve_set(const ofx_handle* h, Bump& b, int B, int L, SetWs* w) {
     return b.off;
 }
 struct ClipWs { float* X; char* H; char* QKV; char* U; int* idx; char* PL; float* E; float* XP; char* HP; char* UP; char* slab; size_t slab_bytes;
-                char* XB; float* P; float* S; char* XLO; };   // LayerNorm folding: raw operand copy of X, per-segment partial stats, (mean, rstd), lo half of the (hi, lo) stream
-// km = 3: the three-product towers keep their GEMM operands K-concatenated ([hi | lo | hi] rows of 3 W / 3 MLP elements);
+                char* XB; float* P; float* S; char* XLO; };   // LayerNorm folding: the (hi, lo) residual stream XB / XLO, per-segment partial stats, (mean, rstd)
+// km = 3: the three-product towers keep their GEMM operands K-concatenated ([hi | lo | hi] rows of 3 W / 3 MLP elements), their residual
+// stream in the fp32 X; the folded towers (km = 1) keep it in XB / XLO.  x: the fp32 rows X are carved for the folded tower too (the text
+// embedding writes them).  A buffer a tower does not use stays null.
 // kk = K multiplier of the pooled-row GEMMs' split-K plans (2 with split weights, 3 in three-product mode)
-size_t carve_clip(Bump& b, size_t rows, size_t n, size_t W, size_t MLP, size_t PD, size_t u_min_bytes, size_t qkv_min_bytes, ClipWs* w, size_t km = 1, size_t kk = 1) {
-    ClipWs t;
-    t.X = b.take<float>(rows * W);
+size_t carve_clip(Bump& b, size_t rows, size_t n, size_t W, size_t MLP, size_t PD, size_t u_min_bytes, size_t qkv_min_bytes, ClipWs* w, size_t km, size_t kk, bool x) {
+    ClipWs t{};
+    if (km == 3 || x) t.X = b.take<float>(rows * W);
     t.H = b.take<char>(rows * km * W * 2);
     t.QKV = b.take<char>(std::max(rows * 3 * W * (km == 3 ? 4 : 2), qkv_min_bytes));      // three-product towers keep q | k | v in fp32
     t.U = b.take<char>(std::max(rows * km * MLP * 2, u_min_bytes));
@@ -536,10 +524,12 @@ size_t carve_clip(Bump& b, size_t rows, size_t n, size_t W, size_t MLP, size_t P
         t.slab_bytes = std::max(std::max(std::max(ofx_gemm_splitk_bytes((int)n, (int)W, (int)(k * W)), ofx_gemm_splitk_bytes((int)n, (int)MLP, (int)(k * W))),
                                          std::max(ofx_gemm_splitk_bytes((int)n, (int)W, (int)(k * MLP)), ofx_gemm_splitk_bytes((int)n, (int)PD, (int)(k * W)))), t.slab_bytes);
     t.slab = b.take<char>(t.slab_bytes);
-    t.XB = b.take<char>(rows * W * 2);
-    t.P = b.take<float>(rows * (W / 64) * 2);
-    t.S = b.take<float>(rows * 2);
-    t.XLO = b.take<char>(rows * W * 2);
+    if (km != 3) {
+        t.XB = b.take<char>(rows * W * 2);
+        t.P = b.take<float>(rows * (W / 64) * 2);
+        t.S = b.take<float>(rows * 2);
+        t.XLO = b.take<char>(rows * W * 2);
+    }
     if (w) *w = t;
     return b.off;
 }
@@ -548,13 +538,13 @@ size_t vit_bytes(const ofx_handle* h, int n, ClipWs* w, void* ws, size_t cap) {
     const size_t g = d.vit_image / d.vit_patch, S = g * g + 1, KP = 3 * (size_t)d.vit_patch * d.vit_patch;
     Bump b(ws, cap);
     // the patch matrix aliases U and the fp32 patch-GEMM output aliases QKV (both dead before the layers start)
-    size_t r = carve_clip(b, (size_t)n * S, n, d.vit_width, d.vit_mlp, d.proj_dim, (size_t)n * g * g * KP * 2, (size_t)n * g * g * d.vit_width * 4, w, h->vit_x3 ? 3 : 1, h->vit_x3 ? 3 : 2);
+    size_t r = carve_clip(b, (size_t)n * S, n, d.vit_width, d.vit_mlp, d.proj_dim, (size_t)n * g * g * KP * 2, (size_t)n * g * g * d.vit_width * 4, w, h->vit_x3 ? 3 : 1, h->vit_x3 ? 3 : 2, false);
     return align_up(r, 256);
 }
 size_t txt_bytes(const ofx_handle* h, int n, int Tc, ClipWs* w, void* ws, size_t cap) {
     const ofx_model_desc& d = h->d;
     Bump b(ws, cap);
-    size_t r = carve_clip(b, (size_t)n * Tc, n, d.txt_width, d.txt_mlp, d.proj_dim, 0, 0, w, h->txt_x3 ? 3 : 1, h->txt_x3 ? 3 : (h->txt_w2_mask ? 2 : 1));
+    size_t r = carve_clip(b, (size_t)n * Tc, n, d.txt_width, d.txt_mlp, d.proj_dim, 0, 0, w, h->txt_x3 ? 3 : 1, h->txt_x3 ? 3 : (h->txt_w2_mask ? 2 : 1), true);
     return align_up(r, 256);
 }
 constexpr int VIT_CHUNK_MAX = 2048;
@@ -722,97 +712,70 @@ int ofx_launch_fused_qkv_attn(const void* X, const void* Wqkv, const float* bias
 int g_x3_vit_f32_attn = 0;   // ofx_tune(20, v), experiment: 1 = the three-product ViT keeps q | k | v in fp32 and runs the fp32 set attention (as the text tower does) instead of
                             // the MFMA attention on operand-rounded q | k | v - what the attention core's operand rounding costs under peaked attention
 int g_prune_q = 1;      // ofx_tune(8, v): 1 = the ViT's last layer computes queries for the CLS rows only
-int g_ln_fold = 2;      // ofx_tune(6, v) (default 2): 0 = materialise every LayerNorm, 1 = fold the towers' LayerNorms into the GEMM epilogues,
-                        // 2 = fold AND keep the residual stream as an operand-type (hi, lo) pair (no fp32 stream between the layers)
 
-// fold == true: on entry w.XB / w.S hold the operand copy and the (mean, rstd) of X; on exit (non-pooled layers) they hold
-// those of the layer's output, produced by the fc2 epilogue.  No LayerNorm kernel runs on the full rows.
+// One CLIP encoder layer with its LayerNorms folded into the GEMM epilogues.  On entry w.XB / w.XLO hold the residual stream as an
+// operand-type (hi, lo) pair and w.S the (mean, rstd) of its rows; the out-proj / fc2 epilogues add into the pair in place and leave
+// per-segment statistics for the next folded consumer, so no LayerNorm kernel runs on the full rows.  The pooled last layer
+// (`pool_idx`) gathers the pooled rows into the fp32 w.XP and runs its tail there, LayerNorm 2 materialised.
 static int clip_layer(const ClipLayer& L, const ClipWs& w, int rows, int nseq, int S, int W, int MLP, int heads, int act,
-                      float eps, int causal, const int64_t* key_mask, int mask_ld, int dt, const int* pool_idx, hipStream_t s, bool fold = false,
-                      bool pool_first = false) {
-    // fused QKV projection + attention (non-pooled ViT layers: one 33..64-token tile per sequence, no mask): q | k | v never reach HBM
-    const bool qkv_w2 = L.w_qkv_f2 != nullptr;     // split q | k | v weights: the dual-weight variant of the fused kernel, or (ofx_tune(9, 1)) the dual-weight GEMM + the attention kernel
-    const bool fused = (g_fuse_qkv & (qkv_w2 ? 2 : 1)) && !pool_idx && !causal && !key_mask && S >= 33 && S <= 64 && (256 / S - 1) * S + 64 - 256 <= 16;   // (the kernel's key-row overshoot fits its 16 pad rows)
+                      float eps, int causal, const int64_t* key_mask, int mask_ld, int dt, const int* pool_idx, hipStream_t s, bool pool_first) {
+    // fused QKV projection + attention (non-pooled ViT layers: one 33..64-token tile per sequence, no mask): q | k | v never reach HBM;
+    // split q | k | v weights: its dual-weight variant (ofx_tune(9, 3)), else the dual-weight GEMM + the attention kernel
+    const bool fused = (g_fuse_qkv & (L.qkv.split ? 2 : 1)) && !pool_idx && !causal && !key_mask && S >= 33 && S <= 64 && (256 / S - 1) * S + 64 - 256 <= 16;   // (the kernel's key-row overshoot fits its 16 pad rows)
     if (fused) {
-        if (fold) {
-            TRY(ofx_launch_fused_qkv_attn(w.XB, qkv_w2 ? L.w_qkv_f2 : L.w_qkv_f, L.bf_qkv, w.S, qkv_w2 ? L.cs_qkv2 : L.cs_qkv, w.H, nseq, S, W, heads, W, W, 0.125f, dt, s, qkv_w2));
-        } else {
-            LnArgs ln{w.X, nullptr, L.g1, L.be1, w.U, rows, W, W, OFX_OUT_OP, eps};        // the MLP buffer is idle here; the kernel must not read what it writes
-            TRY(ofx_launch_layernorm(ln, dt, s));
-            TRY(ofx_launch_fused_qkv_attn(w.U, qkv_w2 ? L.w_qkv2 : L.w_qkv, L.b_qkv, nullptr, nullptr, w.H, nseq, S, W, heads, W, W, 0.125f, dt, s, qkv_w2));
-        }
-    }
-    GemmArgs g1{}; g1.C = w.QKV; g1.M = rows; g1.N = 3 * W; g1.K = W; g1.lda = W;
-    g1.ldc = 3 * W; g1.act = OFX_ACT_NONE; g1.out_kind = OFX_OUT_OP;
-    size_t wrow = (size_t)W * 2;                   // bytes per weight row of g1.W
-    if (fused) {
-    } else if (fold) {
-        g1.A = w.XB; g1.W = L.w_qkv_f; g1.bias = L.bf_qkv; g1.row_stat = w.S; g1.col_sum = L.cs_qkv;
-        if (qkv_w2) { use_split(g1, L.w_qkv_f2, W, L.f8_qkv_f2); g1.col_sum = L.cs_qkv2; wrow *= 2; }
+        TRY(ofx_launch_fused_qkv_attn(w.XB, L.qkv.w, L.qkv.bias, w.S, L.qkv.col_sum, w.H, nseq, S, W, heads, W, W, 0.125f, dt, s, L.qkv.split));
     } else {
-        LnArgs ln{w.X, nullptr, L.g1, L.be1, w.H, rows, W, W, OFX_OUT_OP, eps};
-        TRY(ofx_launch_layernorm(ln, dt, s));
-        g1.A = w.H; g1.W = L.w_qkv; g1.bias = L.b_qkv;
-        if (qkv_w2) { use_split(g1, L.w_qkv2, W, L.f8_qkv2); wrow *= 2; }
-    }
-    if (fused) {
-    } else if (pool_idx && pool_first && g_prune_q) {
-        // last layer, pooled row = first row of every sequence (ViT CLS): only those rows' queries are ever used.  K | V for all
-        // rows (weight rows W .. 3W), then Q for the nseq pooled rows through strided A / C / statistics.  The other rows' Q
-        // columns keep stale workspace bytes; their attention outputs are never read (the tail gathers the pooled rows only).
-        GemmArgs kv = g1;
-        kv.W = (const char*)g1.W + (size_t)W * wrow; kv.bias = g1.bias + W; kv.C = (char*)w.QKV + (size_t)W * 2; kv.N = 2 * W;
-        if (g1.W8) { kv.W8 = (const char*)g1.W8 + (size_t)W * W; kv.w8_scale = (const char*)g1.w8_scale + W; }      // weight rows W .. 3W: fp8 rows of W bytes, scale bytes 128 per 128-row block
-        if (fold) kv.col_sum = g1.col_sum + W;
-        TRY(ofx_launch_gemm(kv, dt, s));
-        GemmArgs q = g1;
-        q.M = nseq; q.N = W; q.lda = S * W; q.ldc = S * 3 * W; q.stat_ld = S;
-        TRY(ofx_launch_gemm(q, dt, s));
-    } else
-        TRY(ofx_launch_gemm(g1, dt, s));
-    if (!fused) {
+        GemmArgs g1{}; g1.A = w.XB; g1.C = w.QKV; g1.row_stat = w.S; g1.M = rows; g1.N = 3 * W; g1.lda = W;
+        g1.ldc = 3 * W; g1.act = OFX_ACT_NONE; g1.out_kind = OFX_OUT_OP;
+        use_gemm(g1, L.qkv, W);
+        const bool prune = pool_idx && pool_first && g_prune_q;
+        if (prune) {
+            // last layer, pooled row = first row of every sequence (ViT CLS): only those rows' queries are ever used.  K | V for all
+            // rows (weight rows W .. 3W), then Q for the nseq pooled rows through strided A / C / statistics.  The other rows' Q
+            // columns keep stale workspace bytes; their attention outputs are never read (the tail gathers the pooled rows only).
+            GemmArgs kv = g1;
+            kv.W = (const char*)g1.W + (size_t)W * g1.K * 2; kv.bias = g1.bias + W; kv.col_sum = g1.col_sum + W; kv.C = (char*)w.QKV + (size_t)W * 2; kv.N = 2 * W;
+            if (g1.W8) { kv.W8 = (const char*)g1.W8 + (size_t)W * W; kv.w8_scale = (const char*)g1.w8_scale + W; }      // weight rows W .. 3W: fp8 rows of W bytes, scale bytes 128 per 128-row block
+            TRY(ofx_launch_gemm(kv, dt, s));
+            GemmArgs q = g1;
+            q.M = nseq; q.N = W; q.lda = S * W; q.ldc = S * 3 * W; q.stat_ld = S;
+            TRY(ofx_launch_gemm(q, dt, s));
+        } else
+            TRY(ofx_launch_gemm(g1, dt, s));
         AttnArgs at{w.QKV, w.H, key_mask, nseq, S, heads, 3 * W, W, W, 2 * W, mask_ld, causal, 0.125f};
-        at.only_row0 = (pool_idx && pool_first && g_prune_q) ? 1 : 0;       // pruned last layer of the ViT: only the CLS query row is read afterwards
+        at.only_row0 = prune ? 1 : 0;       // pruned last layer of the ViT: only the CLS query row is read afterwards
         TRY(ofx_launch_attention_mfma(at, dt, s));
     }
-    float* X = w.X; char* H = w.H; char* U = w.U; int M = rows;
+    char* H = w.H; char* U = w.U; int M = rows;
     if (pool_idx) {
         TRY(ofx_launch_gather_rows(w.H, pool_idx, w.HP, nseq, W * 2, W * 2, s));
-        if (fold && g_ln_fold == 2) TRY(ofx_launch_gather_hilo(w.XB, w.XLO, pool_idx, w.XP, nseq, W, dt, s));
-        else TRY(ofx_launch_gather_rows(w.X, pool_idx, w.XP, nseq, W * 4, W * 4, s));
-        X = w.XP; H = w.HP; U = w.UP; M = nseq;
+        TRY(ofx_launch_gather_hilo(w.XB, w.XLO, pool_idx, w.XP, nseq, W, dt, s));
+        H = w.HP; U = w.UP; M = nseq;
     }
-    GemmArgs g2{}; g2.A = H; g2.W = L.w_o; g2.C = X; g2.bias = L.b_o; g2.resid = X; g2.M = M; g2.N = W; g2.K = W; g2.lda = W;
-    g2.ldc = W; g2.ldr = W; g2.act = OFX_ACT_NONE; g2.out_kind = OFX_OUT_F32;
-    if (pool_idx) { g2.slab = w.slab; g2.slab_bytes = w.slab_bytes; }
-    const bool fold2 = fold && !pool_idx;          // the pruned last layer runs its tail on the pooled rows, unfolded
-    const bool hilo = fold && g_ln_fold == 2;      // residual stream = (XB, XLO) operand-type pair, no fp32 X (ofx_tune(6, 2))
-    if (fold2) { g2.xb_out = w.XB; g2.stat_part = w.P; }
-    if (fold2 && hilo) { g2.xlo = w.XLO; g2.C = w.XB; g2.ldc = W; g2.out_kind = OFX_OUT_OP; g2.resid = nullptr; }
-    if (L.w_o2) use_split(g2, L.w_o2, W, L.f8_o2);                                       // split weights: A . (hi + lo)^T
+    // out-proj and fc2 add into the residual stream: the (hi, lo) pair in place, or the pooled fp32 rows
+    auto to_stream = [&](GemmArgs& g) {
+        g.M = M; g.N = W; g.ldc = W; g.ldr = W; g.act = OFX_ACT_NONE;
+        if (pool_idx) { g.C = w.XP; g.resid = w.XP; g.out_kind = OFX_OUT_F32; g.slab = w.slab; g.slab_bytes = w.slab_bytes; }
+        else { g.C = w.XB; g.xb_out = w.XB; g.xlo = w.XLO; g.stat_part = w.P; g.out_kind = OFX_OUT_OP; }
+    };
+    GemmArgs g2{}; g2.A = H; g2.lda = W;
+    use_gemm(g2, L.o, W); to_stream(g2);
     TRY(ofx_launch_gemm(g2, dt, s));
-    GemmArgs g3{}; g3.C = U; g3.M = M; g3.N = MLP; g3.K = W; g3.lda = W;
-    g3.ldc = MLP; g3.act = act; g3.out_kind = OFX_OUT_OP;
-    if (fold2) {
-        TRY(ofx_launch_stats_finalize(w.P, W / 64, W, eps, w.S, M, s));
-        g3.A = w.XB; g3.W = L.w_fc1_f; g3.bias = L.bf_fc1; g3.row_stat = w.S; g3.col_sum = L.cs_fc1;
-        if (L.w_fc1_f2) { use_split(g3, L.w_fc1_f2, W, L.f8_fc1_f2); g3.col_sum = L.cs_fc12; }
-    } else {
-        LnArgs ln2{X, nullptr, L.g2, L.be2, H, M, W, W, OFX_OUT_OP, eps};
+    GemmArgs g3{}; g3.C = U; g3.M = M; g3.N = MLP; g3.lda = W; g3.ldc = MLP; g3.act = act; g3.out_kind = OFX_OUT_OP;
+    if (pool_idx) {
+        LnArgs ln2{w.XP, nullptr, L.g2, L.be2, H, M, W, W, OFX_OUT_OP, eps};
         TRY(ofx_launch_layernorm(ln2, dt, s));
-        g3.A = H; g3.W = L.w_fc1; g3.bias = L.b_fc1;
-        if (L.w_fc12) use_split(g3, L.w_fc12, W, L.f8_fc12);
+        g3.A = H; g3.slab = w.slab; g3.slab_bytes = w.slab_bytes;
+    } else {
+        TRY(ofx_launch_stats_finalize(w.P, W / 64, W, eps, w.S, M, s));
+        g3.A = w.XB; g3.row_stat = w.S;
     }
-    if (pool_idx) { g3.slab = w.slab; g3.slab_bytes = w.slab_bytes; }
+    use_gemm(g3, L.fc1, W);
     TRY(ofx_launch_gemm(g3, dt, s));
-    GemmArgs g4{}; g4.A = U; g4.W = L.w_fc2; g4.C = X; g4.bias = L.b_fc2; g4.resid = X; g4.M = M; g4.N = W; g4.K = MLP;
-    g4.lda = MLP; g4.ldc = W; g4.ldr = W; g4.act = OFX_ACT_NONE; g4.out_kind = OFX_OUT_F32;
-    if (pool_idx) { g4.slab = w.slab; g4.slab_bytes = w.slab_bytes; }
-    if (fold2) { g4.xb_out = w.XB; g4.stat_part = w.P; }
-    if (fold2 && hilo) { g4.xlo = w.XLO; g4.C = w.XB; g4.ldc = W; g4.out_kind = OFX_OUT_OP; g4.resid = nullptr; }
-    if (L.w_fc22) use_split(g4, L.w_fc22, MLP, L.f8_fc22);
+    GemmArgs g4{}; g4.A = U; g4.lda = MLP;
+    use_gemm(g4, L.fc2, MLP); to_stream(g4);
     TRY(ofx_launch_gemm(g4, dt, s));
-    if (fold2) TRY(ofx_launch_stats_finalize(w.P, W / 64, W, eps, w.S, M, s));
+    if (!pool_idx) TRY(ofx_launch_stats_finalize(w.P, W / 64, W, eps, w.S, M, s));
     return OFX_OK;
 }
 
@@ -823,7 +786,7 @@ static int clip_layer_x3(const ClipLayer& L, const ClipWs& w, int rows, int nseq
                          float eps, int causal, const int64_t* key_mask, int mask_ld, int dt, const int* pool_idx, hipStream_t s, bool mfma_attn = false) {
     LnArgs ln{w.X, nullptr, L.g1, L.be1, w.H, rows, W, 3 * W, OFX_OUT_SPLIT3, eps};
     TRY(ofx_launch_layernorm(ln, dt, s));
-    GemmArgs g1{}; g1.A = w.H; g1.W = L.w_qkv; g1.C = w.QKV; g1.bias = L.b_qkv; g1.M = rows; g1.N = 3 * W; g1.K = 3 * W; g1.k_mult = 3; g1.lda = 3 * W;
+    GemmArgs g1{}; g1.A = w.H; g1.W = L.qkv.w; g1.C = w.QKV; g1.bias = L.qkv.bias; g1.M = rows; g1.N = 3 * W; g1.K = 3 * W; g1.k_mult = 3; g1.lda = 3 * W;
     // q | k | v stay fp32 and the attention runs in fp32 arithmetic (the outfit transformer's set kernel with HF's causal AND
     // key-padding mask, up to 64 rows per sequence): rounding q, k, v, P to the operand type alone leaves 3.5e-4 at the text embedding
     // (tests/studies/operand_scheme_cpu.py); the single-tile MFMA kernel stays as the fallback beyond 64 rows (never reached:
@@ -848,37 +811,35 @@ static int clip_layer_x3(const ClipLayer& L, const ClipWs& w, int rows, int nseq
         TRY(ofx_launch_gather_rows(w.X, pool_idx, w.XP, nseq, W * 4, W * 4, s));
         X = w.XP; H = w.HP; U = w.UP; M = nseq;
     }
-    GemmArgs g2{}; g2.A = H; g2.W = L.w_o; g2.C = X; g2.bias = L.b_o; g2.resid = X; g2.M = M; g2.N = W; g2.K = 3 * W; g2.k_mult = 3; g2.lda = 3 * W;
+    GemmArgs g2{}; g2.A = H; g2.W = L.o.w; g2.C = X; g2.bias = L.o.bias; g2.resid = X; g2.M = M; g2.N = W; g2.K = 3 * W; g2.k_mult = 3; g2.lda = 3 * W;
     g2.ldc = W; g2.ldr = W; g2.act = OFX_ACT_NONE; g2.out_kind = OFX_OUT_F32;
     if (pool_idx) { g2.slab = w.slab; g2.slab_bytes = w.slab_bytes; }          // the split-K scratch is sized for the pooled rows
     TRY(ofx_launch_gemm(g2, dt, s));
     LnArgs ln2{X, nullptr, L.g2, L.be2, H, M, W, 3 * W, OFX_OUT_SPLIT3, eps};
     TRY(ofx_launch_layernorm(ln2, dt, s));
-    GemmArgs g3{}; g3.A = H; g3.W = L.w_fc1; g3.C = U; g3.bias = L.b_fc1; g3.M = M; g3.N = MLP; g3.K = 3 * W; g3.k_mult = 3; g3.lda = 3 * W;
+    GemmArgs g3{}; g3.A = H; g3.W = L.fc1.w; g3.C = U; g3.bias = L.fc1.bias; g3.M = M; g3.N = MLP; g3.K = 3 * W; g3.k_mult = 3; g3.lda = 3 * W;
     g3.ldc = 3 * MLP; g3.act = act; g3.out_kind = OFX_OUT_SPLIT3;
     if (pool_idx) { g3.slab = w.slab; g3.slab_bytes = w.slab_bytes; }
     TRY(ofx_launch_gemm(g3, dt, s));
-    GemmArgs g4{}; g4.A = U; g4.W = L.w_fc2; g4.C = X; g4.bias = L.b_fc2; g4.resid = X; g4.M = M; g4.N = W; g4.K = 3 * MLP; g4.k_mult = 3;
+    GemmArgs g4{}; g4.A = U; g4.W = L.fc2.w; g4.C = X; g4.bias = L.fc2.bias; g4.resid = X; g4.M = M; g4.N = W; g4.K = 3 * MLP; g4.k_mult = 3;
     g4.lda = 3 * MLP; g4.ldc = W; g4.ldr = W; g4.act = OFX_ACT_NONE; g4.out_kind = OFX_OUT_F32;
     if (pool_idx) { g4.slab = w.slab; g4.slab_bytes = w.slab_bytes; }
     return ofx_launch_gemm(g4, dt, s);
 }
 
-// All layers; the pooled rows end up compacted in w.XP [nseq, W].
-static bool clip_fold(int W) { return g_ln_fold != 0 && W % 64 == 0; }
+// All layers; the pooled rows end up compacted in w.XP [nseq, W].  On entry the residual stream sits in w.X (x3) or, with its row
+// statistics, in w.XB / w.XLO / w.S.
 static int clip_layers(const std::vector<ClipLayer>& Ls, const ClipWs& w, int rows, int nseq, int S, int W, int MLP,
                        int heads, int act, float eps, int causal, const int64_t* key_mask, int mask_ld, int dt,
-                       const int* pool_idx, hipStream_t s, bool stats_ready = false, bool pool_first = false, bool x3 = false) {
+                       const int* pool_idx, hipStream_t s, bool pool_first, bool x3) {
     if (x3) {
         for (size_t l = 0; l < Ls.size(); ++l)
             TRY(clip_layer_x3(Ls[l], w, rows, nseq, S, W, MLP, heads, act, eps, causal, key_mask, mask_ld, dt, l + 1 == Ls.size() ? pool_idx : nullptr, s, !causal && !key_mask && !g_x3_vit_f32_attn));
         return OFX_OK;
     }
-    const bool fold = clip_fold(W);
-    if (fold && !stats_ready) TRY(ofx_launch_row_stats_cast(w.X, w.XB, w.S, rows, W, eps, dt, s, g_ln_fold == 2 ? w.XLO : nullptr));     // layer 0's LayerNorm-1 inputs
     for (size_t l = 0; l < Ls.size(); ++l)
         TRY(clip_layer(Ls[l], w, rows, nseq, S, W, MLP, heads, act, eps, causal, key_mask, mask_ld, dt,
-                       l + 1 == Ls.size() ? pool_idx : nullptr, s, fold, pool_first));
+                       l + 1 == Ls.size() ? pool_idx : nullptr, s, pool_first));
     return OFX_OK;
 }
 
@@ -913,17 +874,17 @@ static int vit_core(ofx_handle* h, const float* pixels, const RawImages* raw, in
             TRY(ofx_launch_patchify(pixels + (size_t)n0 * px_per_img, w.U, n, d.vit_image, d.vit_patch, dt, s));
         GemmArgs gp{}; gp.A = w.U; gp.W = h->v_patch_w; gp.C = w.QKV; gp.M = n * g * g; gp.N = W; gp.K = KP; gp.lda = KP; gp.ldc = W;
         gp.act = OFX_ACT_NONE; gp.out_kind = OFX_OUT_F32;
-        if (h->v_patch_w2) use_split(gp, h->v_patch_w2, (int)KP, h->f8_patch);
+        if (h->vit_w2_mask & OFX_W2_PATCH) use_split(gp, h->v_patch_w, KP, h->f8_patch);
         TRY(ofx_launch_gemm(gp, dt, s));
-        const bool fold = clip_fold(W) && !h->vit_x3;                    // the pre-LN kernel then also emits layer 0's operand copy + statistics
-        TRY(ofx_launch_vit_embed_ln((const float*)w.QKV, h->v_cls, h->v_pos, h->v_pre_g, h->v_pre_b, fold && g_ln_fold == 2 ? nullptr : w.X, n, S, W, d.ln_eps, s, fold ? w.XB : nullptr,
-                                    fold ? w.S : nullptr, dt, fold && g_ln_fold == 2 ? w.XLO : nullptr));
+        // the pre-LN kernel writes the stream the layers start from: X (three-product ViT), or the (hi, lo) pair + row statistics
+        // (the carve leaves the other form's buffers null)
+        TRY(ofx_launch_vit_embed_ln((const float*)w.QKV, h->v_cls, h->v_pos, h->v_pre_g, h->v_pre_b, w.X, n, S, W, d.ln_eps, s, w.XB, w.S, dt, w.XLO));
         TRY(ofx_launch_iota_rows(w.idx, n, S, s));                        // CLS rows
-        TRY(clip_layers(h->vl, w, rows, n, S, W, d.vit_mlp, d.vit_heads, d.vit_act, d.ln_eps, 0, nullptr, 0, dt, w.idx, s, fold, true, h->vit_x3 != 0));
-        const int pk = h->v_proj_w3 ? 3 : 1;          // the output tail in three products: post-LayerNorm rows [hi | lo | hi] x [hi | hi | lo]
+        TRY(clip_layers(h->vl, w, rows, n, S, W, d.vit_mlp, d.vit_heads, d.vit_act, d.ln_eps, 0, nullptr, 0, dt, w.idx, s, true, h->vit_x3 != 0));
+        const int pk = h->proj_x3 ? 3 : 1;            // the output tail in three products: post-LayerNorm rows [hi | lo | hi] x [hi | hi | lo]
         LnArgs ln{w.XP, nullptr, h->v_post_g, h->v_post_b, w.PL, n, W, pk * W, pk == 3 ? OFX_OUT_SPLIT3 : OFX_OUT_OP, d.ln_eps};
         TRY(ofx_launch_layernorm(ln, dt, s));
-        GemmArgs gj{}; gj.A = w.PL; gj.W = pk == 3 ? h->v_proj_w3 : h->v_proj_w; gj.C = w.E; gj.M = n; gj.N = d.proj_dim; gj.K = pk * W; gj.k_mult = pk; gj.lda = pk * W; gj.ldc = d.proj_dim;
+        GemmArgs gj{}; gj.A = w.PL; gj.W = h->v_proj_w; gj.C = w.E; gj.M = n; gj.N = d.proj_dim; gj.K = pk * W; gj.k_mult = pk; gj.lda = pk * W; gj.ldc = d.proj_dim;
         gj.act = OFX_ACT_NONE; gj.out_kind = OFX_OUT_F32; gj.slab = w.slab; gj.slab_bytes = w.slab_bytes;
         TRY(ofx_launch_gemm(gj, dt, s));
         TRY(ofx_launch_l2norm_store(w.E, emb + (size_t)n0 * emb_ld, n, d.proj_dim, emb_ld, emb_col, normalize, s));
@@ -976,7 +937,8 @@ extern "C" int ofx_clip_text_fwd(ofx_handle* h, const int64_t* ids, const int64_
     TRY(ofx_launch_text_eos_index(ids, w.idx, N, T, Tc, d.txt_eos_id, s));      // EOS rows
     const bool x3 = h->txt_x3 != 0, x3p = x3 || h->proj_x3;
     const int pk = x3p ? 3 : 1;
-    TRY(clip_layers(h->tl, w, rows, N, Tc, W, d.txt_mlp, d.txt_heads, d.txt_act, d.ln_eps, 1, attn_mask, T, dt, w.idx, s, false, false, x3));
+    if (!x3) TRY(ofx_launch_row_stats_cast(w.X, w.XB, w.XLO, w.S, rows, W, d.ln_eps, dt, s));      // layer 0's (hi, lo) stream + LayerNorm-1 statistics
+    TRY(clip_layers(h->tl, w, rows, N, Tc, W, d.txt_mlp, d.txt_heads, d.txt_act, d.ln_eps, 1, attn_mask, T, dt, w.idx, s, false, x3));
     LnArgs ln{w.XP, nullptr, h->t_fin_g, h->t_fin_b, w.PL, N, W, pk * W, x3p ? OFX_OUT_SPLIT3 : OFX_OUT_OP, d.ln_eps};
     TRY(ofx_launch_layernorm(ln, dt, s));
     GemmArgs gj{}; gj.A = w.PL; gj.W = h->t_proj_w; gj.C = w.E; gj.M = N; gj.N = d.proj_dim; gj.K = pk * W; gj.k_mult = pk; gj.lda = pk * W; gj.ldc = d.proj_dim;
@@ -1369,7 +1331,7 @@ extern "C" int ofx_tune(int knob, int value) {
     switch (knob) {
         case 2: g_gemm_kernel = value; return OFX_OK;
         case 5: g_gemm_splitk = value; return OFX_OK;
-        case 6: g_ln_fold = value; return OFX_OK;
+        case 6: if (value != 2) { ofx_set_error("ofx_tune(6): %d is not 2 (the towers' LayerNorms are always folded)", value); return OFX_EINVAL; } return OFX_OK;
         case 7: g_train_mfma_attn = value; return OFX_OK;
         case 8: g_prune_q = value; return OFX_OK;
         case 9: g_fuse_qkv = value; return OFX_OK;

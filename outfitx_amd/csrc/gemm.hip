@@ -230,14 +230,14 @@ int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
     k.ka_tiles = ka / BK;
     k.M = g.M; k.N = g.N; k.K = g.K; k.lda = g.lda; k.ldc = g.ldc; k.ldr = g.ldr; k.act = g.act; k.out_kind = g.out_kind; k.drop = g.drop; k.n_valid = g.N;
     k.xb_out = (char*)g.xb_out; k.stat_part = g.stat_part; k.row_stat = g.row_stat; k.col_sum = g.col_sum; k.stat_ld = g.stat_ld > 0 ? g.stat_ld : 1; k.xlo = (char*)g.xlo;
-    OFX_REQUIRE(!g.xlo || (g.xb_out && g.stat_part), OFX_EINVAL, "gemm: xlo needs the LayerNorm-fold producer outputs");
-    OFX_REQUIRE(!(g.xb_out || g.stat_part) || ((g.out_kind == 0 || (g.xlo && g.out_kind == 1 && g.C == g.xb_out && g.ldc == g.N)) && g.N % 64 == 0), OFX_EINVAL,
-                "gemm: LayerNorm-fold producer outputs need an fp32 output (or, with xlo, C == xb_out in the operand type)");
+    const bool producer = g.xb_out || g.stat_part || g.xlo;
+    OFX_REQUIRE(!producer || (g.xb_out && g.stat_part && g.xlo && g.C == g.xb_out && g.out_kind == 1 && g.ldc == g.N && g.N % 64 == 0), OFX_EINVAL,
+                "gemm: a LayerNorm-fold producer takes xb_out, stat_part and xlo together, with C == xb_out in the operand type");
     OFX_REQUIRE(!g.row_stat || g.col_sum, OFX_EINVAL, "gemm: row_stat needs col_sum");
-    OFX_REQUIRE(!(g.row_stat || g.xb_out || g.stat_part) || (!g.aux_out && !g.drop.thresh && g.act != OFX_ACT_MISH && g.act != OFX_ACT_MISH_GRAD), OFX_EINVAL,
+    OFX_REQUIRE(!(g.row_stat || producer) || (!g.aux_out && !g.drop.thresh && g.act != OFX_ACT_MISH && g.act != OFX_ACT_MISH_GRAD), OFX_EINVAL,
                 "gemm: LayerNorm folding does not combine with the training epilogue features");
-    OFX_REQUIRE(!g.row_stat || !g.resid, OFX_EINVAL, "gemm: a LayerNorm-fold consumer takes no residual");
-    OFX_REQUIRE(!(g.xb_out || g.stat_part) || g.act == OFX_ACT_NONE, OFX_EINVAL, "gemm: a LayerNorm-fold producer has no activation");
+    OFX_REQUIRE(!(g.row_stat || producer) || !g.resid, OFX_EINVAL, "gemm: LayerNorm folding takes no residual (a producer's stream is (xb_out, xlo))");
+    OFX_REQUIRE(!producer || g.act == OFX_ACT_NONE, OFX_EINVAL, "gemm: a LayerNorm-fold producer has no activation");
     static DeviceOnce attr_set;
     TRY(attr_set.run([]() -> int {
         OFX_HIP(hipFuncSetAttribute((const void*)gemm_128x128_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES));
@@ -269,12 +269,12 @@ int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
     if (g_ofx_prof_on) {
         const int km = g.a_wrap ? g.K / g.a_wrap : (g.k_mult > 0 ? g.k_mult : 1);
         // algorithmic HBM bytes of this launch: A once (its k index wraps over a_wrap columns for split weights), the weight rows as
-        // stored, and per output element what the configured epilogue moves: fp32 4 (+4 residual read, +2 operand copy), operand
-        // type 2 (in-place (hi, lo) stream: 4 read + 4 written), [hi | lo | hi] 6, +4 pre-activation tape copy
+        // stored, and per output element what the configured epilogue moves: fp32 4 (+4 residual read), operand type 2 (in-place
+        // (hi, lo) stream: 4 read + 4 written), [hi | lo | hi] 6, +4 pre-activation tape copy
         const double ab = kind == 9 ? 2.0 * g.M * (g.K / 3) * 2 : 2.0 * g.M * (g.a_wrap ? g.a_wrap : g.K), wb = kind == 8 ? 3.0 * g.N * g.a_wrap : (kind == 9 ? 2.0 * g.N * (g.K / 3) * 2 : 2.0 * g.N * g.K);      // kind 8 reads the hi rows (2 B) + the fp8 lo rows (1 B)
         double ob = g.out_kind == 0 ? 4.0 : (g.out_kind == 2 ? 6.0 : 2.0);
         if (g.xlo) ob = 8.0;
-        else { if (g.resid) ob += 4.0; if (g.xb_out) ob += 2.0; }
+        else if (g.resid) ob += 4.0;
         if (g.aux_out) ob += 4.0;
         ofx_prof_set_tag(g.M, g.N, g.K / km, kind, km, ab + wb + ob * g.M * g.N);
     }
@@ -297,7 +297,7 @@ int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
         int gm = (int)((3u << 20) / ((size_t)BM * g.K * 2) / 2);
         gm = gm < 1 ? 1 : (gm > 8 ? 8 : gm);
         k.group_m = gm;
-        const bool can_split = g.slab && !g.xb_out && !g.stat_part && !g.row_stat;
+        const bool can_split = g.slab && !producer && !g.row_stat;
         const bool can64 = (kind == 5) || (kind == 1 && g_gemm_kernel == 0 && g.M > 64 && (long)k.tiles_m * k.tiles_n <= 384);
         SmallPlan pl = plan_small(g.M, g.N, g.K, can_split, can64);
         if (kind == 5) pl.tile64 = 1;

@@ -79,7 +79,7 @@ __device__ __forceinline__ void epilogue(const KArgs& p, OFX_LDS float* ep, int 
                     for (int e = 0; e < 4; ++e) v[e] *= act_mish_grad(rr[e]);
                 } else v += rr;
             }
-            if (p.xlo) {            // LayerNorm-fold producer on a (hi, lo) residual stream (see epilogue2, FOLD 3): in-place update
+            if (p.xlo) {            // LayerNorm-fold producer on the (hi, lo) residual stream (see epilogue2, FOLD 3): in-place update
                 T* hp = (T*)p.xb_out + (size_t)gm * p.N + gn;
                 T* lp = (T*)p.xlo + (size_t)gm * p.N + gn;
                 const v4 h0 = *(const v4*)hp, l0 = *(const v4*)lp;
@@ -92,17 +92,6 @@ __device__ __forceinline__ void epilogue(const KArgs& p, OFX_LDS float* ep, int 
                 if ((lane & 15) == 15) *(f32x2*)(p.stat_part + ((size_t)gm * (p.N >> 6) + (gn0 >> 6)) * 2) = f32x2{ssum, ssq};
             } else if (p.out_kind == 0) {
                 *(f32x4*)(p.C + ((size_t)gm * p.ldc + gn) * 4) = v;
-                if (p.xb_out) {
-                    v4 hb;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) hb[e] = (T)v[e];
-                    *(v4*)((T*)p.xb_out + (size_t)gm * p.N + gn) = hb;
-                }
-                if (p.stat_part) {          // gm is uniform over the 16 lanes that share this row
-                    const float ssum = row16_sum_to_lane15((v[0] + v[1]) + (v[2] + v[3]));
-                    const float ssq = row16_sum_to_lane15((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]));
-                    if ((lane & 15) == 15) *(f32x2*)(p.stat_part + ((size_t)gm * (p.N >> 6) + (gn0 >> 6)) * 2) = f32x2{ssum, ssq};
-                }
             } else {
                 v4 hi;
 #pragma unroll
@@ -142,9 +131,9 @@ __device__ __forceinline__ float act_apply(float v) {
     return v;
 }
 
-// FOLD (LayerNorm folding, compile-time so the common path keeps its registers): 0 none, 1 producer (fp32 output + operand copy
-// + per-segment statistics), 2 consumer (row statistics + column sums applied to the accumulator), 3 producer whose residual
-// stream is the operand-type pair (xb_out = hi, xlo = lo = x - hi), read and rewritten in place - no fp32 copy of the stream.
+// FOLD (LayerNorm folding, compile-time so the common path keeps its registers): 0 none, 2 consumer (row statistics + column sums
+// applied to the accumulator), 3 producer whose residual stream is the operand-type pair (xb_out = hi, xlo = lo = x - hi), read and
+// rewritten in place with per-segment statistics - no fp32 copy of the stream.
 // NP x 16 rows by 64 columns of the wave's accumulators: acc[i][J0 + j], i < NP passes, j < 4 column fragments (the 128x64 wave tile
 // is NP = 8, JW = 4, J0 = 0; a 64x128 wave tile drains as two halves NP = 4, JW = 8, J0 = 0 / 4).
 template <typename T, int ACT, int FOLD = 0, int RAMP = 0, int NP = 8, int JW = 4, int J0 = 0>
@@ -207,17 +196,6 @@ __device__ __forceinline__ void epilogue2(const KArgs& p, OFX_LDS char* ep, f32x
                         for (int e = 0; e < 4; ++e) v[e] *= act_mish_grad((RAMP ? resr[RAMP ? i : 0][it] : res[i % (DEPTH + 1)][it])[e]);
                     } else v += (RAMP ? resr[RAMP ? i : 0][it] : res[i % (DEPTH + 1)][it]);
                     *(f32x4*)(p.C + ((size_t)gm * p.ldc + gn) * 4) = v;
-                    if (FOLD == 1 && p.xb_out) {
-                        typename OpT<T>::v4 hb;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) hb[e] = (T)v[e];
-                        *(typename OpT<T>::v4*)((T*)p.xb_out + (size_t)gm * p.N + gn) = hb;
-                    }
-                    if (FOLD == 1 && p.stat_part) {      // gm is uniform over the 16 lanes (same rsub) that share this row
-                        const float ssum = row16_sum_to_lane15((v[0] + v[1]) + (v[2] + v[3]));
-                        const float ssq = row16_sum_to_lane15((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]));
-                        if (chunk == 15) *(f32x2*)(p.stat_part + ((size_t)gm * (p.N >> 6) + (gn0 >> 6)) * 2) = f32x2{ssum, ssq};
-                    }
                 }
             }
         }
@@ -408,7 +386,7 @@ __device__ __forceinline__ void epilogue_direct(const KArgs& p, f32x4 (&acc)[NP]
 
 template <typename T, int NP, int JW>
 __device__ __forceinline__ bool epilogue_direct_dispatch(const KArgs& p, f32x4 (&acc)[NP][JW], int gm0, int gn0, int lane, OFX_LDS float* st) {
-    if (!p.epi_direct || p.out_kind != 1 || p.resid || p.xb_out || p.stat_part || p.aux_out || p.drop.thresh || p.n_valid != p.N) return false;
+    if (!p.epi_direct || p.out_kind != 1 || p.resid || p.xlo || p.aux_out || p.drop.thresh || p.n_valid != p.N) return false;
     if ((size_t)p.M * p.ldc * 2 >= 0x7fffffff) return false;
 #define OFX_EPD(ACT_, FOLD_) { epilogue_direct<T, ACT_, FOLD_, NP, JW>(p, acc, gm0, gn0, lane, st); return true; }
     if (p.row_stat) {
@@ -440,9 +418,8 @@ __device__ __forceinline__ void epilogue2_dispatch(const KArgs& p, OFX_LDS char*
         }
         return;
     }
-    if (p.xb_out || p.stat_part) {
-        if (p.xlo) epilogue2<T, OFX_ACT_NONE, 3, 1, NP, JW, J0>(p, ep, acc, gm0, gn0, lane);
-        else epilogue2<T, OFX_ACT_NONE, 1, 1, NP, JW, J0>(p, ep, acc, gm0, gn0, lane);
+    if (p.xlo) {                                       // LayerNorm-fold producer: (xb_out, xlo) stream + stat_part (ofx_launch_gemm checks the triple)
+        epilogue2<T, OFX_ACT_NONE, 3, 1, NP, JW, J0>(p, ep, acc, gm0, gn0, lane);
         return;
     }
     switch (p.act) {

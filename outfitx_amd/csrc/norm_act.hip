@@ -210,8 +210,8 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* px, T* out, 
     }
 }
 
-// x[n*50 + t] = LN( (t == 0 ? cls : patch_out[n*49 + t-1]) + pos[t] )  -> fp32 residual stream
-// Optionally (LayerNorm folding) also the operand-type copy of the output row and its (mean, rstd): layer 0's LayerNorm-1 inputs.
+// x[n*50 + t] = LN( (t == 0 ? cls : patch_out[n*49 + t-1]) + pos[t] )  -> the residual stream: fp32 rows x (three-product ViT), or
+// (LayerNorm folding) the operand-type pair (xb = hi, xlo = x - hi) and the rows' (mean, rstd), layer 0's LayerNorm-1 inputs.
 template <int NCH, typename T>
 __global__ __launch_bounds__(256) void vit_embed_ln_kernel(const float* patch_out, const float* cls, const float* pos,
                                                           const float* gamma, const float* beta, float* x, int N, int S,
@@ -243,7 +243,7 @@ __global__ __launch_bounds__(256) void vit_embed_ln_kernel(const float* patch_ou
         for (int c = 0; c < NCH; ++c) {
             const int col = (lane + 64 * c) * 4;
             v[c] = v[c] * rstd * *(const f32x4*)(gamma + col) + *(const f32x4*)(beta + col);
-            if (x) *(f32x4*)(x + (size_t)r * D + col) = v[c];          // NULL: the stream lives in (xb, xlo) only
+            if (x) *(f32x4*)(x + (size_t)r * D + col) = v[c];
             so += (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]);
         }
         if (xb) {
@@ -256,12 +256,10 @@ __global__ __launch_bounds__(256) void vit_embed_ln_kernel(const float* patch_ou
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { const float dlt = v[c][e] - mo; qo += dlt * dlt; o[e] = (T)v[c][e]; }
                 *(v4*)(xb + (size_t)r * D + col) = o;
-                if (xlo) {              // residual stream as a (hi, lo) operand-type pair: lo = x - hi
-                    v4 l;
+                v4 l;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) l[e] = (T)(v[c][e] - (float)o[e]);
-                    *(v4*)(xlo + (size_t)r * D + col) = l;
-                }
+                for (int e = 0; e < 4; ++e) l[e] = (T)(v[c][e] - (float)o[e]);
+                *(v4*)(xlo + (size_t)r * D + col) = l;
             }
             qo = wave_sum(qo);
             if (lane == 0) { stat[2 * (size_t)r] = mo; stat[2 * (size_t)r + 1] = rsqrtf(qo * (1.0f / D) + eps); }
@@ -434,7 +432,9 @@ __global__ __launch_bounds__(256) void cir_prefix_kernel(const float* img_emb, c
 }
 
 // ---- LayerNorm folding support (GemmArgs::row_stat / col_sum) ---------------------------------------------------------
-// First layer of a tower: operand-type copy of the raw rows + their (mean, rstd).  One wave per row.
+// First layer of a tower: the raw rows as an operand-type (hi, lo) pair + their (mean, rstd).  One wave per row.  The launcher
+// always passes Xlo; the kernel keeps its null test because the variance sum it compiles to with it (fma for some terms, a rounded
+// product for others) is the one the text tower's results are bit-for-bit tied to.
 template <typename T>
 __global__ __launch_bounds__(256) void row_stats_cast_kernel(const float* X, T* Xb, float* stat, int rows, int W, float eps, T* Xlo) {
     typedef typename OpT<T>::v4 v4;
@@ -541,6 +541,7 @@ int ofx_launch_patchify(const float* px, void* out, int N, int img, int patch, i
 int ofx_launch_vit_embed_ln(const float* patch_out, const float* cls, const float* pos, const float* g, const float* b,
                             float* x, int N, int S, int D, float eps, hipStream_t s, void* xb, float* stat, int op_dtype, void* xlo) {
     OFX_REQUIRE(D == 768 || D == 512 || D == 1024, OFX_ESHAPE, "vit_embed_ln: D=%d", D);
+    OFX_REQUIRE(x ? !xb && !stat && !xlo : xb && stat && xlo, OFX_EINVAL, "vit_embed_ln: writes either x or the (xb, xlo) stream + stat");
     const int grid = rows_grid(N * S);
     ProfScope prof(PROF_NORM, s);
 #define VEL(NCH, T) hipLaunchKernelGGL((vit_embed_ln_kernel<NCH, T>), dim3(grid), dim3(256), 0, s, patch_out, cls, pos, g, b, x, N, S, eps, (T*)xb, stat, (T*)xlo)
@@ -602,8 +603,9 @@ int ofx_launch_gather_hilo(const void* hi, const void* lo, const int* idx, float
     OFX_LAUNCH_CHECK();
     return OFX_OK;
 }
-int ofx_launch_row_stats_cast(const float* X, void* Xb, float* stat, int rows, int W, float eps, int op_dtype, hipStream_t s, void* Xlo) {
+int ofx_launch_row_stats_cast(const float* X, void* Xb, void* Xlo, float* stat, int rows, int W, float eps, int op_dtype, hipStream_t s) {
     OFX_REQUIRE(W % 4 == 0 && rows > 0, OFX_ESHAPE, "row_stats_cast: rows=%d W=%d", rows, W);
+    OFX_REQUIRE(Xb && Xlo && stat, OFX_EINVAL, "row_stats_cast: the (hi, lo) pair and the statistics are all written");
     ProfScope prof(PROF_NORM, s);
     if (op_dtype == OFX_F16) hipLaunchKernelGGL(row_stats_cast_kernel<f16_t>, dim3(rows_grid(rows)), dim3(256), 0, s, X, (f16_t*)Xb, stat, rows, W, eps, (f16_t*)Xlo);
     else hipLaunchKernelGGL(row_stats_cast_kernel<bf16_t>, dim3(rows_grid(rows)), dim3(256), 0, s, X, (bf16_t*)Xb, stat, rows, W, eps, (bf16_t*)Xlo);

@@ -229,15 +229,15 @@ struct GemmArgs {
     int out_kind;       // 0 fp32 | 1 operand type | 2 split3 (hi|lo|hi at column blocks of width N, ldc >= 3N; bf16 only)
     DropArgs drop;      // applied to act(acc + bias) BEFORE the residual add (MISH_GRAD: to acc before the mish' factor)
     // ---- LayerNorm folding (CLIP towers): the LayerNorm between a residual-stream producer and the next linear layer is
-    // never materialised.  Producer side (fp32 output): also store the operand-type copy of the output row and, per row
-    // and per 64-column segment, (sum, sum of squares) -> stat_part[row][segment] (float2).  Consumer side: A is that raw
-    // copy, W is pre-scaled by gamma, and the epilogue applies  rstd[row] * (acc - mean[row] * col_sum[n]) + bias[n].
+    // never materialised.  Producer side (xb_out, xlo and stat_part together, C == xb_out, no resid): the residual stream is the
+    // operand-type pair (hi at xb_out, lo = x - hi at xlo), read, added to and rewritten in place, and per row and per 64-column
+    // segment (sum, sum of squares) -> stat_part[row][segment] (float2).  Consumer side: A is the hi half, W is pre-scaled by
+    // gamma, and the epilogue applies  rstd[row] * (acc - mean[row] * col_sum[n]) + bias[n].
     void* xb_out = nullptr;         // [M, N] operand type
     float* stat_part = nullptr;     // [M, N / 64, 2]
     const float* row_stat = nullptr;   // [M, 2] (mean, rstd)
     int stat_ld = 1;                   // row m's statistics sit at row_stat[2 * m * stat_ld] (strided A rows)
-    void* xlo = nullptr;               // producer with xb_out: the residual stream is the operand-type pair (xb_out, xlo), updated in place;
-                                       // `resid` / `C` are then unused (no fp32 copy of the stream exists)
+    void* xlo = nullptr;               // [M, N] operand type
     const float* col_sum = nullptr;    // [N] column sums of the (rounded) gamma-scaled weight rows
     // ---- split weights against ONE copy of A ("W2"): W = [N, K] with K = 2 a_wrap, row n = [hi(a_wrap) | lo(a_wrap)]; A is
     // [M, a_wrap] and its k index wraps, so C = A . (hi + lo)^T: ~22 significant weight bits for two MFMA products
@@ -290,8 +290,7 @@ int ofx_launch_pack_rows(const float* src, void* dst, int rows_src, int rows_dst
                          int mode, int op_dtype, hipStream_t s);
 int ofx_launch_patchify(const float* px, void* out, int N, int img, int patch, int op_dtype, hipStream_t s);
 int ofx_launch_vit_embed_ln(const float* patch_out, const float* cls, const float* pos, const float* g, const float* b,
-                            float* x, int N, int S, int D, float eps, hipStream_t s, void* xb = nullptr, float* stat = nullptr, int op_dtype = OFX_BF16,
-                            void* xlo = nullptr);
+                            float* x, int N, int S, int D, float eps, hipStream_t s, void* xb, float* stat, int op_dtype, void* xlo);
 int ofx_launch_text_embed(const int64_t* ids, const float* tok, const float* pos, float* x, int N, int T, int Tc, int D,
                           int vocab, hipStream_t s);
 int ofx_launch_text_eos_index(const int64_t* ids, int* row_idx, int N, int T, int Tc, int eos_id, hipStream_t s);
@@ -304,7 +303,7 @@ int ofx_launch_set_build_indexed(const float* table, int ld, long long n_table, 
                                  int prefix_stride, int* cu_rows, float* X, int B, int D, hipStream_t s);
 int ofx_preprocess_to(const uint8_t* src, const long long* offsets, const int* heights, const int* widths, int N, int channels, int size,
                       const float* mean, const float* stdv, float* out, void* patches, int patch, int op_dtype, void* ws, size_t ws_bytes, hipStream_t stream);
-int ofx_launch_row_stats_cast(const float* X, void* Xb, float* stat, int rows, int W, float eps, int op_dtype, hipStream_t s, void* Xlo = nullptr);
+int ofx_launch_row_stats_cast(const float* X, void* Xb, void* Xlo, float* stat, int rows, int W, float eps, int op_dtype, hipStream_t s);
 int ofx_launch_gather_hilo(const void* hi, const void* lo, const int* idx, float* dst, int rows, int W, int op_dtype, hipStream_t s);
 int ofx_launch_stats_finalize(const float* part, int slots, int W, float eps, float* stat, int rows, hipStream_t s);
 int ofx_launch_fold_pack(const float* Wsrc, const float* gamma, const float* beta, const float* bias, void* Wf, float* col_sum, float* bias_f,
