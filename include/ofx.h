@@ -233,6 +233,23 @@ int ofx_focal_loss(const float* logits, const float* labels, int B, float alpha,
  * *loss, if given, their sum. */
 int ofx_focal_loss_ex(const float* logits, const float* labels, int B, float alpha, float gamma, float upstream, int reduction, float* loss,
                       float* per_elem, float* dlogits, ofx_stream stream);
+/* SetWiseRankingLoss(margin) forward and upstream * d loss / d y_hat (src/losses/set_wise_ranking_loss.py:15-36), the CIR trainer's loss
+ * (complementary_item_retrieval_trainer.py:79-88), fp32, one pass over the negatives.  Stateless (no handle).
+ *   y, y_hat [B, D]; neg [B, K, D] (contiguous; may be NULL when K = 0); neg_mask [B, K], one byte per entry, non-zero = padded
+ *   (NULL = nothing padded).  d_pos = ||y_hat - y + 1e-6|| (F.pairwise_distance's eps), d_k = ||y_hat - neg_k||;
+ *   *loss = sum over valid (b, k) of relu(d_pos - d_k + margin) / max(#valid in the batch, 1)
+ *         + mean over b of relu(d_pos - min over valid k of d_k + margin)       (a row without a valid negative adds 0);
+ *   dy_hat [B, D] (may be NULL: value only) = upstream * d loss / d y_hat: relu'(0) = 0, ties for the hardest negative go to the lowest
+ *   index, a zero distance contributes a zero direction (never a NaN).  There is no gradient into y or neg.
+ *   d_pos [B], d_neg [B, K] (either may be NULL): the distances, for tests and diagnostics; padded entries of d_neg read +inf and their
+ *   rows of neg are never loaded.
+ * Supported: B >= 1, K >= 0, D % 4 == 0, 4 <= D <= 4096 (else OFX_ESHAPE); y, y_hat, neg, dy_hat 16-byte aligned.  Workspace:
+ * the size function below (no alignment beyond 16 bytes; contents need not survive the call).  Two launches; deterministic - no
+ * floating-point atomics, two calls on the same inputs return the same bits.  While K * D <= 10240 floats (K <= 10 at D = 1024) a row's negatives
+ * stay in LDS between the distance pass and the gradient pass; beyond that the gradient pass re-reads them (outfitx_amd/csrc/rank_loss.hip). */
+size_t ofx_set_rank_loss_ws_bytes(int B, int K, int D);
+int ofx_set_rank_loss(const float* y, const float* y_hat, const float* neg, const uint8_t* neg_mask, int B, int K, int D, float margin,
+                      float upstream, float* loss, float* dy_hat, float* d_pos, float* d_neg, void* ws, size_t ws_bytes, ofx_stream stream);
 
 /* ------------------------------------------------------------------ profiling --------------- */
 /* HIP-event timing of every launch, by category {0 GEMM, 1 norm/embed, 2 attention, 3 other}.

@@ -155,6 +155,8 @@ SIGNATURES = {
     "ofx_dropout_mask": (_i, [_f, C.c_uint, _i, _i, _i, _vp, _vp]),
     "ofx_focal_loss": (_i, [_vp, _vp, _i, _f, _f, _f, _vp, _vp, _vp]),
     "ofx_focal_loss_ex": (_i, [_vp, _vp, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp]),
+    "ofx_set_rank_loss_ws_bytes": (_sz, [_i, _i, _i]),
+    "ofx_set_rank_loss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ofx_profile_enable": (None, [_i]),
     "ofx_profile_read": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
     "ofx_profile_records": (_i, [C.POINTER(ProfRecord), _i]),

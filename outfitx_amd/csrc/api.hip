@@ -138,6 +138,9 @@ int ofx_launch_set_attention_bwd_mfma(const void* qkv, const float* d_o, void* d
 int ofx_launch_drop_rows(float* x, int rows, int cols, const DropArgs& d, hipStream_t s);
 int ofx_launch_focal_loss(const float* logits, const float* labels, int B, float alpha, float gamma, float upstream, float* loss, float* dlogits, hipStream_t s,
                           int reduction = 1, float* per_elem = nullptr);
+size_t ofx_set_rank_loss_ws(int B, int K);
+int ofx_launch_set_rank_loss(const float* y, const float* y_hat, const float* neg, const uint8_t* mask, int B, int K, int D, float margin, float upstream,
+                             float* loss, float* dy_hat, float* d_pos, float* d_neg, void* ws, hipStream_t s);
 int ofx_launch_cp_head_bwd(const float* dlogits, const float* w_or_rows, const int* cu, float* dX, void* dXb, float* db, int B, int D, int op_dtype,
                            const DropArgs& head, const DropArgs& below, hipStream_t s, int accumulate = 0);
 int ofx_launch_fitb(const float* y, const float* cand, int B, int C, int D, int64_t* idx, float* dist, hipStream_t s);
@@ -1321,6 +1324,18 @@ extern "C" int ofx_focal_loss_ex(const float* logits, const float* labels, int B
     OFX_REQUIRE(logits && labels && B > 0 && reduction >= 0 && reduction <= 2, OFX_EINVAL, "focal_loss_ex: bad argument");
     OFX_REQUIRE(reduction != 0 || per_elem, OFX_EINVAL, "focal_loss_ex: reduction 'none' needs per_elem");
     return ofx_launch_focal_loss(logits, labels, B, alpha, gamma, upstream, loss, dlogits, (hipStream_t)stream, reduction, per_elem);
+}
+
+static bool rank_loss_shape_ok(int B, int K, int D) { return B >= 1 && K >= 0 && D >= 4 && D <= 4096 && D % 4 == 0; }
+extern "C" size_t ofx_set_rank_loss_ws_bytes(int B, int K, int D) { return rank_loss_shape_ok(B, K, D) ? ofx_set_rank_loss_ws(B, K) : 0; }
+extern "C" int ofx_set_rank_loss(const float* y, const float* y_hat, const float* neg, const uint8_t* neg_mask, int B, int K, int D, float margin,
+                                 float upstream, float* loss, float* dy_hat, float* d_pos, float* d_neg, void* ws, size_t ws_bytes, ofx_stream stream) {
+    OFX_REQUIRE(rank_loss_shape_ok(B, K, D), OFX_ESHAPE, "set_rank_loss: B = %d, K = %d, D = %d; needs B >= 1, K >= 0, D %% 4 == 0, 4 <= D <= 4096", B, K, D);
+    OFX_REQUIRE(y && y_hat && loss && ws && (neg || K == 0), OFX_EINVAL, "set_rank_loss: NULL argument");
+    OFX_REQUIRE((((uintptr_t)y | (uintptr_t)y_hat | (uintptr_t)neg | (uintptr_t)dy_hat | (uintptr_t)ws) & 15) == 0, OFX_EINVAL,
+                "set_rank_loss: y, y_hat, neg, dy_hat and ws must be 16-byte aligned");
+    OFX_REQUIRE(ws_bytes >= ofx_set_rank_loss_ws(B, K), OFX_EWORKSPACE, "set_rank_loss: workspace %zu < %zu bytes", ws_bytes, ofx_set_rank_loss_ws(B, K));
+    return ofx_launch_set_rank_loss(y, y_hat, neg, neg_mask, B, K, D, margin, upstream, loss, dy_hat, d_pos, d_neg, ws, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------- tuning

@@ -430,6 +430,36 @@ def focal_loss(logits: torch.Tensor, labels: torch.Tensor, alpha: float, gamma: 
     return (per if red == 0 else loss), dl
 
 
+def set_rank_loss(y: torch.Tensor, y_hat: torch.Tensor, neg: torch.Tensor, neg_mask: Optional[torch.Tensor], margin: float,
+                  upstream: float = 1.0, need_grad: bool = True):
+    """SetWiseRankingLoss(margin) (src/losses/set_wise_ranking_loss.py:15-36) and upstream * d loss / d y_hat from one pass over the
+    negatives (ofx_set_rank_loss).  y, y_hat [B, D]; neg [B, K, D]; neg_mask [B, K], True / non-zero = padded (None: nothing padded).
+    -> (0-d loss, dy_hat [B, D] or None)."""
+    lib = L.load()
+    dev = y_hat.device
+    if dev.type != "cuda":
+        raise L.OfxError("set_rank_loss needs HIP tensors; the torch expression in losses.SetWiseRankingLoss is the CPU path")
+    if y_hat.dim() != 2 or neg.dim() != 3 or y.shape != y_hat.shape or neg.shape[0] != y_hat.shape[0] or neg.shape[2] != y_hat.shape[1]:
+        raise ValueError(f"set_rank_loss: y {tuple(y.shape)}, y_hat {tuple(y_hat.shape)}, neg {tuple(neg.shape)} are not [B,D], [B,D], [B,K,D]")
+    B, D = y_hat.shape
+    K = neg.shape[1]
+    yc, hc, nc = _f32c(y.detach(), dev), _f32c(y_hat.detach(), dev), _f32c(neg.detach(), dev)
+    mk = None
+    if neg_mask is not None:
+        if tuple(neg_mask.shape) != (B, K):
+            raise ValueError(f"set_rank_loss: neg_mask {tuple(neg_mask.shape)} is not [B,K] = {(B, K)}")
+        mk = neg_mask.to(dev)
+        mk = (mk if mk.dtype in (torch.bool, torch.uint8) else mk != 0).contiguous().view(torch.uint8)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    dy = torch.empty_like(hc) if need_grad else None
+    n_ws = lib.ofx_set_rank_loss_ws_bytes(B, K, D)
+    ws = torch.empty(max(n_ws, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.ofx_set_rank_loss(_ptr(yc), _ptr(hc), _ptr(nc) if K else None, _ptr(mk) if K else None, B, K, D, float(margin), float(upstream),
+                                      _ptr(loss), _ptr(dy), None, None, _ptr(ws), ws.numel(), _stream(dev)), "ofx_set_rank_loss")
+    return loss, dy
+
+
 def topk_merge(idx_parts: torch.Tensor, dist_parts: torch.Tensor):
     """[parts,nq,k] per-shard candidates (global indices) -> ([nq,k] idx, [nq,k] dist), ascending, ties -> smaller idx."""
     lib = L.load()

@@ -2,13 +2,17 @@
 d loss / d logits come from ONE kernel (ofx_focal_loss_ex; reduction 'mean' | 'sum' | 'none' as focal_loss.py:36-41) instead of
 ~12 eager elementwise launches.  Used by the CP
 trainer as `FocalLoss(alpha=0.75, gamma=2, reduction='mean')` (compatibility_prediction_trainer.py:369-370).
-No CPU path: HIP tensors only."""
+No CPU path: HIP tensors only.
+
+SetWiseRankingLoss — drop-in for `src.losses.SetWiseRankingLoss` (src/losses/set_wise_ranking_loss.py:5-39), the CIR trainer's loss:
+on HIP tensors the value and d loss / d y_hat come from one pass over the negatives (ofx_set_rank_loss); everywhere else (CPU
+tensors, other dtypes, gradients wanted into the positives or the negatives) it is the torch expression."""
 from __future__ import annotations
 
 import torch
 from torch import nn
 
-from .engine import focal_loss
+from .engine import focal_loss, set_rank_loss
 
 
 class _FocalFn(torch.autograd.Function):
@@ -37,19 +41,49 @@ class FocalLoss(nn.Module):
         return _FocalFn.apply(y_hat, y_true, float(self.alpha), float(self.gamma), self.reduction)
 
 
+class _SetRankFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y_hat, y, neg, neg_mask, margin):
+        loss, dy = set_rank_loss(y, y_hat, neg, neg_mask, margin, 1.0, need_grad=y_hat.requires_grad)
+        ctx.save_for_backward(dy)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dy,) = ctx.saved_tensors
+        return dy * g, None, None, None, None
+
+
 class SetWiseRankingLoss(nn.Module):
     """Drop-in for the reference's `src.losses.SetWiseRankingLoss` (src/losses/set_wise_ranking_loss.py:5-39), the CIR trainer's
     loss (complementary_item_retrieval_trainer.py:79-88): with d+ = ||y_hat - y||, d-_k = ||y_hat - neg_k||,
         L_all  = sum over valid negatives of relu(d+ - d-_k + margin) / max(#valid, 1)
         L_hard = mean_b relu(d+ - min_k d-_k + margin)            (padded negatives count as +inf)
-    returned as L_all + L_hard.  Caller-side torch code on [B,D] / [B,K,D] tensors (autograd supplies d loss / d y_hat, which
-    the HIP backward of the CIR path consumes); `pairwise_distance`'s eps = 1e-6 is kept."""
+    returned as L_all + L_hard; `pairwise_distance`'s eps = 1e-6 is kept.  With all four tensors on a HIP device, y_hat in fp32 and no
+    gradient wanted into batch_y / batch_negative_samples (the trainer feeds precomputed embeddings) it is ONE fused kernel pass
+    (outfitx_amd/csrc/rank_loss.hip: the [B,K,D] difference tensor is never materialised; d loss / d y_hat is saved for backward, which
+    the HIP backward of the CIR path consumes).  Anything else - CPU tensors, other dtypes, a gradient into the positives or the
+    negatives - runs the torch expression below, unchanged."""
 
     def __init__(self, margin: float = 2.0):
         super().__init__()
         self.margin = margin
 
+    @staticmethod
+    def _fused_ok(batch_y, batch_y_hat, batch_negative_samples, batch_negative_mask) -> bool:
+        ts = (batch_y, batch_y_hat, batch_negative_samples, batch_negative_mask)
+        return (all(isinstance(t, torch.Tensor) and t.device.type == "cuda" for t in ts) and batch_y_hat.dtype == torch.float32
+                and batch_y.dtype == torch.float32 and batch_negative_samples.dtype == torch.float32
+                and batch_negative_mask.dtype == torch.bool
+                and not batch_y.requires_grad and not batch_negative_samples.requires_grad
+                and batch_y_hat.dim() == 2 and batch_negative_samples.dim() == 3 and batch_y.shape == batch_y_hat.shape
+                and batch_negative_mask.shape == batch_negative_samples.shape[:2] and batch_negative_samples.shape[0] == batch_y_hat.shape[0]
+                and batch_negative_samples.shape[2] == batch_y_hat.shape[1] and batch_y_hat.shape[0] >= 1
+                and batch_y_hat.shape[1] % 4 == 0 and 4 <= batch_y_hat.shape[1] <= 4096)
+
     def forward(self, batch_y, batch_y_hat, batch_negative_samples, batch_negative_mask):
+        if self._fused_ok(batch_y, batch_y_hat, batch_negative_samples, batch_negative_mask):
+            return _SetRankFn.apply(batch_y_hat, batch_y, batch_negative_samples, batch_negative_mask, float(self.margin))
         d_pos = torch.linalg.vector_norm(batch_y_hat - batch_y + 1e-6, dim=-1)                 # F.pairwise_distance adds eps to the difference
         d_neg = torch.linalg.vector_norm(batch_y_hat[:, None, :] - batch_negative_samples, dim=-1)
         valid = ~batch_negative_mask

@@ -21,6 +21,11 @@ Differences from DDP by design (MI355X / xGMI, point-to-point links, per-link bo
   * no per-step all_gather_object / barrier pair (reference C4/C5): error propagation is the job of the
     launcher (torchrun tears the group down when a rank raises).
 
+`CIRTrainer` is the same loop for the reference's other training job, complementary item retrieval
+(src/trains/trainers/complementary_item_retrieval_trainer.py:66-116): model(CIR batch) -> SetWiseRankingLoss(margin 2; one fused kernel
+pass on HIP tensors) -> / accumulation_steps -> the hand-written CIR backward, then the identical boundary step.  Both trainers share
+`FlatGradTrainer` below (arena, gradient sink, per-layer slices, armed layer events, overlapped reduction, clip, AdamW, OneCycleLR).
+
 The loop itself is device-agnostic torch host code (the CPU tests drive it with a stub module over gloo); the model it is
 meant for, `outfitx_amd.OutfitX` in train() mode, only runs on a HIP device.
 """
@@ -47,6 +52,21 @@ class CPTrainConfig:
     div_factor: float = 25.0
     final_div_factor: float = 1e4
     fused_optimizer: bool = True      # torch.optim.AdamW(fused=True): one multi-tensor kernel per step
+
+
+@dataclass
+class CIRTrainConfig:
+    """Defaults = the reference's ComplementaryItemRetrievalTrainConfig (src/trains/configs/complementary_item_retrieval_train_config.py;
+    its per-GPU batch is 3072 with 10 negatives per query) and the OneCycleLR settings of its trainer."""
+    learning_rate: float = 2e-5
+    accumulation_steps: int = 4
+    n_epochs: int = 300
+    max_grad_norm: float = 1.0
+    margin: float = 2.0
+    pct_start: float = 0.3
+    div_factor: float = 25.0
+    final_div_factor: float = 1e4
+    fused_optimizer: bool = True
 
 
 class FlatGrads:
@@ -150,19 +170,20 @@ def gather_epoch(local_y: torch.Tensor, local_labels: torch.Tensor, local_loss: 
     return {"loss": float(loss), **cp_metrics(ys, ls)}
 
 
-class CPTrainer:
-    """model(task=CP, outfit_embedding=..., outfit_mask=...) -> [B,1] logits; batches are dicts like the reference's
-    collate output: {'input_dict': {'task', 'outfit_embedding', 'outfit_mask'}, 'label'}."""
+class FlatGradTrainer:
+    """What the CP and the CIR loop share: the flat gradient arena, gradient-sink mode of the HIP model, per-layer gradient slices,
+    the overlapped mean over the ranks, and the accumulation-boundary step (clip -> AdamW -> OneCycleLR -> zero).  `cfg` carries
+    learning_rate, accumulation_steps, n_epochs, max_grad_norm, pct_start, div_factor, final_div_factor, fused_optimizer."""
 
-    def __init__(self, model: torch.nn.Module, steps_per_epoch: int, cfg: Optional[CPTrainConfig] = None,
-                 loss_fn: Optional[Callable] = None, params: Optional[Iterable[torch.nn.Parameter]] = None, group=None):
-        self.model, self.cfg, self.group = model, cfg or CPTrainConfig(), group
+    # OutfitX._outfit_tensors() entries that are NOT on the task's path (sink_ready ignores them): CP skips target_item_image_emb, cir_ffn
+    _sink_skip = (1, 4)
+
+    def __init__(self, model: torch.nn.Module, steps_per_epoch: int, cfg, loss_fn: Callable,
+                 params: Optional[Iterable[torch.nn.Parameter]] = None, group=None):
+        self.model, self.cfg, self.group = model, cfg, group
         c = self.cfg
-        ps = list(params) if params is not None else [p for p in model.parameters() if p.requires_grad]
+        ps = list(params) if params is not None else self._default_params(model)
         self.grads = FlatGrads(ps)
-        if loss_fn is None:
-            from .losses import FocalLoss
-            loss_fn = FocalLoss(alpha=c.focal_alpha, gamma=c.focal_gamma, reduction="mean")
         self.loss_fn = loss_fn
         dev = self.grads.flat.device
         fused = c.fused_optimizer and dev.type == "cuda"
@@ -189,6 +210,10 @@ class CPTrainer:
         self._layer_events = None
         self._comm_stream = None
 
+    @staticmethod
+    def _default_params(model: torch.nn.Module) -> List[torch.nn.Parameter]:
+        return [p for p in model.parameters() if p.requires_grad]
+
     def _world(self) -> int:
         return dist.get_world_size(self.group) if dist.is_available() and dist.is_initialized() else 1
 
@@ -199,7 +224,7 @@ class CPTrainer:
             return False
         # the events mean "final in the arena" only on the gradient-sink path; any tensor whose .grad is not the arena view (detached,
         # non-contiguous, not fp32) sends the backward through autograd's accumulation, which runs AFTER the events: plain reduction then
-        if hasattr(self.model, "sink_ready") and not self.model.sink_ready():
+        if hasattr(self.model, "sink_ready") and not self.model.sink_ready(self._sink_skip):
             return False
         if self._layer_events is None:
             self._layer_events = [torch.cuda.Event() for _ in self.layer_slices]
@@ -240,15 +265,10 @@ class CPTrainer:
                 dist.all_reduce(flat[lo:hi], op=dist.ReduceOp.SUM, group=self.group)
         flat.div_(world)
 
-    def micro_step(self, batch: dict, step: int):
-        """One micro-batch: forward, loss / accumulation_steps, backward; optimizer step on the accumulation boundary.
-        Returns (detached loss, detached logits)."""
+    def _backward_and_step(self, loss: torch.Tensor, step: int) -> None:
+        """(loss / accumulation_steps).backward(); on every accumulation_steps-th micro-batch or the epoch's last: mean over the
+        ranks, clip, optimizer and scheduler step, zero (cp_trainer:70-80 = cir_trainer:89-99)."""
         c = self.cfg
-        dev = self.grads.flat.device
-        inp = {k: (v if k == "task" else v.to(dev, non_blocking=True)) for k, v in batch["input_dict"].items()}
-        labels = batch["label"].to(dev, non_blocking=True)
-        y_hat = self.model(**inp).squeeze(dim=-1)
-        loss = self.loss_fn(y_hat=y_hat, y_true=labels)
         boundary = (step + 1) % c.accumulation_steps == 0 or step + 1 == self.steps_per_epoch
         overlapped = boundary and self._arm_overlap()
         (loss / c.accumulation_steps).backward()
@@ -259,6 +279,29 @@ class CPTrainer:
             self.scheduler.step()
             self.grads.zero_()
             getattr(self.model, "mark_weights_changed", lambda: None)()     # fused optimizers do not bump tensor versions
+
+
+class CPTrainer(FlatGradTrainer):
+    """model(task=CP, outfit_embedding=..., outfit_mask=...) -> [B,1] logits; batches are dicts like the reference's
+    collate output: {'input_dict': {'task', 'outfit_embedding', 'outfit_mask'}, 'label'}."""
+
+    def __init__(self, model: torch.nn.Module, steps_per_epoch: int, cfg: Optional[CPTrainConfig] = None,
+                 loss_fn: Optional[Callable] = None, params: Optional[Iterable[torch.nn.Parameter]] = None, group=None):
+        cfg = cfg or CPTrainConfig()
+        if loss_fn is None:
+            from .losses import FocalLoss
+            loss_fn = FocalLoss(alpha=cfg.focal_alpha, gamma=cfg.focal_gamma, reduction="mean")
+        super().__init__(model, steps_per_epoch, cfg, loss_fn, params, group)
+
+    def micro_step(self, batch: dict, step: int):
+        """One micro-batch: forward, loss / accumulation_steps, backward; optimizer step on the accumulation boundary.
+        Returns (detached loss, detached logits)."""
+        dev = self.grads.flat.device
+        inp = {k: (v if k == "task" else v.to(dev, non_blocking=True)) for k, v in batch["input_dict"].items()}
+        labels = batch["label"].to(dev, non_blocking=True)
+        y_hat = self.model(**inp).squeeze(dim=-1)
+        loss = self.loss_fn(y_hat=y_hat, y_true=labels)
+        self._backward_and_step(loss, step)
         return loss.detach(), y_hat.detach(), labels
 
     def train_epoch(self, batches: Iterable[dict]) -> Dict[str, float]:
@@ -271,3 +314,60 @@ class CPTrainer:
             loss, y, lab = self.micro_step(batch, step)
             total += loss; ys.append(y); ls.append(lab); n += 1
         return gather_epoch(torch.cat(ys), torch.cat(ls), total, max(n, 1), self.group)
+
+
+class CIRTrainer(FlatGradTrainer):
+    """model(task=CIR, outfit_embedding=..., outfit_mask=..., target_item_text_embedding=...) -> [B, d_embed] target-item embeddings;
+    batches are the reference's collate dicts (complementary_item_retrieval_trainer.py:73-87):
+    {'input_dict': {...CIR task tensors...}, 'pos_item_embedding' [B,D], 'neg_items_embedding' [B,K,D], 'neg_items_mask' [B,K] bool}.
+    Replaces ComplementaryItemRetrievalTrainer.train_epoch (:66-116); negative sampling, the easy -> hard switch, checkpoints and the
+    recall@k validation loop stay with the caller (parallel.cir_topk covers the last)."""
+
+    _sink_skip = (0, 2, 3)        # outfit_token and the CP head are not on the CIR path
+
+    def __init__(self, model: torch.nn.Module, steps_per_epoch: int, cfg: Optional[CIRTrainConfig] = None,
+                 loss_fn: Optional[Callable] = None, params: Optional[Iterable[torch.nn.Parameter]] = None, group=None):
+        cfg = cfg or CIRTrainConfig()
+        if loss_fn is None:
+            from .losses import SetWiseRankingLoss
+            loss_fn = SetWiseRankingLoss(margin=cfg.margin)
+        super().__init__(model, steps_per_epoch, cfg, loss_fn, params, group)
+
+    @staticmethod
+    def _default_params(model: torch.nn.Module) -> List[torch.nn.Parameter]:
+        """Every trainable parameter except OutfitX's outfit_token and CP head: they never receive a CIR gradient, and the reference's
+        AdamW skips parameters whose .grad is None - inside the arena their gradient would be a zero VIEW, and AdamW's weight
+        decay would shrink them on every step."""
+        off = [t for t in (getattr(model, "outfit_token", None),) if isinstance(t, torch.nn.Parameter)]
+        head = getattr(model, "cp_ffn", None)
+        if isinstance(head, torch.nn.Module):
+            off += list(head.parameters())
+        off_ids = {id(t) for t in off}
+        return [p for p in model.parameters() if p.requires_grad and id(p) not in off_ids]
+
+    def micro_step(self, batch: dict, step: int):
+        """One micro-batch (:73-99): forward, loss / accumulation_steps, backward; optimizer step on the accumulation boundary.
+        Returns (detached loss, detached y_hat)."""
+        dev = self.grads.flat.device
+        inp = {k: (v if k == "task" else v.to(dev, non_blocking=True)) for k, v in batch["input_dict"].items()}
+        y_hat = self.model(**inp)
+        loss = self.loss_fn(batch_y=batch["pos_item_embedding"].to(dev, non_blocking=True), batch_y_hat=y_hat,
+                            batch_negative_samples=batch["neg_items_embedding"].to(dev, non_blocking=True),
+                            batch_negative_mask=batch["neg_items_mask"].to(dev, non_blocking=True))
+        self._backward_and_step(loss, step)
+        return loss.detach(), y_hat.detach()
+
+    def train_epoch(self, batches: Iterable[dict]) -> Dict[str, float]:
+        """-> {'loss': summed micro-batch loss / number of batches (:100, :114), averaged over the ranks}."""
+        self.model.train()
+        self.grads.zero_()
+        total = torch.zeros((), dtype=torch.float32, device=self.grads.flat.device)
+        n = 0
+        for step, batch in enumerate(batches):
+            total += self.micro_step(batch, step)[0]
+            n += 1
+        total = total / max(n, 1)
+        if self._world() > 1:
+            dist.all_reduce(total, op=dist.ReduceOp.SUM, group=self.group)
+            total = total / self._world()
+        return {"loss": float(total)}

@@ -10,6 +10,13 @@ ms_step is the reference-shaped step (torch clip_grad_norm_ + default AdamW on p
 outfitx_amd.trainer.CPTrainer step (flat gradient arena, one all-reduce, fused AdamW), accumulation 1 = an optimizer step
 and an all-reduce on EVERY micro-batch (the worst case; the reference default accumulates 4).
 
+--task cir: the reference's other training job (complementary_item_retrieval_trainer.py:66-116, K = 10 negatives per query): the
+outfitx_amd.trainer.CIRTrainer step at per-GPU batch 256 and 3072 (the reference config's batch), and SetWiseRankingLoss forward +
+backward ALONE in the fused form (ofx_set_rank_loss) and in the eager torch form, alternating, medians over --loss-reps device-event
+timings.  `loss_kernel_GBps` is (B K D 4 + 3 B D 4) bytes - neg read once, y / y_hat read, dy_hat written - over the two-launch call.
+
+    python tools/bench_train.py --task cir [--cir-batches 256,3072] [--negatives 10] [--loss-reps 30]
+
 --eager also times the same step written with plain torch modules (nn.TransformerEncoder under bf16 autocast, what the
 reference's trainer executes) on the same GPU, for a like-for-like ratio.  Prints one JSON line.
 """
@@ -37,8 +44,88 @@ def timed(fn, steps, warmup):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
+def median_ms(fns, reps, warmup):
+    """Device-event time of each callable, the callables ALTERNATING inside every repetition -> list of medians (ms)."""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    ts = [[] for _ in fns]
+    for _ in range(reps):
+        for i, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); fn(); b.record()
+            b.synchronize()
+            ts[i].append(a.elapsed_time(b))
+    return [float(np.median(t)) for t in ts]
+
+
+def eager_set_rank_loss(batch_y, batch_y_hat, batch_negative_samples, batch_negative_mask, margin=2.0):
+    """The torch expression of outfitx_amd.losses.SetWiseRankingLoss (its CPU / fallback path), whatever the tensors' device."""
+    d_pos = torch.linalg.vector_norm(batch_y_hat - batch_y + 1e-6, dim=-1)
+    d_neg = torch.linalg.vector_norm(batch_y_hat[:, None, :] - batch_negative_samples, dim=-1)
+    valid = ~batch_negative_mask
+    n_valid = valid.sum().clamp(min=1)
+    hinge_all = torch.relu(d_pos[:, None] - d_neg + margin) * valid
+    hardest = d_neg.masked_fill(batch_negative_mask, float("inf")).amin(dim=1)
+    return hinge_all.sum() / n_valid + torch.relu(d_pos - hardest + margin).mean()
+
+
+def cir_main(a, m, params):
+    from outfitx_amd.engine import set_rank_loss
+    from outfitx_amd.trainer import CIRTrainConfig, CIRTrainer
+    from src.losses import SetWiseRankingLoss
+    from src.models.datatypes import OutfitComplementaryItemRetrievalTask as CIR
+    K, D = a.negatives, 1024
+    off = {id(m.outfit_token)} | {id(p) for p in m.cp_ffn.parameters()}
+    params = [p for p in params if id(p) not in off]
+    res = {"workload": f"CIR trainer step, outfits x {a.items} items (padded {a.pad}), {K} negatives per query, precomputed embeddings",
+           "precision": a.precision, "loss_reps": a.loss_reps}
+    for B in [int(v) for v in a.cir_batches.split(",")]:
+        emb, mask = synth.outfit_batch(99, B, a.pad, a.items)
+        batch = {"input_dict": {"task": CIR, "outfit_embedding": torch.from_numpy(emb).cuda(), "outfit_mask": torch.from_numpy(mask).cuda(),
+                                "target_item_text_embedding": torch.from_numpy(synth.unit_rows(99, "target_text", B, 512)).cuda()},
+                 "pos_item_embedding": torch.from_numpy(synth.item_embeddings(99, "pos", B) * 3.0).cuda(),
+                 "neg_items_embedding": torch.from_numpy(synth.item_embeddings(99, "neg", B * K).reshape(B, K, D) * 3.0).cuda(),
+                 "neg_items_mask": torch.from_numpy(np.random.default_rng(99).random((B, K)) < 0.1).cuda()}
+        for acc in (1, 4):
+            tr = CIRTrainer(m, steps_per_epoch=10 ** 9, cfg=CIRTrainConfig(accumulation_steps=acc), params=params)
+            k = [0]
+            def dp_step():
+                tr.micro_step(batch, k[0]); k[0] += 1
+            res[f"ms_step_dp_b{B}" if acc == 1 else f"ms_step_dp_accum4_b{B}"] = timed(dp_step, a.steps if acc == 1 else 4 * max(a.steps // 4, 1), a.warmup if acc == 1 else 4)
+            del tr
+        # the loss alone, forward + backward
+        y_hat0 = torch.from_numpy(synth.item_embeddings(99, "y_hat", B) * 3.0).cuda()
+        y, neg, nm = batch["pos_item_embedding"], batch["neg_items_embedding"], batch["neg_items_mask"]
+        fused = SetWiseRankingLoss(margin=2.0)
+
+        def loss_fused():
+            yh = y_hat0.detach().requires_grad_(True)
+            fused(batch_y=y, batch_y_hat=yh, batch_negative_samples=neg, batch_negative_mask=nm).backward()
+            return yh.grad
+
+        def loss_eager():
+            yh = y_hat0.detach().requires_grad_(True)
+            eager_set_rank_loss(y, yh, neg, nm).backward()
+            return yh.grad
+
+        ga, gb = loss_fused(), loss_eager()
+        res[f"loss_grad_fused_vs_eager_b{B}"] = float((ga - gb).abs().max() / gb.abs().max())
+        t_f, t_e, t_k = median_ms([loss_fused, loss_eager, lambda: set_rank_loss(y, y_hat0, neg, nm, 2.0)], a.loss_reps, 5)
+        nbytes = B * K * D * 4 + 3 * B * D * 4
+        res[f"ms_loss_fwd_bwd_fused_b{B}"], res[f"ms_loss_fwd_bwd_eager_b{B}"], res[f"ms_loss_kernel_call_b{B}"] = t_f, t_e, t_k
+        res[f"loss_eager_over_fused_b{B}"] = t_e / t_f
+        res[f"loss_kernel_GBps_b{B}"] = nbytes / (t_k * 1e-3) / 1e9
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--task", choices=["cp", "cir"], default="cp")
+    ap.add_argument("--cir-batches", default="256,3072")
+    ap.add_argument("--negatives", type=int, default=10)
+    ap.add_argument("--loss-reps", type=int, default=30)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--items", type=int, default=8)
     ap.add_argument("--pad", type=int, default=16)
@@ -60,6 +147,8 @@ def main():
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     m = m.cuda().train()
     params = [v for k, v in m.named_parameters() if not k.startswith("item_encoder.")]
+    if a.task == "cir":
+        return cir_main(a, m, params)
     opt = torch.optim.AdamW(params, lr=2e-5)
     n_items = synth.ragged_lengths(99, a.batch, 2, 8) if a.polyvore else a.items
     emb, mask = synth.outfit_batch(99, a.batch, a.pad, n_items)
