@@ -142,14 +142,21 @@ int ofx_clip_text_fwd(ofx_handle* h, const int64_t* ids, const int64_t* attn_mas
                       size_t ws_bytes, ofx_stream stream);
 
 /* Row H: torch.cdist(y[B,1,D], cand[B,C,D]).squeeze(1).argmin(-1) (fill_in_the_blank_trainer.py:50-56).
- * idx int64 [B]; dist fp32 [B,C] optional.                                                      */
+ * idx int64 [B] = the first minimum; dist fp32 [B,C] optional.  D a multiple of 4 (else OFX_EINVAL); rows are read as 16-byte vectors.
+ * Non-finite inputs follow torch: a NaN distance wins over every number and the first NaN is returned; +inf is an ordinary (largest) value. */
 int ofx_fitb_argmin(const float* y_hat, const float* cand, int B, int C, int D, int64_t* idx, float* dist,
                     ofx_stream stream);
 /* Row I: torch.cdist(Q,P) -> topk(k, largest=False) (complementary_item_retrieval_trainer.py:240-249).
- * fp32-exact distances; ascending; ties -> smaller pool index.  idx int64 [nq,k] = row + index_base.  */
+ * fp32-exact distances; ascending; ties -> smaller pool index.  idx int64 [nq,k] = row + index_base.
+ * Preconditions, checked: D a multiple of 32 and 1 <= k <= min(128, np) (else OFX_ESHAPE), Q and P 16-byte aligned and no NULL argument
+ * (OFX_EINVAL), ws_bytes >= ofx_workspace_bytes(OFX_OP_TOPK, nq, np) (OFX_EWORKSPACE); a rejected call launches nothing.
+ * Non-finite inputs: a pool row that holds a NaN or an infinity has a non-finite distance (NaN or +inf) to every query and sorts behind every
+ * finite distance, as in torch.topk(largest=False): it is returned only when fewer than k rows are finite; the finite rows are selected and
+ * ordered as if it were absent.  A query that holds one gets k distinct in-range rows with non-finite distances, nothing more. */
 int ofx_l2_topk(ofx_handle* h, const float* Q, const float* P, int nq, int np, int D, int k, int64_t index_base,
                 int64_t* idx, float* dist, void* ws, size_t ws_bytes, ofx_stream stream);
-/* Merge `parts` candidate lists (after the RCCL all-gather of per-shard top-k): in [parts,nq,k]. */
+/* Merge `parts` candidate lists (after the RCCL all-gather of per-shard top-k): in [parts,nq,k], each list ascending, rows unique across lists.
+ * parts * k <= 1024 (else OFX_ESHAPE).  Ordered by (distance bits, global index): NaN distances sort last here as well. */
 int ofx_topk_merge(const int64_t* idx_in, const float* dist_in, int parts, int nq, int k, int64_t* idx, float* dist,
                    ofx_stream stream);
 

@@ -250,7 +250,9 @@ def fitb_argmin(y_hat, candidates):
 def l2_topk(Q, P, k=50, chunk=256):
     """complementary_item_retrieval_trainer.py:240-249: cdist(Q,P) (‖q‖²+‖p‖²−2q·p form, fp32,
     clamped at 0, sqrt) → topk(k, largest=False): ascending, ties → smaller index first here.
-    Returns (idx [nq,k] int64, dist [nq,k] float32)."""
+    Returns (idx [nq,k] int64, dist [nq,k] float32).  The order among candidates whose fp32 distances
+    round together depends on this function's own summation order; for comparisons that are exact on
+    ties use l2_topk_exact on lattice() inputs."""
     Q = Q.astype(np.float32); P = P.astype(np.float32)
     pn = (P * P).sum(-1)
     idx = np.empty((Q.shape[0], k), np.int64); dist = np.empty((Q.shape[0], k), np.float32)
@@ -268,6 +270,71 @@ def l2_dist_exact(Q, P):
     """float64 direct-form distances, for tie analysis in tests."""
     Q = Q.astype(np.float64); P = P.astype(np.float64)
     return np.sqrt(np.maximum((Q * Q).sum(-1)[:, None] + (P * P).sum(-1)[None] - 2 * Q @ P.T, 0))
+
+
+def lattice(seed, rows, D, lo, hi):
+    """float32 [rows, D] with integer coordinates drawn uniformly from [lo, hi].
+
+    With 2 D max(lo², hi²) < 2^24 every product, row norm and partial sum of ‖q‖² + ‖p‖² − 2 q·p is an
+    integer below 2^24, hence exact in fp32 in ANY summation order: a kernel's fp32 d² then equals
+    the float64 d² bit for bit, and selection and order are defined on every position (no near-ties).
+    With d² < 2^18 neighbouring integers are ≥ 4 fp32 ulps apart after the square root, so a last-bit
+    difference in sqrtf cannot reorder anything.  Both bounds are asserted on what is returned: the
+    first on the coordinate range, the second as 4 max‖row‖² (≥ any d² between two rows that respect
+    it, also rows of different lattice() calls)."""
+    x = np.random.default_rng(seed).integers(lo, hi + 1, size=(rows, D)).astype(np.float32)
+    assert 2 * D * max(lo * lo, hi * hi) < 2 ** 24, (D, lo, hi)
+    assert 4 * float((x.astype(np.float64) ** 2).sum(-1).max(initial=0.0)) < 2 ** 18, (D, lo, hi)
+    return x
+
+
+def d2_exact(Q, P):
+    """float64 [nq, np] squared distances, direct form sum((q − p)²).  Integer-valued inputs whose
+    norms stay below 2^50 take the ‖q‖² + ‖p‖² − 2 q·p form instead: every term is then an exact
+    float64 integer, so it is the same number, at the cost of one matrix product."""
+    Q = np.asarray(Q, np.float64); P = np.asarray(P, np.float64)
+    assert np.isfinite(Q).all() and np.isfinite(P).all(), "finite inputs only"
+    qn, pn = (Q * Q).sum(-1), (P * P).sum(-1)
+    if (Q == np.rint(Q)).all() and (P == np.rint(P)).all() and max(qn.max(initial=0), pn.max(initial=0)) < 2.0 ** 50:
+        return qn[:, None] + pn[None, :] - 2.0 * (Q @ P.T)
+    out = np.empty((Q.shape[0], P.shape[0]), np.float64)
+    for i in range(Q.shape[0]):
+        for s in range(0, P.shape[0], 8192):
+            d = Q[i] - P[s:s + 8192]
+            out[i, s:s + 8192] = (d * d).sum(-1)
+    return out
+
+
+def l2_topk_exact(Q, P, k, index_base=0):
+    """The k nearest pool rows of every query by EXACT squared distance (float64, direct form; finite
+    inputs only), ascending, ties → smaller pool index (a stable sort).
+    Returns (idx int64 [nq, k] = row + index_base, d2 float64 [nq, k])."""
+    nq, npool = len(Q), len(P)
+    assert 1 <= k <= npool
+    idx = np.empty((nq, k), np.int64); d2k = np.empty((nq, k), np.float64)
+    for s in range(0, nq, 64):
+        d2 = d2_exact(Q[s:s + 64], P)
+        kth = np.partition(d2, k - 1, axis=1)[:, k - 1]
+        for i in range(d2.shape[0]):
+            c = np.flatnonzero(d2[i] <= kth[i])                     # ascending rows, so the stable sort keeps the smaller row first
+            c = c[np.argsort(d2[i, c], kind="stable")][:k]
+            idx[s + i] = c + index_base
+            d2k[s + i] = d2[i, c]
+    return idx, d2k
+
+
+def fitb_argmin_exact(y, cand):
+    """First minimum over the candidates of the exact float64 d² (direct form).  y [B, D], cand [B, C, D]
+    → (idx int64 [B], d2 float64 [B, C])."""
+    y = np.asarray(y, np.float64); cand = np.asarray(cand, np.float64)
+    assert np.isfinite(y).all() and np.isfinite(cand).all(), "finite inputs only"
+    B, C, D = cand.shape
+    d2 = np.empty((B, C), np.float64)
+    step = max(1, (1 << 22) // (C * D))
+    for s in range(0, B, step):
+        d = y[s:s + step, None, :] - cand[s:s + step]
+        d2[s:s + step] = (d * d).sum(-1)
+    return d2.argmin(-1).astype(np.int64), d2
 
 
 # ------------------------------------------------- next row N1: FocalLoss

@@ -30,7 +30,8 @@ __global__ __launch_bounds__(256) void fitb_kernel(const float* y, const float* 
             }
             const float dd = sqrtf(wave_sum(s));
             if (dist && lane == 0) dist[(size_t)b * C + c] = dd;
-            if (dd < best) { best = dd; arg = c; }          // strict <: first minimum wins (torch argmin)
+            // strict <: first minimum wins; a NaN distance beats every number and the first NaN stays (torch argmin)
+            if (dd < best || (dd != dd && best == best)) { best = dd; arg = c; }
         }
         if (lane == 0) idx[b] = arg;
     }
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const float* x, float* out,
     }
 }
 
-// dist[q, p] = sqrt(max(qn[q] + pn[p] - 2 q.p, 0)) on the fp32 matrix instruction (v_mfma_f32_32x32x2_f32: an exact fmaf chain, so a
+// dist[q, p] = sqrt(max(qn[q] + pn[p] - 2 q.p, 0)) (NaN stays NaN) on the fp32 matrix instruction (v_mfma_f32_32x32x2_f32: an exact fmaf chain, so a
 // (q, p) pair's distance has the same bits whichever tile, shard or launch computes it - what the sharded == unsharded merge relies on).
 //
 // Round 4 rewrite (the round-3 kernel staged each k-step with synchronous loads + 32 scalar LDS stores per thread and read its
@@ -173,9 +174,11 @@ __global__ __launch_bounds__(256, 2) void dist_mfma_kernel(const float* Q, const
                     asm volatile("" : "+v"(q));          // opaque: the per-query loads below stay inside this element's scope (hoisting all 32 queries' norms and thresholds above the element loops spilled)
                     if (q < nq && p < np) {
                         const float d2 = qn[q] + pnv - 2.0f * acc[i][j][e];
-                        const float d = d2 > 0.f ? sqrtf(d2) : 0.f;                 // never -0: bit order == value order
+                        // never -0: bit order == value order.  A NaN d2 (a non-finite coordinate in either row) fails `<= 0` and stays NaN:
+                        // its bits sort behind +inf in the select and the sorts below, where torch.topk(largest=False) puts it
+                        const float d = !(d2 <= 0.f) ? sqrtf(d2) : 0.f;
                         if (!FILTER) dist[(size_t)q * ld + (p - p_begin)] = d;
-                        else if (d <= tau[(size_t)q * tau_ld]) {
+                        else if (!(d > tau[(size_t)q * tau_ld])) {       // a NaN tau (fewer than k numbers among the sample's distances) passes every row: the list overflows and the fallback recomputes the query
                             const int pos = atomicAdd(&cnt[q], 1);
                             if (pos < cap) cand[(size_t)q * cap + pos] = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)p;
                         }
@@ -223,7 +226,7 @@ __device__ __forceinline__ void bitonic_sort(unsigned long long* keys, int n /*p
     __syncthreads();
 }
 
-// one block per query row: exact k smallest of row[0..np) (non-negative floats), ties -> smaller index
+// one block per query row: exact k smallest of row[0..np) (non-negative floats, or NaN: ordered by bit pattern, i.e. last), ties -> smaller index
 __global__ __launch_bounds__(256) void topk_select_kernel(const float* dist, int ld, int np, int k, int64_t index_base,
                                                          int64_t* idx_out, float* dist_out, const int* only_flagged = nullptr) {
     if (only_flagged && !only_flagged[blockIdx.x]) return;          // fallback launch: only the flagged queries
