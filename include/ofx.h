@@ -346,7 +346,6 @@ int ofx_attention(const void* qkv, void* out, const int64_t* key_mask, int nseq,
                   int ldo, int k_off, int v_off, int mask_ld, int causal, float scale, int op_dtype, ofx_stream stream);
 int ofx_set_attention(const float* qkv, void* out, const int* cu_seqlens, int nseq, int n_head, int D, int ldo,
                       int out_kind, int max_len, int only_row0, float scale, int op_dtype, ofx_stream stream);
-/* fp32 [rows, cols] -> operand type; mode 0 plain, 1 [hi|lo|hi] (activation split), 2 [hi|hi|lo] (weight split) */
 /* Fused QKV projection + scaled-dot-product attention of a CLIP ViT layer (HF CLIPAttention's q/k/v_proj + softmax(q k^T * scale) v,
  * reached from clip_image_encoder.py:74-76), q | k | v staged in LDS only: X [nseq * seq_len, ldx] operand type, Wqkv [3 width, width]
  * (q | k | v rows), bias [3 width]; optional LayerNorm-fold consumer inputs row_stat [rows, 2] (mean, rstd) + col_sum [3 width];
@@ -361,6 +360,7 @@ int ofx_fused_qkv_attention_w2(const void* X, const void* Wqkv2, const float* bi
  * (q | k | v), HF's causal AND key-padding mask (key_mask [nseq, mask_ld] int64, 0 = ignored, may be NULL); out as ofx_set_attention. */
 int ofx_attention_f32(const float* qkv, void* out, const int64_t* key_mask, int nseq, int seq_len, int n_head, int D, int ldo, int out_kind,
                       int mask_ld, int causal, float scale, int op_dtype, ofx_stream stream);
+/* fp32 [rows, cols] -> operand type; mode 0 plain, 1 [hi|lo|hi] (activation split), 2 [hi|hi|lo] (weight split) */
 int ofx_convert(const float* src, void* dst, int rows, int cols, int mode, int op_dtype, ofx_stream stream);
 
 #ifdef __cplusplus

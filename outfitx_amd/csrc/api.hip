@@ -49,6 +49,11 @@ int g_prof_next_tag[5] = {0, 0, 0, 0, 0};
 double g_prof_next_bytes = 0.0;
 size_t g_prof_used = 0;
 bool g_prof_over = false;
+void fill_record(ProfRec& r, int cat, double flops) {        // takes the pending label (ofx_prof_set_tag), which is then cleared
+    r.cat = cat; r.flops = flops;
+    for (int i = 0; i < 5; ++i) { r.tag[i] = g_prof_next_tag[i]; g_prof_next_tag[i] = 0; }
+    r.bytes = g_prof_next_bytes; g_prof_next_bytes = 0.0;
+}
 }
 void ofx_prof_begin(int cat, hipStream_t s, double flops) {
     if (g_prof_used == g_prof.size()) {              // pool exhausted: stop recording rather than stall the launch path
@@ -57,9 +62,7 @@ void ofx_prof_begin(int cat, hipStream_t s, double flops) {
     }
     g_prof_over = false;
     ProfRec& r = g_prof[g_prof_used];
-    r.cat = cat; r.flops = flops;
-    for (int i = 0; i < 5; ++i) { r.tag[i] = g_prof_next_tag[i]; g_prof_next_tag[i] = 0; }
-    r.bytes = g_prof_next_bytes; g_prof_next_bytes = 0.0;
+    fill_record(r, cat, flops);
     (void)hipEventRecord(r.a, s);
 }
 void ofx_prof_set_tag(int M, int N, int K, int kind, int kmul, double bytes) { g_prof_next_tag[0] = M; g_prof_next_tag[1] = N; g_prof_next_tag[2] = K; g_prof_next_tag[3] = kind; g_prof_next_tag[4] = kmul; g_prof_next_bytes = bytes; }
@@ -70,9 +73,7 @@ hipEvent_t g_ofx_launch_e0 = nullptr, g_ofx_launch_e1 = nullptr;
 bool ofx_prof_ext_begin(int cat, double flops) {
     if (g_prof_used == g_prof.size()) return false;
     ProfRec& r = g_prof[g_prof_used];
-    r.cat = cat; r.flops = flops;
-    for (int i = 0; i < 5; ++i) { r.tag[i] = g_prof_next_tag[i]; g_prof_next_tag[i] = 0; }
-    r.bytes = g_prof_next_bytes; g_prof_next_bytes = 0.0;
+    fill_record(r, cat, flops);
     g_ofx_launch_e0 = r.a; g_ofx_launch_e1 = r.b;
     return true;
 }
@@ -184,10 +185,12 @@ static void use_split(GemmArgs& g, const void* w2, int K, const F8Pair& f8) {
 // One tower GEMM as its launch reads it: the weight rows in ONE form - plain [N, K], split [N, hi(K) | lo(K)] (GemmArgs::a_wrap; with
 // the fp8 companion of the lo halves, a null pair where the shape / type has none) or three-product [N, hi | hi | lo] -, the bias, and
 // for a LayerNorm-folded weight (W . gamma rounded) the column sums of the rounded rows, its bias being bias + W beta (null: not folded)
-struct ClipGemm { void* w = nullptr; float* bias = nullptr; float* col_sum = nullptr; bool split = false; F8Pair f8; };
+struct ClipGemm { void* w = nullptr; float* bias = nullptr; float* col_sum = nullptr; int mode = 0; F8Pair f8; };   // mode: 0 plain, 3 split, 2 three-product (ofx_launch_pack_rows)
+// K = the logical depth; the A rows are [M, K], or [hi | lo | hi] rows of 3 K elements for a three-product weight
 static void use_gemm(GemmArgs& g, const ClipGemm& c, int K) {
-    g.W = c.w; g.K = K; g.bias = c.bias; g.col_sum = c.col_sum;
-    if (c.split) use_split(g, c.w, K, c.f8);
+    g.W = c.w; g.K = K; g.lda = K; g.bias = c.bias; g.col_sum = c.col_sum;
+    if (c.mode == 3) use_split(g, c.w, K, c.f8);
+    if (c.mode == 2) { g.K = 3 * K; g.k_mult = 3; g.lda = 3 * K; }
 }
 struct ClipLayer { ClipGemm qkv, o, fc1, fc2; float *g1, *be1, *g2, *be2; };
 
@@ -214,6 +217,16 @@ struct ofx_handle {
     std::vector<ClipLayer> tl;
     float *t_tok, *t_pos, *t_fin_g, *t_fin_b; void* t_proj_w;
 };
+// One outfit-transformer GEMM against a weight of ofx_pack_outfit_weights, as the handle's precision packed it: plain [N, K], [hi | lo]
+// against one copy of the activations (f16w2: GemmArgs::a_wrap) or three-product [hi | hi | lo] against [hi | lo | hi] rows of 3 K
+// elements (bf16x3).  K = the logical depth; slab = the workspace's split-K scratch (null: the plan never splits).
+static GemmArgs outfit_gemm(const ofx_handle* h, const void* W, int K, void* slab, size_t slab_bytes) {
+    GemmArgs g{};
+    g.W = W; g.K = h->ot_kmul * K; g.k_mult = h->ot_kmul; g.lda = h->ot_kmul * K;
+    if (h->ot_w2) { g.K = 2 * K; g.a_wrap = K; }
+    g.slab = slab; g.slab_bytes = slab_bytes;
+    return g;
+}
 
 extern "C" void ofx_default_desc(ofx_model_desc* d) {
     memset(d, 0, sizeof(*d));
@@ -372,21 +385,21 @@ static int pack_clip_gemm(Arena& A, ClipGemm& c, const void* const* q, std::init
     const size_t N = Nb * blocks.size(), km = mode == 2 ? 3 : (mode == 3 ? 2 : 1);
     c = ClipGemm{};
     char* w = A.take<char>(2 * km * N * K);
-    c.w = w; c.split = mode == 3; c.bias = A.take<float>(N);
+    c.w = w; c.mode = mode; c.bias = A.take<float>(N);
     if (ln >= 0) c.col_sum = A.take<float>(N);
     size_t r = 0;
     for (int i : blocks) {
         const float* src = (const float*)q[i];
         if (ln >= 0)
             TRY(ofx_launch_fold_pack(src, (const float*)q[ln], (const float*)q[ln + 1], (const float*)q[i + 1], w + 2 * km * r * K, c.col_sum + r, c.bias + r,
-                                     (int)Nb, (int)K, dt, s, c.split));
+                                     (int)Nb, (int)K, dt, s, mode == 3));
         else {
             TRY(ofx_launch_pack_rows(src, w + 2 * km * r * K, (int)Nb, (int)Nb, (int)K, (int)K, (int)K, mode, dt, s));
             TRY(copy_f32(c.bias + r, q[i + 1], Nb, s));
         }
         r += Nb;
     }
-    if (c.split) TRY(pack_f8(A, w, N, K, dt, s, c.f8));       // one [N, K] matrix: q | k | v row blocks
+    if (mode == 3) TRY(pack_f8(A, w, N, K, dt, s, c.f8));       // one [N, K] matrix: q | k | v row blocks
     return OFX_OK;
 }
 
@@ -573,6 +586,11 @@ struct SetInput {
     const float* x = nullptr; const uint8_t* pad_mask = nullptr;                                   // dense
     const float* table = nullptr; int ld = 0; long long n_table = 0; const int* item_index = nullptr; const int* cu_items = nullptr;   // indexed
 };
+static SetInput dense_set(const float* x, const uint8_t* pad_mask) { SetInput in; in.x = x; in.pad_mask = pad_mask; return in; }
+static SetInput indexed_set(const float* table, int ld, long long n_table, const int* item_index, const int* cu_items) {
+    SetInput in; in.table = table; in.ld = ld; in.n_table = n_table; in.item_index = item_index; in.cu_items = cu_items;
+    return in;
+}
 static int build_set(const ofx_handle* h, const SetInput& in, const float* prefix, int prefix_stride, int* cu, float* X, int B, int L, hipStream_t s) {
     const int D = h->d.d_model;
     if (in.table) return ofx_launch_set_build_indexed(in.table, in.ld, in.n_table, in.item_index, in.cu_items, prefix, prefix_stride, cu, X, B, D, s);
@@ -587,8 +605,7 @@ extern "C" int ofx_set_encoder_fwd(ofx_handle* h, const float* x, const uint8_t*
     OFX_REQUIRE(h && h->out_ready, OFX_ESTATE, "set_encoder_fwd: outfit weights not packed");
     OFX_REQUIRE(B > 0 && L >= 0 && L <= 63, OFX_ESHAPE, "set_encoder_fwd: B=%d L=%d (L must be in [0,63])", B, L);
     OFX_REQUIRE((x || L == 0) && (pad_mask || L == 0) && out_row0 && ws, OFX_EINVAL, "set_encoder_fwd: NULL argument");
-    SetInput in; in.x = x; in.pad_mask = pad_mask;
-    return set_encoder_core(h, in, prefix, prefix_stride, B, L, out_row0, ws, ws_bytes, (hipStream_t)stream);
+    return set_encoder_core(h, dense_set(x, pad_mask), prefix, prefix_stride, B, L, out_row0, ws, ws_bytes, (hipStream_t)stream);
 }
 extern "C" int ofx_set_encoder_fwd_indexed(ofx_handle* h, const float* table, int ld, long long n_table, const int* item_index, const int* cu_items,
                                            const float* prefix, int prefix_stride, int B, int max_len, float* out_row0, void* ws, size_t ws_bytes,
@@ -596,8 +613,7 @@ extern "C" int ofx_set_encoder_fwd_indexed(ofx_handle* h, const float* table, in
     OFX_REQUIRE(h && h->out_ready, OFX_ESTATE, "set_encoder_fwd_indexed: outfit weights not packed");
     OFX_REQUIRE(B > 0 && max_len >= 0 && max_len <= 63, OFX_ESHAPE, "set_encoder_fwd_indexed: B=%d max_len=%d (must be in [0,63])", B, max_len);
     OFX_REQUIRE(table && item_index && cu_items && out_row0 && ws && n_table > 0, OFX_EINVAL, "set_encoder_fwd_indexed: NULL argument");
-    SetInput in; in.table = table; in.ld = ld; in.n_table = n_table; in.item_index = item_index; in.cu_items = cu_items;
-    return set_encoder_core(h, in, prefix, prefix_stride, B, max_len, out_row0, ws, ws_bytes, (hipStream_t)stream);
+    return set_encoder_core(h, indexed_set(table, ld, n_table, item_index, cu_items), prefix, prefix_stride, B, max_len, out_row0, ws, ws_bytes, (hipStream_t)stream);
 }
 static int set_encoder_core(ofx_handle* h, const SetInput& in, const float* prefix, int prefix_stride, int B, int L, float* out_row0, void* ws,
                             size_t ws_bytes, hipStream_t s) {
@@ -623,14 +639,12 @@ static int set_encoder_core(ofx_handle* h, const SetInput& in, const float* pref
             TRY(ofx_launch_layernorm_dev(ln, m_dev, dt, s));
         }
         ln1_done = false;
-        GemmArgs g1{}; g1.A = w.H; g1.W = Ly.w_in; g1.C = w.QKV; g1.bias = Ly.b_in; g1.resid = nullptr; g1.m_dev = m_dev;
-        g1.M = M; g1.N = 3 * D; g1.K = km * D; g1.k_mult = km; g1.lda = km * D; g1.ldc = 3 * D; g1.ldr = 0; g1.act = OFX_ACT_NONE;
+        GemmArgs g1 = outfit_gemm(h, Ly.w_in, D, w.slab, w.slab_bytes);
+        g1.A = w.H; g1.C = w.QKV; g1.bias = Ly.b_in; g1.m_dev = m_dev; g1.M = M; g1.N = 3 * D; g1.ldc = 3 * D;
         // single-product precisions: q|k|v stay in the operand type and the varlen MFMA attention runs (as in the training forward);
         // bf16x3 keeps fp32 q|k|v and the fp32 set attention (1e-5 parity)
-        if (h->ot_w2) { g1.K = 2 * D; g1.a_wrap = D; }          // split weights: A . (hi + lo)^T on one copy of the activations
         const bool mfma_attn = km == 1 && !h->ot_w2 && g_train_mfma_attn;       // f16w2 keeps fp32 q | k | v and the fp32 set attention, as bf16x3 does
         g1.out_kind = mfma_attn ? OFX_OUT_OP : OFX_OUT_F32;
-        g1.slab = w.slab; g1.slab_bytes = w.slab_bytes;
         int qkv_splits = 1;
         if (fuse_att && !mfma_attn) g1.defer_splits = &qkv_splits;
         TRY(ofx_launch_gemm(g1, dt, s));
@@ -649,10 +663,8 @@ static int set_encoder_core(ofx_handle* h, const SetInput& in, const float* pref
             TRY(ofx_launch_gather_rows(w.X, w.cu, out_row0, B, D * 4, D * 4, s));
             X = out_row0; H = w.HP; U = w.UP; Ml = B; md = nullptr;
         }
-        GemmArgs g2{}; g2.A = H; g2.W = Ly.w_out; g2.C = X; g2.bias = Ly.b_out; g2.resid = X; g2.m_dev = md;
-        g2.M = Ml; g2.N = D; g2.K = km * D; g2.k_mult = km; g2.lda = km * D; g2.ldc = D; g2.ldr = D; g2.act = OFX_ACT_NONE; g2.out_kind = OFX_OUT_F32;
-        g2.slab = w.slab; g2.slab_bytes = w.slab_bytes;
-        if (h->ot_w2) { g2.K = 2 * D; g2.a_wrap = D; }
+        GemmArgs g2 = outfit_gemm(h, Ly.w_out, D, w.slab, w.slab_bytes);
+        g2.A = H; g2.C = X; g2.bias = Ly.b_out; g2.resid = X; g2.m_dev = md; g2.M = Ml; g2.N = D; g2.ldc = D; g2.ldr = D; g2.out_kind = OFX_OUT_F32;
         bool ln2_done = false;
         if (fuse) { g2.ln_gamma = Ly.g2; g2.ln_beta = Ly.be2; g2.ln_out = H; g2.ln_ld = km * D; g2.ln_kind = okind; g2.ln_eps = d.ln_eps; g2.ln_done = &ln2_done; }
         TRY(ofx_launch_gemm(g2, dt, s));
@@ -660,15 +672,11 @@ static int set_encoder_core(ofx_handle* h, const SetInput& in, const float* pref
             LnArgs ln2{X, nullptr, Ly.g2, Ly.be2, H, Ml, D, km * D, okind, d.ln_eps};
             TRY(ofx_launch_layernorm_dev(ln2, md, dt, s));
         }
-        GemmArgs g3{}; g3.A = H; g3.W = Ly.w_1; g3.C = U; g3.bias = Ly.b_1; g3.resid = nullptr; g3.m_dev = md;
-        g3.M = Ml; g3.N = Fp; g3.K = km * D; g3.k_mult = km; g3.lda = km * D; g3.ldc = km * Fp; g3.ldr = 0; g3.act = d.outfit_act; g3.out_kind = okind;
-        g3.slab = w.slab; g3.slab_bytes = w.slab_bytes;
-        if (h->ot_w2) { g3.K = 2 * D; g3.a_wrap = D; }
+        GemmArgs g3 = outfit_gemm(h, Ly.w_1, D, w.slab, w.slab_bytes);
+        g3.A = H; g3.C = U; g3.bias = Ly.b_1; g3.m_dev = md; g3.M = Ml; g3.N = Fp; g3.ldc = km * Fp; g3.act = d.outfit_act; g3.out_kind = okind;
         TRY(ofx_launch_gemm(g3, dt, s));
-        GemmArgs g4{}; g4.A = U; g4.W = Ly.w_2; g4.C = X; g4.bias = Ly.b_2; g4.resid = X; g4.m_dev = md;
-        g4.M = Ml; g4.N = D; g4.K = km * Fp; g4.k_mult = km; g4.lda = km * Fp; g4.ldc = D; g4.ldr = D; g4.act = OFX_ACT_NONE; g4.out_kind = OFX_OUT_F32;
-        g4.slab = w.slab; g4.slab_bytes = w.slab_bytes;
-        if (h->ot_w2) { g4.K = 2 * Fp; g4.a_wrap = Fp; }
+        GemmArgs g4 = outfit_gemm(h, Ly.w_2, Fp, w.slab, w.slab_bytes);
+        g4.A = U; g4.C = X; g4.bias = Ly.b_2; g4.resid = X; g4.m_dev = md; g4.M = Ml; g4.N = D; g4.ldc = D; g4.ldr = D; g4.out_kind = OFX_OUT_F32;
         if (fuse && !last) {                            // ... and the next layer's norm1
             const OutfitLayer& Nx = h->ol[l + 1];
             g4.ln_gamma = Nx.g1; g4.ln_beta = Nx.be1; g4.ln_out = w.H; g4.ln_ld = km * D; g4.ln_kind = okind; g4.ln_eps = d.ln_eps; g4.ln_done = &ln1_done;
@@ -691,9 +699,9 @@ extern "C" int ofx_cir_head(ofx_handle* h, const float* row0, int B, float* emb,
     OFX_REQUIRE(ws_bytes >= (size_t)B * km * D * 2, OFX_EWORKSPACE, "cir_head: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     TRY(ofx_launch_pack_rows(row0, ws, B, B, D, D, D, km == 3 ? 1 : 0, h->ot_dtype, s));
-    GemmArgs g{}; g.A = ws; g.W = h->cir_w; g.C = emb; g.bias = nullptr; g.resid = nullptr;
-    g.M = B; g.N = D; g.K = km * D; g.lda = km * D; g.ldc = D; g.ldr = 0; g.act = OFX_ACT_NONE; g.out_kind = OFX_OUT_F32;
-    if (h->ot_w2) { g.K = 2 * D; g.a_wrap = D; }
+    GemmArgs g = outfit_gemm(h, h->cir_w, D, nullptr, 0);
+    g.A = ws; g.C = emb; g.M = B; g.N = D; g.ldc = D; g.out_kind = OFX_OUT_F32;
+    g.k_mult = 1;       // the head has always launched, and been recorded, as a plain GEMM over K = 3 D in bf16x3: from 6,144 rows on k_mult = 3 would select gemm_x3's kernel
     return ofx_launch_gemm(g, h->ot_dtype, s);
 }
 
@@ -724,11 +732,11 @@ static int clip_layer(const ClipLayer& L, const ClipWs& w, int rows, int nseq, i
                       float eps, int causal, const int64_t* key_mask, int mask_ld, int dt, const int* pool_idx, hipStream_t s, bool pool_first) {
     // fused QKV projection + attention (non-pooled ViT layers: one 33..64-token tile per sequence, no mask): q | k | v never reach HBM;
     // split q | k | v weights: its dual-weight variant (ofx_tune(9, 3)), else the dual-weight GEMM + the attention kernel
-    const bool fused = (g_fuse_qkv & (L.qkv.split ? 2 : 1)) && !pool_idx && !causal && !key_mask && S >= 33 && S <= 64 && (256 / S - 1) * S + 64 - 256 <= 16;   // (the kernel's key-row overshoot fits its 16 pad rows)
+    const bool fused = (g_fuse_qkv & (L.qkv.mode == 3 ? 2 : 1)) && !pool_idx && !causal && !key_mask && S >= 33 && S <= 64 && (256 / S - 1) * S + 64 - 256 <= 16;   // (the kernel's key-row overshoot fits its 16 pad rows)
     if (fused) {
-        TRY(ofx_launch_fused_qkv_attn(w.XB, L.qkv.w, L.qkv.bias, w.S, L.qkv.col_sum, w.H, nseq, S, W, heads, W, W, 0.125f, dt, s, L.qkv.split));
+        TRY(ofx_launch_fused_qkv_attn(w.XB, L.qkv.w, L.qkv.bias, w.S, L.qkv.col_sum, w.H, nseq, S, W, heads, W, W, 0.125f, dt, s, L.qkv.mode == 3));
     } else {
-        GemmArgs g1{}; g1.A = w.XB; g1.C = w.QKV; g1.row_stat = w.S; g1.M = rows; g1.N = 3 * W; g1.lda = W;
+        GemmArgs g1{}; g1.A = w.XB; g1.C = w.QKV; g1.row_stat = w.S; g1.M = rows; g1.N = 3 * W;
         g1.ldc = 3 * W; g1.act = OFX_ACT_NONE; g1.out_kind = OFX_OUT_OP;
         use_gemm(g1, L.qkv, W);
         const bool prune = pool_idx && pool_first && g_prune_q;
@@ -761,10 +769,10 @@ static int clip_layer(const ClipLayer& L, const ClipWs& w, int rows, int nseq, i
         if (pool_idx) { g.C = w.XP; g.resid = w.XP; g.out_kind = OFX_OUT_F32; g.slab = w.slab; g.slab_bytes = w.slab_bytes; }
         else { g.C = w.XB; g.xb_out = w.XB; g.xlo = w.XLO; g.stat_part = w.P; g.out_kind = OFX_OUT_OP; }
     };
-    GemmArgs g2{}; g2.A = H; g2.lda = W;
+    GemmArgs g2{}; g2.A = H;
     use_gemm(g2, L.o, W); to_stream(g2);
     TRY(ofx_launch_gemm(g2, dt, s));
-    GemmArgs g3{}; g3.C = U; g3.M = M; g3.N = MLP; g3.lda = W; g3.ldc = MLP; g3.act = act; g3.out_kind = OFX_OUT_OP;
+    GemmArgs g3{}; g3.C = U; g3.M = M; g3.N = MLP; g3.ldc = MLP; g3.act = act; g3.out_kind = OFX_OUT_OP;
     if (pool_idx) {
         LnArgs ln2{w.XP, nullptr, L.g2, L.be2, H, M, W, W, OFX_OUT_OP, eps};
         TRY(ofx_launch_layernorm(ln2, dt, s));
@@ -775,7 +783,7 @@ static int clip_layer(const ClipLayer& L, const ClipWs& w, int rows, int nseq, i
     }
     use_gemm(g3, L.fc1, W);
     TRY(ofx_launch_gemm(g3, dt, s));
-    GemmArgs g4{}; g4.A = U; g4.lda = MLP;
+    GemmArgs g4{}; g4.A = U;
     use_gemm(g4, L.fc2, MLP); to_stream(g4);
     TRY(ofx_launch_gemm(g4, dt, s));
     if (!pool_idx) TRY(ofx_launch_stats_finalize(w.P, W / 64, W, eps, w.S, M, s));
@@ -789,7 +797,8 @@ static int clip_layer_x3(const ClipLayer& L, const ClipWs& w, int rows, int nseq
                          float eps, int causal, const int64_t* key_mask, int mask_ld, int dt, const int* pool_idx, hipStream_t s, bool mfma_attn = false) {
     LnArgs ln{w.X, nullptr, L.g1, L.be1, w.H, rows, W, 3 * W, OFX_OUT_SPLIT3, eps};
     TRY(ofx_launch_layernorm(ln, dt, s));
-    GemmArgs g1{}; g1.A = w.H; g1.W = L.qkv.w; g1.C = w.QKV; g1.bias = L.qkv.bias; g1.M = rows; g1.N = 3 * W; g1.K = 3 * W; g1.k_mult = 3; g1.lda = 3 * W;
+    GemmArgs g1{}; g1.A = w.H; g1.C = w.QKV; g1.M = rows; g1.N = 3 * W;
+    use_gemm(g1, L.qkv, W);
     // q | k | v stay fp32 and the attention runs in fp32 arithmetic (the outfit transformer's set kernel with HF's causal AND
     // key-padding mask, up to 64 rows per sequence): rounding q, k, v, P to the operand type alone leaves 3.5e-4 at the text embedding
     // (tests/studies/operand_scheme_cpu.py); the single-tile MFMA kernel stays as the fallback beyond 64 rows (never reached:
@@ -814,18 +823,18 @@ static int clip_layer_x3(const ClipLayer& L, const ClipWs& w, int rows, int nseq
         TRY(ofx_launch_gather_rows(w.X, pool_idx, w.XP, nseq, W * 4, W * 4, s));
         X = w.XP; H = w.HP; U = w.UP; M = nseq;
     }
-    GemmArgs g2{}; g2.A = H; g2.W = L.o.w; g2.C = X; g2.bias = L.o.bias; g2.resid = X; g2.M = M; g2.N = W; g2.K = 3 * W; g2.k_mult = 3; g2.lda = 3 * W;
-    g2.ldc = W; g2.ldr = W; g2.act = OFX_ACT_NONE; g2.out_kind = OFX_OUT_F32;
+    GemmArgs g2{}; g2.A = H; g2.C = X; g2.resid = X; g2.M = M; g2.N = W; g2.ldc = W; g2.ldr = W; g2.act = OFX_ACT_NONE; g2.out_kind = OFX_OUT_F32;
+    use_gemm(g2, L.o, W);
     if (pool_idx) { g2.slab = w.slab; g2.slab_bytes = w.slab_bytes; }          // the split-K scratch is sized for the pooled rows
     TRY(ofx_launch_gemm(g2, dt, s));
     LnArgs ln2{X, nullptr, L.g2, L.be2, H, M, W, 3 * W, OFX_OUT_SPLIT3, eps};
     TRY(ofx_launch_layernorm(ln2, dt, s));
-    GemmArgs g3{}; g3.A = H; g3.W = L.fc1.w; g3.C = U; g3.bias = L.fc1.bias; g3.M = M; g3.N = MLP; g3.K = 3 * W; g3.k_mult = 3; g3.lda = 3 * W;
-    g3.ldc = 3 * MLP; g3.act = act; g3.out_kind = OFX_OUT_SPLIT3;
+    GemmArgs g3{}; g3.A = H; g3.C = U; g3.M = M; g3.N = MLP; g3.ldc = 3 * MLP; g3.act = act; g3.out_kind = OFX_OUT_SPLIT3;
+    use_gemm(g3, L.fc1, W);
     if (pool_idx) { g3.slab = w.slab; g3.slab_bytes = w.slab_bytes; }
     TRY(ofx_launch_gemm(g3, dt, s));
-    GemmArgs g4{}; g4.A = U; g4.W = L.fc2.w; g4.C = X; g4.bias = L.fc2.bias; g4.resid = X; g4.M = M; g4.N = W; g4.K = 3 * MLP; g4.k_mult = 3;
-    g4.lda = 3 * MLP; g4.ldc = W; g4.ldr = W; g4.act = OFX_ACT_NONE; g4.out_kind = OFX_OUT_F32;
+    GemmArgs g4{}; g4.A = U; g4.C = X; g4.resid = X; g4.M = M; g4.N = W; g4.ldc = W; g4.ldr = W; g4.act = OFX_ACT_NONE; g4.out_kind = OFX_OUT_F32;
+    use_gemm(g4, L.fc2, MLP);
     if (pool_idx) { g4.slab = w.slab; g4.slab_bytes = w.slab_bytes; }
     return ofx_launch_gemm(g4, dt, s);
 }
@@ -963,14 +972,12 @@ extern "C" int ofx_topk_merge(const int64_t* idx_in, const float* dist_in, int p
     return ofx_launch_topk_merge(idx_in, dist_in, parts, nq, k, idx, dist, (hipStream_t)stream);
 }
 
-
-static bool d_outfit_act_is_mish(const ofx_handle* h) { return h->d.outfit_act == OFX_ACT_MISH; }
 // ====================================================================================== training step (N1)
 // Forward with a tape + backward of the CP path on precomputed embeddings.  Single-product operand precisions only
 // (bf16 / f16, like the reference's AMP training); dropout is NOT applied (the caller must use dropout = 0).
 namespace {
 struct TapeLayer { float* Xin; float* st1; char* H1; char* QKV; char* O; float* Xmid; float* st2; char* H2; float* Upre; char* A; };
-struct Tape { int* cu; float* Xfinal; float* row0; float* prefix; char* row0b; char* pO; float* pX; std::vector<TapeLayer> L; size_t bytes; };
+struct Tape { int* cu; float* row0; float* prefix; char* row0b; char* pO; float* pX; std::vector<TapeLayer> L; size_t bytes; };
 size_t carve_tape(const ofx_handle* h, Bump& b, int B, int Lq, Tape* t) {
     const size_t M = (size_t)B * (Lq + 1), D = h->d.d_model, Fp = h->ot_ffn_pad, Mp = align_up(M, 64);   // operand copies: rows readable up to Mp (TN GEMM)
     Tape tp;
@@ -986,7 +993,6 @@ size_t carve_tape(const ofx_handle* h, Bump& b, int B, int Lq, Tape* t) {
         l.O = b.take<char>(Mp * D * 2); l.Xmid = b.take<float>(M * D); l.st2 = b.take<float>(M * 2); l.H2 = b.take<char>(Mp * D * 2);
         l.Upre = b.take<float>(M * Fp); l.A = b.take<char>(Mp * Fp * 2);
     }
-    tp.Xfinal = nullptr;                   // the pruned last layer writes the prefix rows straight into row0
     tp.bytes = align_up(b.off, 256);
     if (t) *t = tp;
     return tp.bytes;
@@ -1047,25 +1053,21 @@ static int cp_train_fwd_core(ofx_handle* h, const SetInput& in, int B, int L, fl
 extern "C" int ofx_cp_train_fwd(ofx_handle* h, const float* x, const uint8_t* pad_mask, int B, int L, float* logits, void* tape_mem,
                                 size_t tape_bytes, void* ws, size_t ws_bytes, float dropout_p, unsigned seed, ofx_stream stream) {
     OFX_REQUIRE(B > 0 && L >= 0 && L <= 31 && (x || L == 0) && (pad_mask || L == 0) && logits && tape_mem, OFX_EINVAL, "cp_train_fwd: bad argument");
-    SetInput in; in.x = x; in.pad_mask = pad_mask;
-    return cp_train_fwd_core(h, in, B, L, logits, tape_mem, tape_bytes, ws, ws_bytes, dropout_p, seed, (hipStream_t)stream);
+    return cp_train_fwd_core(h, dense_set(x, pad_mask), B, L, logits, tape_mem, tape_bytes, ws, ws_bytes, dropout_p, seed, (hipStream_t)stream);
 }
 extern "C" int ofx_cp_train_fwd_indexed(ofx_handle* h, const float* table, int ld, long long n_table, const int* item_index, const int* cu_items,
                                         int B, int max_len, float* logits, void* tape_mem, size_t tape_bytes, void* ws, size_t ws_bytes,
                                         float dropout_p, unsigned seed, ofx_stream stream) {
     OFX_REQUIRE(B > 0 && max_len >= 0 && max_len <= 31 && table && item_index && cu_items && logits && tape_mem && n_table > 0, OFX_EINVAL,
                 "cp_train_fwd_indexed: bad argument");
-    SetInput in; in.table = table; in.ld = ld; in.n_table = n_table; in.item_index = item_index; in.cu_items = cu_items;
-    return cp_train_fwd_core(h, in, B, max_len, logits, tape_mem, tape_bytes, ws, ws_bytes, dropout_p, seed, (hipStream_t)stream);
+    return cp_train_fwd_core(h, indexed_set(table, ld, n_table, item_index, cu_items), B, max_len, logits, tape_mem, tape_bytes, ws, ws_bytes, dropout_p, seed, (hipStream_t)stream);
 }
 extern "C" int ofx_cir_train_fwd(ofx_handle* h, const float* x, const uint8_t* pad_mask, const float* table, int ld, long long n_table,
                                  const int* item_index, const int* cu_items, const float* target_text, int B, int L, float* y, void* tape_mem,
                                  size_t tape_bytes, void* ws, size_t ws_bytes, float dropout_p, unsigned seed, ofx_stream stream) {
     OFX_REQUIRE(B > 0 && L >= 0 && L <= 31 && target_text && y && tape_mem, OFX_EINVAL, "cir_train_fwd: bad argument");
     OFX_REQUIRE((x && pad_mask) || L == 0 || (table && item_index && cu_items && n_table > 0), OFX_EINVAL, "cir_train_fwd: give (x, pad_mask) or (table, item_index, cu_items)");
-    SetInput in;
-    if (table) { in.table = table; in.ld = ld; in.n_table = n_table; in.item_index = item_index; in.cu_items = cu_items; }
-    else { in.x = x; in.pad_mask = pad_mask; }
+    const SetInput in = table ? indexed_set(table, ld, n_table, item_index, cu_items) : dense_set(x, pad_mask);
     return cp_train_fwd_core(h, in, B, L, y, tape_mem, tape_bytes, ws, ws_bytes, dropout_p, seed, (hipStream_t)stream, 1, target_text);
 }
 static int cp_train_fwd_core(ofx_handle* h, const SetInput& in, int B, int L, float* logits, void* tape_mem, size_t tape_bytes, void* ws,
@@ -1093,13 +1095,12 @@ static int cp_train_fwd_core(ofx_handle* h, const SetInput& in, int B, int L, fl
     for (int l = 0; l < d.n_layers; ++l) {
         const OutfitLayer& Ly = h->ol[l];
         TapeLayer& t = T.L[l];
-        float* Xnext = l + 1 < d.n_layers ? T.L[l + 1].Xin : nullptr;          // the last layer never reaches the full-row FFN (pruned below)
+        const bool last = l + 1 == d.n_layers;
         LnArgs ln{t.Xin, nullptr, Ly.g1, Ly.be1, t.H1, M, D, D, OFX_OUT_OP, d.ln_eps}; ln.stats = t.st1;
         TRY(ofx_launch_layernorm_dev(ln, m_dev, dt, s));
-        GemmArgs g1{}; g1.A = t.H1; g1.W = Ly.w_in; g1.C = t.QKV; g1.bias = Ly.b_in; g1.m_dev = m_dev; g1.M = M; g1.N = 3 * D; g1.K = D; g1.lda = D;
-        g1.ldc = 3 * D; g1.out_kind = OFX_OUT_OP; g1.slab = w.slab; g1.slab_bytes = w.slab_bytes;      // q|k|v kept in the operand type
+        GemmArgs g1 = outfit_gemm(h, Ly.w_in, D, w.slab, w.slab_bytes);
+        g1.A = t.H1; g1.C = t.QKV; g1.bias = Ly.b_in; g1.m_dev = m_dev; g1.M = M; g1.N = 3 * D; g1.ldc = 3 * D; g1.out_kind = OFX_OUT_OP;      // q|k|v kept in the operand type
         TRY(ofx_launch_gemm(g1, dt, s));
-        const bool last = l + 1 == d.n_layers;
         if (g_train_mfma_attn) {           // varlen MFMA attention on the operand-type q|k|v (probabilities rounded to the operand type, as autocast SDPA does)
             AttnArgs at{t.QKV, t.O, nullptr, B, L + 1, d.n_head, 3 * D, D, D, 2 * D, 0, 0, 0.125f};
             at.cu_seqlens = T.cu; at.only_row0 = last ? 1 : 0; at.drop = make_drop(dropout_p, seed, 4 * l + 0);
@@ -1109,46 +1110,34 @@ static int cp_train_fwd_core(ofx_handle* h, const SetInput& in, int B, int L, fl
             sa.drop = make_drop(dropout_p, seed, 4 * l + 0); sa.qkv_op = 1;
             TRY(ofx_launch_set_attention(sa, dt, s));
         }
+        // the rest of the layer: on the live rows, from the attention output and the layer input into the next layer's input
+        int rows = M; const int* md = m_dev; const void* O = t.O; const float* Xin = t.Xin; float* Xout = last ? T.row0 : T.L[l + 1].Xin;
         if (last) {
             // Only the prefix row of every outfit feeds the heads (outfit_x.py:142,170): out-proj, LayerNorm-2 and the FFN of the last
             // layer run on those B rows (compacted: row b of the Xmid / st2 / H2 / Upre / A tape buffers; dropout rows = b).
             TRY(ofx_launch_gather_rows(t.O, T.cu, T.pO, B, D * 2, D * 2, s));
             TRY(ofx_launch_gather_rows(t.Xin, T.cu, T.pX, B, D * 4, D * 4, s));
-            GemmArgs p2{}; p2.A = T.pO; p2.W = Ly.w_out; p2.C = t.Xmid; p2.bias = Ly.b_out; p2.resid = T.pX; p2.M = B; p2.N = D; p2.K = D;
-            p2.lda = D; p2.ldc = D; p2.ldr = D; p2.out_kind = OFX_OUT_F32; p2.slab = w.slab; p2.slab_bytes = w.slab_bytes;
-            p2.drop = make_drop(dropout_p, seed, 4 * l + 1);
-            TRY(ofx_launch_gemm(p2, dt, s));
-            LnArgs lp{t.Xmid, nullptr, Ly.g2, Ly.be2, t.H2, B, D, D, OFX_OUT_OP, d.ln_eps}; lp.stats = t.st2;
-            TRY(ofx_launch_layernorm(lp, dt, s));
-            GemmArgs p3{}; p3.A = t.H2; p3.W = Ly.w_1; p3.C = t.A; p3.bias = Ly.b_1; p3.aux_out = t.Upre; p3.M = B; p3.N = Fp; p3.K = D;
-            p3.lda = D; p3.ldc = Fp; p3.act = d.outfit_act; p3.out_kind = OFX_OUT_OP; p3.slab = w.slab; p3.slab_bytes = w.slab_bytes;
-            p3.drop = make_drop(dropout_p, seed, 4 * l + 2);
-            TRY(ofx_launch_gemm(p3, dt, s));
-            GemmArgs p4{}; p4.A = t.A; p4.W = Ly.w_2; p4.C = T.row0; p4.bias = Ly.b_2; p4.resid = t.Xmid; p4.M = B; p4.N = D; p4.K = Fp;
-            p4.lda = Fp; p4.ldc = D; p4.ldr = D; p4.out_kind = OFX_OUT_F32; p4.slab = w.slab; p4.slab_bytes = w.slab_bytes;
-            p4.drop = make_drop(dropout_p, seed, 4 * l + 3);
-            TRY(ofx_launch_gemm(p4, dt, s));
-            break;
+            rows = B; md = nullptr; O = T.pO; Xin = T.pX;
         }
-        GemmArgs g2{}; g2.A = t.O; g2.W = Ly.w_out; g2.C = t.Xmid; g2.bias = Ly.b_out; g2.resid = t.Xin; g2.m_dev = m_dev; g2.M = M; g2.N = D; g2.K = D;
-        g2.lda = D; g2.ldc = D; g2.ldr = D; g2.out_kind = OFX_OUT_F32; g2.slab = w.slab; g2.slab_bytes = w.slab_bytes;
+        GemmArgs g2 = outfit_gemm(h, Ly.w_out, D, w.slab, w.slab_bytes);
+        g2.A = O; g2.C = t.Xmid; g2.bias = Ly.b_out; g2.resid = Xin; g2.m_dev = md; g2.M = rows; g2.N = D; g2.ldc = D; g2.ldr = D; g2.out_kind = OFX_OUT_F32;
         g2.drop = make_drop(dropout_p, seed, 4 * l + 1);
         TRY(ofx_launch_gemm(g2, dt, s));
-        LnArgs ln2{t.Xmid, nullptr, Ly.g2, Ly.be2, t.H2, M, D, D, OFX_OUT_OP, d.ln_eps}; ln2.stats = t.st2;
-        TRY(ofx_launch_layernorm_dev(ln2, m_dev, dt, s));
-        GemmArgs g3{}; g3.A = t.H2; g3.W = Ly.w_1; g3.C = t.A; g3.bias = Ly.b_1; g3.aux_out = t.Upre; g3.m_dev = m_dev; g3.M = M; g3.N = Fp; g3.K = D;
-        g3.lda = D; g3.ldc = Fp; g3.act = d.outfit_act; g3.out_kind = OFX_OUT_OP; g3.slab = w.slab; g3.slab_bytes = w.slab_bytes;
+        LnArgs ln2{t.Xmid, nullptr, Ly.g2, Ly.be2, t.H2, rows, D, D, OFX_OUT_OP, d.ln_eps}; ln2.stats = t.st2;
+        TRY(ofx_launch_layernorm_dev(ln2, md, dt, s));
+        GemmArgs g3 = outfit_gemm(h, Ly.w_1, D, w.slab, w.slab_bytes);
+        g3.A = t.H2; g3.C = t.A; g3.bias = Ly.b_1; g3.aux_out = t.Upre; g3.m_dev = md; g3.M = rows; g3.N = Fp; g3.ldc = Fp; g3.act = d.outfit_act; g3.out_kind = OFX_OUT_OP;
         g3.drop = make_drop(dropout_p, seed, 4 * l + 2);
         TRY(ofx_launch_gemm(g3, dt, s));
-        GemmArgs g4{}; g4.A = t.A; g4.W = Ly.w_2; g4.C = Xnext; g4.bias = Ly.b_2; g4.resid = t.Xmid; g4.m_dev = m_dev; g4.M = M; g4.N = D; g4.K = Fp;
-        g4.lda = Fp; g4.ldc = D; g4.ldr = D; g4.out_kind = OFX_OUT_F32; g4.slab = w.slab; g4.slab_bytes = w.slab_bytes;
+        GemmArgs g4 = outfit_gemm(h, Ly.w_2, Fp, w.slab, w.slab_bytes);
+        g4.A = t.A; g4.C = Xout; g4.bias = Ly.b_2; g4.resid = t.Xmid; g4.m_dev = md; g4.M = rows; g4.N = D; g4.ldc = D; g4.ldr = D; g4.out_kind = OFX_OUT_F32;
         g4.drop = make_drop(dropout_p, seed, 4 * l + 3);
         TRY(ofx_launch_gemm(g4, dt, s));
     }
     if (head == 1) {                                                // cir_ffn = Linear(D, d_embed, bias=False): no dropout (outfit_x.py:61-63)
         TRY(ofx_launch_pack_rows(T.row0, T.row0b, B, B, D, D, D, 0, dt, s));
-        GemmArgs g{}; g.A = T.row0b; g.W = h->cir_w; g.C = logits; g.M = B; g.N = D; g.K = D; g.lda = D; g.ldc = D; g.out_kind = OFX_OUT_F32;
-        g.slab = w.slab; g.slab_bytes = w.slab_bytes;
+        GemmArgs g = outfit_gemm(h, h->cir_w, D, w.slab, w.slab_bytes);
+        g.A = T.row0b; g.C = logits; g.M = B; g.N = D; g.ldc = D; g.out_kind = OFX_OUT_F32;
         return ofx_launch_gemm(g, dt, s);
     }
     TRY(ofx_launch_drop_rows(T.row0, B, D, make_drop(dropout_p, seed, 4 * d.n_layers), s));     // the tape keeps the dropped-out rows
@@ -1193,7 +1182,7 @@ static int set_train_bwd_core(ofx_handle* h, void* tape_mem, size_t tape_bytes, 
     if (h) layer_ev.swap(h->bwd_events);
     OFX_REQUIRE(h && h->out_ready && h->ot_kmul == 1 && !h->ot_w2, OFX_ESTATE, "cp_train_bwd: needs packed single-product weights");
     OFX_REQUIRE(tape_mem && dlogits && (grads || grad_ptrs) && ws && B > 0, OFX_EINVAL, "cp_train_bwd: bad argument");
-    OFX_REQUIRE(d_outfit_act_is_mish(h), OFX_ESTATE, "cp_train_bwd: only the Mish activation has a backward epilogue");
+    OFX_REQUIRE(h->d.outfit_act == OFX_ACT_MISH, OFX_ESTATE, "cp_train_bwd: only the Mish activation has a backward epilogue");
     const ofx_model_desc& d = h->d;
     hipStream_t s = (hipStream_t)stream;
     Bump tb(tape_mem, tape_bytes);
@@ -1213,92 +1202,70 @@ static int set_train_bwd_core(ofx_handle* h, void* tape_mem, size_t tape_bytes, 
     // destination of packed tensor i; in the per-parameter form the FFN tensors have their real (unpadded) extents
     auto G = [&](int i) -> float* { return grad_ptrs ? grad_ptrs[i] : grads + off[i]; };
     const int Fv = grad_ptrs ? F : Fp;                 // valid rows of dW1 / entries of db1 / columns of dW2
-    auto dgrad = [&](const void* A, int lda, const void* W, void* C, int ldc, int n, int k, int out_kind, int act, const float* resid, int ldr, const DropArgs& drop) {
-        GemmArgs g{}; g.A = A; g.W = W; g.C = C; g.M = M; g.N = n; g.K = k; g.lda = lda; g.ldc = ldc; g.out_kind = out_kind; g.act = act; g.resid = resid; g.ldr = ldr;
-        g.m_dev = m_dev; g.slab = w.slab; g.slab_bytes = w.slab_bytes; g.drop = drop;
-        return ofx_launch_gemm(g, dt, s);
-    };
     auto site = [&](int l, int k) { return make_drop(dropout_p, seed, 4 * l + k); };
     const DropArgs nodrop;
-    // dW[n_w, k_w] = dY[rows, n_w]^T X[rows, k_w], contraction over the live rows
-    // out[:mv, :nv] (row pitch ldc) of dW[n_w, k_w] = dY^T X; the per-parameter form stores only the real FFN extent
-    auto wgrad_rows = [&](int rows, const int* md, const void* dY, int n_w, const void* X, int k_w, float* out, int ldc = 0, int mv = 0, int nv = 0) {
+    // Both GEMMs of the backward run on (rows, md) = (M, m_dev), the pad-free live rows, or (B, nullptr), the compacted prefix rows of
+    // the pruned last layer.
+    // wgrad: dW[n_w, k_w] = dY[rows, n_w]^T X[rows, k_w], contraction over the rows -> out[:mv, :nv] (row pitch ldc): the per-parameter
+    // form stores only the real FFN extent
+    auto wgrad = [&](int rows, const int* md, const void* dY, int n_w, const void* X, int k_w, float* out, int ldc = 0, int mv = 0, int nv = 0) {
         return ofx_launch_gemm_tn(dY, n_w, X, k_w, out, ldc ? ldc : k_w, n_w, k_w, rows, md, w.slab, w.slab_bytes, dt, s, mv, nv, acc);
     };
-    auto wgrad = [&](const void* dY, int n_w, const void* X, int k_w, float* out, int ldc = 0, int mv = 0, int nv = 0) {
-        return wgrad_rows(M, m_dev, dY, n_w, X, k_w, out, ldc, mv, nv);
-    };
-    // rows == M with m_dev: the pad-free live rows; rows == B with md == nullptr: the compacted prefix rows of the pruned last layer
-    auto dgrad_rows = [&](int rows, const int* md, const void* A, int lda, const void* W, void* C, int ldc, int n, int k, int out_kind, int act, const float* resid,
-                          int ldr, const DropArgs& drop) {
-        GemmArgs g{}; g.A = A; g.W = W; g.C = C; g.M = rows; g.N = n; g.K = k; g.lda = lda; g.ldc = ldc; g.out_kind = out_kind; g.act = act; g.resid = resid; g.ldr = ldr;
-        g.m_dev = md; g.slab = w.slab; g.slab_bytes = w.slab_bytes; g.drop = drop;
+    // dgrad: C[rows, n] = epilogue(dY[rows, k] Wt[n, k]^T), Wt the W^T operand copy of the pack
+    auto dgrad = [&](int rows, const int* md, const void* dY, const void* Wt, void* C, int n, int k, int out_kind = OFX_OUT_F32, int act = OFX_ACT_NONE,
+                     const float* resid = nullptr, const DropArgs& drop = DropArgs()) {
+        GemmArgs g = outfit_gemm(h, Wt, k, w.slab, w.slab_bytes);
+        g.A = dY; g.C = C; g.M = rows; g.N = n; g.ldc = n; g.out_kind = out_kind; g.act = act; g.resid = resid; g.ldr = resid ? n : 0; g.m_dev = md; g.drop = drop;
         return ofx_launch_gemm(g, dt, s);
     };
+    const auto attention_bwd = g_train_mfma_attn ? ofx_launch_set_attention_bwd_mfma : ofx_launch_set_attention_bwd;
     float* dX = w.dXa; float* dX2 = w.dXb_f;
     const int lastl = d.n_layers - 1;
     // ---- heads -> d row0 [B, D] (fp32, w.d_row0) and its operand copy times the last layer's dropout2 mask (w.gXb rows 0..B)
     if (head == 1) {
         // y = row0 Wc^T:  dWc = dy^T row0 (TN GEMM over the B rows), d row0 = dy Wc
         TRY(ofx_launch_pack_rows(dlogits, w.dyb, B, B, D, D, D, 0, dt, s));
-        TRY(ofx_launch_gemm_tn(w.dyb, D, T.row0b, D, G(4), D, D, D, B, nullptr, w.slab, w.slab_bytes, dt, s, 0, 0, acc));
-        GemmArgs g{}; g.A = w.dyb; g.W = h->cir_w_t; g.C = w.d_row0; g.M = B; g.N = D; g.K = D; g.lda = D; g.ldc = D; g.out_kind = OFX_OUT_F32;
-        g.slab = w.slab; g.slab_bytes = w.slab_bytes;
-        TRY(ofx_launch_gemm(g, dt, s));
+        TRY(wgrad(B, nullptr, w.dyb, D, T.row0b, D, G(4)));
+        TRY(dgrad(B, nullptr, w.dyb, h->cir_w_t, w.d_row0, D, D));
         TRY(ofx_launch_cp_head_bwd(nullptr, w.d_row0, nullptr, w.d_row0, w.gXb, nullptr, B, D, dt, nodrop, site(lastl, 3), s));
     } else {
         TRY(ofx_launch_cp_head_bwd(dlogits, h->cp_w, nullptr, w.d_row0, w.gXb, G(3), B, D, dt, site(d.n_layers, 0), site(lastl, 3), s, acc));
         TRY(ofx_launch_colsum(T.row0, 0, D, nullptr, dlogits, G(2), nullptr, nullptr, D, w.part, D, nullptr, B, dt, s, 0, acc));             // d cp_w = sum_b dlogit_b (row0_b . m_head)
     }
     TRY(ofx_launch_row_map(T.cu, w.rowmap, B, M, s));
-    {   // ---- last layer: FFN, LayerNorm-2 and out-proj only saw the B prefix rows (compacted, static count)
-        const OutfitLayer& Ly = h->ol[lastl];
-        const TapeLayer& t = T.L[lastl];
-        const int g0 = 5 + 12 * lastl;
-        TRY(ofx_launch_colsum(w.gXb, 1, D, nullptr, nullptr, G(g0 + 7), nullptr, nullptr, D, w.part, D, nullptr, B, dt, s, 0, acc));                      // db2
-        TRY(wgrad_rows(B, nullptr, w.gXb, D, t.A, Fp, G(g0 + 6), Fv, D, Fv));                                                                    // dW2
-        TRY(dgrad_rows(B, nullptr, w.gXb, D, Ly.w_2_t, w.dU, Fp, Fp, D, OFX_OUT_OP, OFX_ACT_MISH_GRAD, t.Upre, Fp, site(lastl, 2)));  // dU
-        TRY(ofx_launch_colsum(w.dU, 1, Fp, nullptr, nullptr, G(g0 + 5), nullptr, nullptr, Fp, w.part, Fp, nullptr, B, dt, s, Fv, acc));                    // db1
-        TRY(wgrad_rows(B, nullptr, w.dU, Fp, t.H2, D, G(g0 + 4), D, Fv, D));                                                                    // dW1
-        TRY(dgrad_rows(B, nullptr, w.dU, Fp, Ly.w_1_t, w.dH, D, D, Fp, OFX_OUT_F32, OFX_ACT_NONE, nullptr, 0, nodrop));               // dH2
-        TRY(ofx_launch_ln_bwd(w.dH, t.Xmid, t.st2, Ly.g2, w.d_row0, nullptr, dX2, w.gXb, G(g0 + 10), G(g0 + 11), G(g0 + 3), w.part, D, nullptr, B, dt,
-                              site(lastl, 1), s, acc));                                                                                    // dXmid (B rows) + dbo
-        TRY(wgrad_rows(B, nullptr, w.gXb, D, T.pO, D, G(g0 + 2)));                                                                    // dWo
-        TRY(dgrad_rows(B, nullptr, w.gXb, D, Ly.w_out_t, w.dO, D, D, D, OFX_OUT_F32, OFX_ACT_NONE, nullptr, 0, nodrop));              // dO (B rows)
-        TRY((g_train_mfma_attn ? ofx_launch_set_attention_bwd_mfma : ofx_launch_set_attention_bwd)(t.QKV, w.dO, w.gQb, T.cu, B, d.n_head, D, L + 1, 0.125f, dt,
-                                                                                                     site(lastl, 0), 1, s));    // all rows get dK, dV
-        TRY(ofx_launch_colsum(w.gQb, 1, 3 * D, nullptr, nullptr, G(g0 + 1), nullptr, nullptr, 3 * D, w.part, 3 * D, m_dev, M, dt, s, 0, acc));
-        TRY(wgrad_rows(M, m_dev, w.gQb, 3 * D, t.H1, D, G(g0 + 0)));
-        TRY(dgrad_rows(M, m_dev, w.gQb, 3 * D, Ly.w_in_t, w.dH, D, D, 3 * D, OFX_OUT_F32, OFX_ACT_NONE, nullptr, 0, nodrop));
-        // dXin = LayerNorm-1 backward + (dXmid at the prefix rows); its column sums = bias gradient of the layer below's linear2
-        TRY(ofx_launch_ln_bwd(w.dH, t.Xin, t.st1, Ly.g1, dX2, w.rowmap, dX, w.gXb, G(g0 + 8), G(g0 + 9), lastl > 0 ? G(g0 - 12 + 7) : nullptr, w.part, D, m_dev, M, dt,
-                              lastl > 0 ? site(lastl - 1, 3) : nodrop, s, acc));
-        // all 12 gradient tensors of the last layer are final (its linear2 bias gradient comes from this very LayerNorm backward of the
-        // layer ABOVE - none here - i.e. from the head path): a data-parallel host may start reducing them now
-        if (!layer_ev.empty()) OFX_HIP(hipEventRecord(layer_ev[lastl], s));
-    }
-    for (int l = lastl - 1; l >= 0; --l) {
+    for (int l = lastl; l >= 0; --l) {
         const OutfitLayer& Ly = h->ol[l];
         const TapeLayer& t = T.L[l];
         const int g0 = 5 + 12 * l;                    // Win, bin, Wo, bo, W1, b1, W2, b2, g1, be1, g2, be2
-        // ---- FFN branch: Xout = Xmid + mish(H2 W1^T + b1) W2^T + b2        (gXb = operand copy of dX)
-        TRY(wgrad(w.gXb, D, t.A, Fp, G(g0 + 6), Fv, D, Fv));                                                                   // dW2 [D, Fp]
-        TRY(dgrad(w.gXb, D, Ly.w_2_t, w.dU, Fp, Fp, D, OFX_OUT_OP, OFX_ACT_MISH_GRAD, t.Upre, Fp, site(l, 2)));                 // dU = (dX W2) * mish'(Upre)
-        TRY(ofx_launch_colsum(w.dU, 1, Fp, nullptr, nullptr, G(g0 + 5), nullptr, nullptr, Fp, w.part, Fp, m_dev, M, dt, s, Fv, acc));   // db1
-        TRY(wgrad(w.dU, Fp, t.H2, D, G(g0 + 4), D, Fv, D));                                                                   // dW1 [Fp, D]
-        TRY(dgrad(w.dU, Fp, Ly.w_1_t, w.dH, D, D, Fp, OFX_OUT_F32, OFX_ACT_NONE, nullptr, 0, nodrop));                      // dH2
-        TRY(ofx_launch_ln_bwd(w.dH, t.Xmid, t.st2, Ly.g2, dX, nullptr, dX2, w.gXb, G(g0 + 10), G(g0 + 11), G(g0 + 3), w.part, D, m_dev, M, dt, site(l, 1), s, acc));   // dXmid (+ dbo)
+        // The last layer's FFN, LayerNorm-2 and out-proj only saw the B prefix rows (compacted, static count): its upstream gradient is
+        // the heads' d row0, and dXmid flows back into the full rows through the row map.  Below it, every row is live.
+        const bool last = l == lastl;
+        const int rows = last ? B : M;
+        const int* md = last ? nullptr : m_dev;
+        const void* O = last ? T.pO : t.O;
+        const float* dXout = last ? w.d_row0 : dX;
+        // ---- FFN branch: Xout = Xmid + mish(H2 W1^T + b1) W2^T + b2        (gXb = operand copy of dXout)
+        if (last) TRY(ofx_launch_colsum(w.gXb, 1, D, nullptr, nullptr, G(g0 + 7), nullptr, nullptr, D, w.part, D, nullptr, B, dt, s, 0, acc));   // db2: no layer above supplies it
+        TRY(wgrad(rows, md, w.gXb, D, t.A, Fp, G(g0 + 6), Fv, D, Fv));                                                                 // dW2 [D, Fp]
+        TRY(dgrad(rows, md, w.gXb, Ly.w_2_t, w.dU, Fp, D, OFX_OUT_OP, OFX_ACT_MISH_GRAD, t.Upre, site(l, 2)));                          // dU = (dXout W2) * mish'(Upre)
+        TRY(ofx_launch_colsum(w.dU, 1, Fp, nullptr, nullptr, G(g0 + 5), nullptr, nullptr, Fp, w.part, Fp, md, rows, dt, s, Fv, acc));    // db1
+        TRY(wgrad(rows, md, w.dU, Fp, t.H2, D, G(g0 + 4), D, Fv, D));                                                                  // dW1 [Fp, D]
+        TRY(dgrad(rows, md, w.dU, Ly.w_1_t, w.dH, D, Fp));                                                                             // dH2
+        TRY(ofx_launch_ln_bwd(w.dH, t.Xmid, t.st2, Ly.g2, dXout, nullptr, dX2, w.gXb, G(g0 + 10), G(g0 + 11), G(g0 + 3), w.part, D, md, rows, dt, site(l, 1), s, acc));   // dXmid (+ dbo)
         // ---- attention branch: Xmid = Xin + O Wo^T + bo
-        TRY(wgrad(w.gXb, D, t.O, D, G(g0 + 2)));                                                                    // dWo [D, D]
-        TRY(dgrad(w.gXb, D, Ly.w_out_t, w.dO, D, D, D, OFX_OUT_F32, OFX_ACT_NONE, nullptr, 0, nodrop));                     // dO
-        TRY((g_train_mfma_attn ? ofx_launch_set_attention_bwd_mfma : ofx_launch_set_attention_bwd)(t.QKV, w.dO, w.gQb, T.cu, B, d.n_head, D, L + 1, 0.125f, dt, site(l, 0), 0, s));
+        TRY(wgrad(rows, md, w.gXb, D, O, D, G(g0 + 2)));                                                                               // dWo [D, D]
+        TRY(dgrad(rows, md, w.gXb, Ly.w_out_t, w.dO, D, D));                                                                           // dO
+        TRY(attention_bwd(t.QKV, w.dO, w.gQb, T.cu, B, d.n_head, D, L + 1, 0.125f, dt, site(l, 0), last ? 1 : 0, s));                  // (last layer: only row 0 has a dO, all rows get dK, dV)
         TRY(ofx_launch_colsum(w.gQb, 1, 3 * D, nullptr, nullptr, G(g0 + 1), nullptr, nullptr, 3 * D, w.part, 3 * D, m_dev, M, dt, s, 0, acc));   // dbin
-        TRY(wgrad(w.gQb, 3 * D, t.H1, D, G(g0 + 0)));                                                               // dWin [3D, D]
-        TRY(dgrad(w.gQb, 3 * D, Ly.w_in_t, w.dH, D, D, 3 * D, OFX_OUT_F32, OFX_ACT_NONE, nullptr, 0, nodrop));              // dH1
-        // dXin; its column sums are the bias gradient of the layer below's linear2
-        TRY(ofx_launch_ln_bwd(w.dH, t.Xin, t.st1, Ly.g1, dX2, nullptr, dX, w.gXb, G(g0 + 8), G(g0 + 9), l > 0 ? G(g0 - 12 + 7) : nullptr, w.part, D, m_dev, M, dt,
-                              l > 0 ? site(l - 1, 3) : nodrop, s, acc));
-        if (!layer_ev.empty()) OFX_HIP(hipEventRecord(layer_ev[l], s));      // layer l's gradients are final (its b2 came from layer l+1's LayerNorm-1 backward)
+        TRY(wgrad(M, m_dev, w.gQb, 3 * D, t.H1, D, G(g0 + 0)));                                                                        // dWin [3D, D]
+        TRY(dgrad(M, m_dev, w.gQb, Ly.w_in_t, w.dH, D, 3 * D));                                                                        // dH1
+        // dXin = LayerNorm-1 backward + dXmid (last layer: at the prefix rows); its column sums are the bias gradient of the layer
+        // below's linear2
+        TRY(ofx_launch_ln_bwd(w.dH, t.Xin, t.st1, Ly.g1, dX2, last ? w.rowmap : nullptr, dX, w.gXb, G(g0 + 8), G(g0 + 9), l > 0 ? G(g0 - 12 + 7) : nullptr, w.part, D,
+                              m_dev, M, dt, l > 0 ? site(l - 1, 3) : nodrop, s, acc));
+        // all 12 gradient tensors of layer l are final: its linear2 bias gradient came from the LayerNorm-1 backward of layer l + 1, or,
+        // for the last layer, from the head path above.  A data-parallel host may start reducing them now
+        if (!layer_ev.empty()) OFX_HIP(hipEventRecord(layer_ev[l], s));
     }
     // CIR: the prefix is [target_item_image_emb | text]: d target_item_image_emb = sum_b dX0[cu[b]][:D/2]
     if (head == 1) return ofx_launch_colsum(dX, 0, D, T.cu, nullptr, G(1), nullptr, nullptr, D / 2, w.part, D / 2, nullptr, B, dt, s, 0, acc);
@@ -1362,22 +1329,25 @@ extern "C" int ofx_tune(int knob, int value) {
 }
 
 // ------------------------------------------------------------------------------------- op level
-extern "C" int ofx_gemm(const void* A, const void* W, void* C, const float* bias, const float* resid, int M, int N, int K,
-                        int lda, int ldc, int ldr, int act, int out_kind, int op_dtype, ofx_stream stream) {
+// the arguments every op-level GEMM entry point shares; K = the depth of the W rows as stored
+static GemmArgs op_gemm(const void* A, const void* W, void* C, const float* bias, const float* resid, int M, int N, int K, int lda, int ldc, int ldr,
+                        int act, int out_kind) {
     GemmArgs g{}; g.A = A; g.W = W; g.C = C; g.bias = bias; g.resid = resid; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc;
     g.ldr = ldr; g.act = act; g.out_kind = out_kind;
-    return ofx_launch_gemm(g, op_dtype, (hipStream_t)stream);
+    return g;
+}
+extern "C" int ofx_gemm(const void* A, const void* W, void* C, const float* bias, const float* resid, int M, int N, int K,
+                        int lda, int ldc, int ldr, int act, int out_kind, int op_dtype, ofx_stream stream) {
+    return ofx_launch_gemm(op_gemm(A, W, C, bias, resid, M, N, K, lda, ldc, ldr, act, out_kind), op_dtype, (hipStream_t)stream);
 }
 extern "C" int ofx_gemm_w2(const void* A, const void* W2, void* C, const float* bias, const float* resid, int M, int N, int K,
                            int lda, int ldc, int ldr, int act, int out_kind, int op_dtype, ofx_stream stream) {
-    GemmArgs g{}; g.A = A; g.W = W2; g.C = C; g.bias = bias; g.resid = resid; g.M = M; g.N = N; g.K = 2 * K; g.a_wrap = K; g.lda = lda; g.ldc = ldc;
-    g.ldr = ldr; g.act = act; g.out_kind = out_kind;
+    GemmArgs g = op_gemm(A, W2, C, bias, resid, M, N, 2 * K, lda, ldc, ldr, act, out_kind); g.a_wrap = K;
     return ofx_launch_gemm(g, op_dtype, (hipStream_t)stream);
 }
 extern "C" int ofx_gemm_x3(const void* A3, const void* W3, void* C, const float* bias, const float* resid, int M, int N, int K,
                            int lda, int ldc, int ldr, int act, int out_kind, int op_dtype, ofx_stream stream) {
-    GemmArgs g{}; g.A = A3; g.W = W3; g.C = C; g.bias = bias; g.resid = resid; g.M = M; g.N = N; g.K = 3 * K; g.k_mult = 3; g.lda = lda; g.ldc = ldc;
-    g.ldr = ldr; g.act = act; g.out_kind = out_kind;
+    GemmArgs g = op_gemm(A3, W3, C, bias, resid, M, N, 3 * K, lda, ldc, ldr, act, out_kind); g.k_mult = 3;
     return ofx_launch_gemm(g, op_dtype, (hipStream_t)stream);
 }
 extern "C" int ofx_pack_lo8(const void* W2, void* W8, void* scale8, int N, int K, ofx_stream stream) {
@@ -1385,15 +1355,13 @@ extern "C" int ofx_pack_lo8(const void* W2, void* W8, void* scale8, int N, int K
 }
 extern "C" int ofx_gemm_w2f8(const void* A, const void* W2, const void* W8, const void* scale8, void* C, const float* bias, const float* resid, int M, int N, int K,
                              int lda, int ldc, int ldr, int act, int out_kind, ofx_stream stream) {
-    GemmArgs g{}; g.A = A; g.W = W2; g.W8 = W8; g.w8_scale = scale8; g.C = C; g.bias = bias; g.resid = resid; g.M = M; g.N = N; g.K = 2 * K; g.a_wrap = K; g.lda = lda; g.ldc = ldc;
-    g.ldr = ldr; g.act = act; g.out_kind = out_kind;
+    GemmArgs g = op_gemm(A, W2, C, bias, resid, M, N, 2 * K, lda, ldc, ldr, act, out_kind); g.a_wrap = K; g.W8 = W8; g.w8_scale = scale8;
     return ofx_launch_gemm(g, OFX_F16, (hipStream_t)stream);
 }
 extern "C" size_t ofx_gemm_splitk_ws(int M, int N, int K) { return ofx_gemm_splitk_bytes(M, N, K); }
 extern "C" int ofx_gemm_splitk(const void* A, const void* W, void* C, const float* bias, const float* resid, int M, int N, int K,
                                int lda, int ldc, int ldr, int act, int out_kind, int op_dtype, void* slab, size_t slab_bytes, ofx_stream stream) {
-    GemmArgs g{}; g.A = A; g.W = W; g.C = C; g.bias = bias; g.resid = resid; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc;
-    g.ldr = ldr; g.act = act; g.out_kind = out_kind; g.slab = slab; g.slab_bytes = slab_bytes;
+    GemmArgs g = op_gemm(A, W, C, bias, resid, M, N, K, lda, ldc, ldr, act, out_kind); g.slab = slab; g.slab_bytes = slab_bytes;
     return ofx_launch_gemm(g, op_dtype, (hipStream_t)stream);
 }
 extern "C" size_t ofx_gemm_tn_ws(int M, int N, int K) { return ofx_gemm_tn_slab_bytes(M, N, K); }

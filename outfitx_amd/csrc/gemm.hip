@@ -194,7 +194,6 @@ static SmallPlan plan_small(int M, int N, int K, bool allow_split, bool allow64)
     }
     return best;
 }
-int ofx_gemm_splitk_plan(int M, int N, int K) { return plan_small(M, N, K, true, M > 64).splits; }
 // Slab size for ANY plan the launcher may pick for this shape: it plans with or without 64-row tiles depending on the kernel knobs
 // and the grid (can64 in ofx_launch_gemm), so the slab covers the larger slice count of the two tile heights (forced plans: <= 16).
 size_t ofx_gemm_splitk_bytes(int M, int N, int K) {

@@ -414,13 +414,6 @@ __global__ __launch_bounds__(256) void gather_hilo_kernel(const T* hi, const T* 
     }
 }
 
-// out[b] = X[cu[b]]
-__global__ __launch_bounds__(256) void gather_row0_kernel(const float* X, const int* cu, float* out, int B, int D) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int b = blockIdx.x * 4 + w; b < B; b += gridDim.x * 4)
-        for (int c = lane; c < D / 4; c += 64) *(f32x4*)(out + (size_t)b * D + c * 4) = *(const f32x4*)(X + (size_t)cu[b] * D + c * 4);
-}
-
 // CIR prefix token: out[b] = [img_emb (D/2) | text_emb[b] (D/2)]
 __global__ __launch_bounds__(256) void cir_prefix_kernel(const float* img_emb, const float* txt, float* out, int B, int D) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, H = D / 2;
@@ -644,11 +637,6 @@ __global__ __launch_bounds__(256) void fill_f32_kernel(float* p, size_t n, float
 int ofx_launch_fill_f32(float* p, size_t n, float v, hipStream_t s) {
     const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
     hipLaunchKernelGGL(fill_f32_kernel, dim3(grid < 1 ? 1 : grid), dim3(256), 0, s, p, n, v);
-    OFX_LAUNCH_CHECK();
-    return OFX_OK;
-}
-int ofx_launch_gather_row0(const float* X, const int* cu, float* out, int B, int D, hipStream_t s) {
-    hipLaunchKernelGGL(gather_row0_kernel, dim3(rows_grid(B)), dim3(256), 0, s, X, cu, out, B, D);
     OFX_LAUNCH_CHECK();
     return OFX_OK;
 }

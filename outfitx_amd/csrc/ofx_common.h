@@ -256,7 +256,6 @@ struct GemmArgs {
     bool* ln_done = nullptr;
 };
 int ofx_launch_gemm(const GemmArgs& g, int op_dtype /*OFX_BF16|OFX_F16*/, hipStream_t s);
-int ofx_gemm_splitk_plan(int M, int N, int K);
 size_t ofx_gemm_splitk_bytes(int M, int N, int K);
 
 struct LnArgs {
@@ -308,7 +307,6 @@ int ofx_launch_gather_hilo(const void* hi, const void* lo, const int* idx, float
 int ofx_launch_stats_finalize(const float* part, int slots, int W, float eps, float* stat, int rows, hipStream_t s);
 int ofx_launch_fold_pack(const float* Wsrc, const float* gamma, const float* beta, const float* bias, void* Wf, float* col_sum, float* bias_f,
                          int N, int K, int op_dtype, hipStream_t s, int split = 0);
-int ofx_launch_gather_row0(const float* X, const int* cu, float* out, int B, int D, hipStream_t s);
 int ofx_launch_cir_prefix(const float* img_emb, const float* txt, float* out, int B, int D, hipStream_t s);
 int ofx_launch_cp_head(const float* row0, const float* w, const float* bias, float* logits, int B, int D, hipStream_t s);
 

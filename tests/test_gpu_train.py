@@ -27,15 +27,20 @@ def cu(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def make_model(train_precision, dropout=0.0):
+def make_model(train_precision, dropout=0.0, n_layers=None):
     if not torch.cuda.is_available():
         pytest.skip("needs a HIP device")
     from src.models import OutfitX
     from src.models.configs import ItemEncoderConfig, OutfitXConfig
     cfg = OutfitXConfig(item_encoder=ItemEncoderConfig(type="clip"))
     cfg.transformer.dropout = dropout
+    if n_layers is not None:
+        cfg.transformer.n_layers = n_layers
     m = OutfitX(cfg, train_precision=train_precision)
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in synth.full_state_dict(W_SEED).items()}, strict=True)
+    sd = {k: torch.from_numpy(v) for k, v in synth.full_state_dict(W_SEED).items()}
+    if n_layers is not None:            # the synthetic weights are the 6-layer model's: a shallower one takes its first layers
+        sd = {k: v for k, v in sd.items() if k in m.state_dict()}
+    m.load_state_dict(sd, strict=True)
     return m.cuda().train()
 
 
@@ -102,41 +107,62 @@ def test_cp_train_step_vs_reference_golden(prec, gtol, ltol, fused_loss):
         assert np.mean(np.abs(du - dr) > 0.1 * float(g["lr"])) <= 0.01, k
 
 
-@pytest.mark.parametrize("n,Lp", [([2, 9, 16, 1, 5, 7], 16), ([31, 1, 22, 30], 31)])
-def test_train_step_matches_torch_autograd_of_the_same_module(n, Lp):
+@pytest.mark.parametrize("n,Lp,n_layers", [([2, 9, 16, 1, 5, 7], 16, None), ([31, 1, 22, 30], 31, None), ([1, 4, 2], 4, 1)],
+                         ids=["n0-16", "n1-31", "n2-4-one_layer"])
+def test_train_step_matches_torch_autograd_of_the_same_module(n, Lp, n_layers):
     """Independent check on fresh inputs: the same nn.TransformerEncoder (plain PyTorch fp32, run on the GPU box's CPU)
     with the same weights -> autograd gradients; ours (f16 operands) within 5e-3 per parameter.  The second case runs the
-    longest sets the kernels take (31 items + prefix = 32 rows: the SMAX = 32 attention variants)."""
-    from src.models.datatypes import OutfitCompatibilityPredictionTask as CP
+    longest sets the kernels take (31 items + prefix = 32 rows: the SMAX = 32 attention variants).  The third is a one-layer
+    model, whose only layer is the pruned last layer AND layer 0 of the backward (no layer below to hand a linear2 bias
+    gradient or a dropout site to); it checks the CIR head's gradients the same way as the CP head's."""
+    from src.models.datatypes import OutfitCompatibilityPredictionTask as CP, OutfitComplementaryItemRetrievalTask as CIR
     n = np.array(n)
-    emb, mask = synth.outfit_batch(4321, len(n), Lp, n)
-    m = make_model("f16")
-    up = torch.linspace(-1.0, 2.0, len(n))
-    y = m(task=CP, outfit_embedding=cu(emb), outfit_mask=cu(mask))
-    (y.squeeze(-1) * up.cuda()).sum().backward()
-    ours = {k: v.grad.detach().cpu() for k, v in trainable(m).items() if v.grad is not None}
+    B = len(n)
+    emb, mask = synth.outfit_batch(4321, B, Lp, n)
+    m = make_model("f16", n_layers=n_layers)
     # plain torch reference of the same op
     t = m.cfg.transformer
     layer = torch.nn.TransformerEncoderLayer(d_model=1024, nhead=t.n_head, dim_feedforward=t.d_ffn, dropout=0.0, batch_first=True,
                                              norm_first=True, activation=torch.nn.functional.mish)
     enc = torch.nn.TransformerEncoder(layer, num_layers=t.n_layers, enable_nested_tensor=False)
     enc.load_state_dict({k: v.detach().cpu() for k, v in m.transformer_encoder.state_dict().items()})
-    tok = m.outfit_token.detach().cpu().clone().requires_grad_(True)
-    w = m.cp_ffn[1].weight.detach().cpu().clone().requires_grad_(True)
-    b = m.cp_ffn[1].bias.detach().cpu().clone().requires_grad_(True)
-    x = torch.cat([tok.view(1, 1, -1).expand(len(n), 1, -1), torch.from_numpy(emb)], 1)
-    km = torch.cat([torch.zeros(len(n), 1, dtype=torch.bool), torch.from_numpy(mask)], 1)
+    km = torch.cat([torch.zeros(B, 1, dtype=torch.bool), torch.from_numpy(mask)], 1)
+    leaf = lambda p: p.detach().cpu().clone().requires_grad_(True)
+
+    def compare(ref):
+        ours = {k: v.grad.detach().cpu() for k, v in trainable(m).items() if v.grad is not None}
+        ref.update({"transformer_encoder." + k: v.grad for k, v in enc.named_parameters()})
+        assert set(ref) == set(ours)
+        bad = {}
+        for k in ref:
+            e = nrm((ours[k] - ref[k]).numpy()) / max(nrm(ref[k].numpy()), 1e-30)
+            if not e <= 5e-3:
+                bad[k] = e
+        assert not bad, bad
+
+    up = torch.linspace(-1.0, 2.0, B)
+    y = m(task=CP, outfit_embedding=cu(emb), outfit_mask=cu(mask))
+    (y.squeeze(-1) * up.cuda()).sum().backward()
+    tok, w, b = leaf(m.outfit_token), leaf(m.cp_ffn[1].weight), leaf(m.cp_ffn[1].bias)
+    x = torch.cat([tok.view(1, 1, -1).expand(B, 1, -1), torch.from_numpy(emb)], 1)
     out = enc.train()(x, src_key_padding_mask=km)[:, 0]
     ((out @ w.t() + b).squeeze(-1) * up).sum().backward()
-    ref = {"outfit_token": tok.grad, "cp_ffn.1.weight": w.grad, "cp_ffn.1.bias": b.grad}
-    ref.update({"transformer_encoder." + k: v.grad for k, v in enc.named_parameters()})
-    assert set(ref) == set(ours)
-    bad = {}
-    for k in ref:
-        e = nrm((ours[k] - ref[k]).numpy()) / max(nrm(ref[k].numpy()), 1e-30)
-        if not e <= 5e-3:
-            bad[k] = e
-    assert not bad, bad
+    compare({"outfit_token": tok.grad, "cp_ffn.1.weight": w.grad, "cp_ffn.1.bias": b.grad})
+    if n_layers is None:
+        return
+    # CIR head: prefix = [target_item_image_emb | target text], y = row0 Wc^T, a non-uniform upstream gradient
+    m.zero_grad(set_to_none=True)
+    enc.zero_grad(set_to_none=True)
+    txt = synth.unit_rows(4321, "target_text", B, 512)
+    dy = torch.from_numpy(np.random.default_rng(4321).standard_normal((B, 1024)).astype(np.float32))
+    y = m(task=CIR, outfit_embedding=cu(emb), outfit_mask=cu(mask), target_item_text_embedding=cu(txt))
+    (y * dy.cuda()).sum().backward()
+    img, wc = leaf(m.target_item_image_emb), leaf(m.cir_ffn[0].weight)
+    prefix = torch.cat([img.view(1, -1).expand(B, -1), torch.from_numpy(txt)], 1)
+    x = torch.cat([prefix[:, None], torch.from_numpy(emb)], 1)
+    out = enc.train()(x, src_key_padding_mask=km)[:, 0]
+    ((out @ wc.t()) * dy).sum().backward()
+    compare({"target_item_image_emb": img.grad, "cir_ffn.0.weight": wc.grad})
 
 
 def test_fused_focal_loss_and_gradient_vs_golden_and_torch():
