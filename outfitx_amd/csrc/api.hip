@@ -39,6 +39,20 @@ extern "C" int ofx_stream_destroy(ofx_stream stream) {
     return OFX_OK;
 }
 
+// ------------------------------------------------------------------------------- grids
+int device_cu_count() {
+    static int cus[64] = {0};                          // per device ordinal; a benign race writes the same value
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    int& c = cus[dev & 63];
+    if (c == 0) { int v = 0; c = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256; }
+    return c;
+}
+int ofx_persistent_grid(int nwg, int persist, bool has_m_dev) {
+    if (persist < 0) persist = device_cu_count();
+    return (persist && !has_m_dev && nwg > persist) ? persist : nwg;
+}
+
 // ------------------------------------------------------------------------------- profiling
 bool g_ofx_prof_on = false;
 int g_ofx_prof_mask = 0xf;

@@ -52,11 +52,7 @@ __global__ __launch_bounds__(512, 2) void fused_qkv_attn_kernel(FusedK p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
 
-    int bid = blockIdx.x;
-    {
-        const int nx = 8, q = p.nwg / nx, r = p.nwg % nx, x = bid % nx, i = bid / nx;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-    }
+    const int bid = xcd_remap(blockIdx.x, p.nwg);
     // L2 working set (4 MiB per XCD, 32 resident blocks): a unit of 36 consecutive blocks = 6 image groups x HALF the heads
     // (6 activation tiles 2.3 MB + 6 heads' weights 1.8 MB), the next unit the same groups x the other half - the activation
     // tiles are fetched once, the weight halves once per 6 groups (head-fastest over all 12 heads needed all 3.5 MB of weights

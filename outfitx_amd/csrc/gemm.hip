@@ -33,29 +33,10 @@ __global__ __launch_bounds__(256, 2) void gemm_128x128_kernel(KArgs p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
 
-    // XCD-aware bijective remap (blocks b and b+8 share an XCD)
-    int bid = blockIdx.x;
-    {
-        const int nx = 8, q = p.nwg / nx, r = p.nwg % nx, x = bid % nx, i = bid / nx;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-    }
-    // grouped rasterisation: consecutive blocks (= the blocks resident on one XCD at a time) cover
-    // group_m row panels x several column tiles, so BOTH the A panels and the W tiles they touch fit the XCD's 4 MiB L2
     int tm, tn;
-    {
-        const int per_group = p.group_m * p.tiles_n;
-        const int gidx = bid / per_group, first = gidx * p.group_m;
-        const int gm = min(p.group_m, p.tiles_m - first);
-        const int r = bid - gidx * per_group;
-        tm = first + r % gm;
-        tn = r / gm;
-    }
+    grouped_tile(xcd_remap(blockIdx.x, p.nwg), p.group_m, p.tiles_m, p.tiles_n, tm, tn);
     const int m0 = tm * BMT, n0 = tn * BN;
-    if (p.m_dev) {                                      // block-uniform: whole tiles past the live rows leave
-        const int m_live = *p.m_dev;
-        p.M = m_live < p.M ? m_live : p.M;
-        if (m0 >= p.M) return;
-    }
+    if (clamp_live_rows(p.m_dev, p.M, m0)) return;
 
     // ---- LDS-DMA source addressing: each wave moves 4 A-chunks and 4 W-chunks of 1 KiB (8 rows) per k-tile
     const int lrow = lane >> 3, lchk = lane & 7;
@@ -208,7 +189,7 @@ int g_x3_persist = 1;     // ofx_tune(16, v): 1 (default) gemm_x3_kernel launche
 int g_x3_kernel = 1;      // three-product GEMMs (k_mult == 3: A rows [hi | lo | hi], W rows [hi | hi | lo]): 1 = the operand-tiles-loaded-once 256x128 kernel
                           // (gemm_x3.hip) from 192 tiles on, 2 = always, 0 = the K-concatenated single-product kernels; ofx_tune(15, v)
 int g_w2_persist = -1;    // dual-weight kernel: persistent grid size (blocks walk tiles b, b + grid, ...): -1 = one block per CU of the device, 0 = one block per tile, ofx_tune(11, v)
-int g_gemm_kernel = 0;    // 0 auto, 1 force 128x128, 2 force 256x256 (8 waves, 2 stages), 3 force 256x128 (4 waves, register-resident k-tile), 4 force 256x256 ping-pong, 6 force the dual-weight 256x256 kernel for split weights
+int g_gemm_kernel = GEMM_AUTO;    // ofx_tune(2, v): a GemmKind (gemm_common.h) forces that kernel
 
 int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
     OFX_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, OFX_ESHAPE, "gemm: empty problem M=%d N=%d K=%d", g.M, g.N, g.K);
@@ -246,48 +227,47 @@ int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
         return OFX_OK;
     }));
     // big tiles when they still fill the chip, else the 128^2 kernel
-    int kind = g_gemm_kernel == 6 ? 0 : g_gemm_kernel;      // 6 only forces the kernel of split-weight GEMMs; every other GEMM keeps the automatic choice
+    int kind = g_gemm_kernel == GEMM_W2 ? GEMM_AUTO : g_gemm_kernel;      // GEMM_W2 only forces the kernel of split-weight GEMMs; every other GEMM keeps the automatic choice
     if (g.a_wrap) {        // split weights: the dual-weight 256x256 kernel when its grid fills the chip, else the 128x128 kernel with a wrapping A index
         const long t2 = (long)((g.M + 255) / 256) * (g.N / 256);
-        kind = (g.K == 2 * g.a_wrap && g.a_wrap % 32 == 0 && g.a_wrap >= 64 && g.N % 256 == 0 && (t2 >= 256 || g_gemm_kernel == 6) && g_gemm_kernel != 1) ? 6 : 1;
+        kind = (g.K == 2 * g.a_wrap && g.a_wrap % 32 == 0 && g.a_wrap >= 64 && g.N % 256 == 0 && (t2 >= 256 || g_gemm_kernel == GEMM_W2) && g_gemm_kernel != GEMM_128) ? GEMM_W2 : GEMM_128;
         // the correction product on the fp8 matrix instruction
-        if (kind == 6 && g.W8 && g.w8_scale && op_dtype == OFX_F16 && g.a_wrap % 128 == 0) kind = 8;
-    } else if (kind == 0) {   // measured crossover points (tools/gemm_bench.py, profiles/r01_gemm_variants.txt)
+        if (kind == GEMM_W2 && g.W8 && g.w8_scale && op_dtype == OFX_F16 && g.a_wrap % 128 == 0) kind = GEMM_W2F8;
+    } else if (kind == GEMM_AUTO) {   // measured crossover points (tools/gemm_bench.py, profiles/r01_gemm_variants.txt)
         const long t2 = (long)((g.M + 255) / 256) * (g.N / 256), t3 = (long)((g.M + 255) / 256) * (g.N / 128);
-        if (g.N % 256 == 0 && t2 >= 1024) kind = g.K <= 1024 ? 4 : 2;   // 256x256, one block per CU (short K: the ping-pong kernel)
-        else if (g.N % 128 == 0 && t3 >= 512) kind = 3;                    // short K / mid-size M: 256x128, two blocks per CU
-        else kind = 1;
+        if (g.N % 256 == 0 && t2 >= 1024) kind = g.K <= 1024 ? GEMM_PP : GEMM_256;   // 256x256, one block per CU (short K: the ping-pong kernel)
+        else if (g.N % 128 == 0 && t3 >= 512) kind = GEMM_256x128;                  // short K / mid-size M: 256x128, two blocks per CU
+        else kind = GEMM_128;
     }
-    if (g.k_mult == 3 && !g.a_wrap && g_x3_kernel && (g_gemm_kernel == 0 || g_gemm_kernel == 6) && g.K % 96 == 0 && g.N % 128 == 0 && g.lda >= g.K &&
+    if (g.k_mult == 3 && !g.a_wrap && g_x3_kernel && (g_gemm_kernel == GEMM_AUTO || g_gemm_kernel == GEMM_W2) && g.K % 96 == 0 && g.N % 128 == 0 && g.lda >= g.K &&
         (g_x3_kernel >= 2 || (long)((g.M + 255) / 256) * (g.N / 128) >= 192))
-        kind = 9;                  // the three products from ONE copy of each operand tile
-    if ((kind == 2 || kind == 4) && g.N % 256) kind = 1;
-    if (kind == 5 && g.N % 128) kind = 1;
-    // record label: logical shape (K without the split-weight / three-product concatenation), the K multiplier and
-    // kernel kind (1 128x128 [+ split-K / 64-row variants], 2 256x256, 3 256x128, 4 256x256 ping-pong, 6 dual-weight 256x256, 8 the same with the fp8 correction product, 9 three-product 256x128 with the operand tiles loaded once)
+        kind = GEMM_X3;            // the three products from ONE copy of each operand tile
+    if ((kind == GEMM_256 || kind == GEMM_PP) && g.N % 256) kind = GEMM_128;
+    if (kind == GEMM_64 && g.N % 128) kind = GEMM_128;
+    // record label: logical shape (K without the split-weight / three-product concatenation), the K multiplier and the GemmKind
     if (g_ofx_prof_on) {
         const int km = g.a_wrap ? g.K / g.a_wrap : (g.k_mult > 0 ? g.k_mult : 1);
         // algorithmic HBM bytes of this launch: A once (its k index wraps over a_wrap columns for split weights), the weight rows as
         // stored, and per output element what the configured epilogue moves: fp32 4 (+4 residual read), operand type 2 (in-place
         // (hi, lo) stream: 4 read + 4 written), [hi | lo | hi] 6, +4 pre-activation tape copy
-        const double ab = kind == 9 ? 2.0 * g.M * (g.K / 3) * 2 : 2.0 * g.M * (g.a_wrap ? g.a_wrap : g.K), wb = kind == 8 ? 3.0 * g.N * g.a_wrap : (kind == 9 ? 2.0 * g.N * (g.K / 3) * 2 : 2.0 * g.N * g.K);      // kind 8 reads the hi rows (2 B) + the fp8 lo rows (1 B)
+        const double ab = kind == GEMM_X3 ? 2.0 * g.M * (g.K / 3) * 2 : 2.0 * g.M * (g.a_wrap ? g.a_wrap : g.K), wb = kind == GEMM_W2F8 ? 3.0 * g.N * g.a_wrap : (kind == GEMM_X3 ? 2.0 * g.N * (g.K / 3) * 2 : 2.0 * g.N * g.K);      // GEMM_W2F8 reads the hi rows (2 B) + the fp8 lo rows (1 B)
         double ob = g.out_kind == 0 ? 4.0 : (g.out_kind == 2 ? 6.0 : 2.0);
         if (g.xlo) ob = 8.0;
         else if (g.resid) ob += 4.0;
         if (g.aux_out) ob += 4.0;
         ofx_prof_set_tag(g.M, g.N, g.K / km, kind, km, ab + wb + ob * g.M * g.N);
     }
-    // executed FLOPs in f16-rate equivalents: the fp8 correction product of kind 8 runs at twice the f16 rate (1.5 products, not 2)
-    ProfScope prof(PROF_GEMM, s, 2.0 * g.M * g.N * g.K * (kind == 8 ? 0.75 : 1.0), true);      // events ride on the launches (OFX_PLAUNCH)
-    if (kind == 2 || kind == 3 || kind == 4 || kind == 6 || kind == 8 || kind == 9) {
-        k.group_m = kind == 3 ? 4 : 8;
+    // executed FLOPs in f16-rate equivalents: the fp8 correction product of GEMM_W2F8 runs at twice the f16 rate (1.5 products, not 2)
+    ProfScope prof(PROF_GEMM, s, 2.0 * g.M * g.N * g.K * (kind == GEMM_W2F8 ? 0.75 : 1.0), true);      // events ride on the launches (OFX_PLAUNCH)
+    if (gemm_kind_big_tile(kind)) {
+        k.group_m = kind == GEMM_256x128 ? 4 : 8;
         int rc;
-        if (kind == 8) {
+        if (kind == GEMM_W2F8) {
             k.W8 = (const char*)g.W8; k.w8_scale = (const char*)g.w8_scale; rc = ofx_gemm_launch_w2f8(&k, g.M, g.N, s);
         }
-        else if (kind == 9) rc = ofx_gemm_launch_x3(&k, op_dtype, g.M, g.N, s);
-        else if (kind == 6) rc = ofx_gemm_launch_w2(&k, op_dtype, g.M, g.N, s);
-        else if (kind == 4) rc = ofx_gemm_launch_pp(&k, op_dtype, g.M, g.N, s);
+        else if (kind == GEMM_X3) rc = ofx_gemm_launch_x3(&k, op_dtype, g.M, g.N, s);
+        else if (kind == GEMM_W2) rc = ofx_gemm_launch_w2(&k, op_dtype, g.M, g.N, s);
+        else if (kind == GEMM_PP) rc = ofx_gemm_launch_pp(&k, op_dtype, g.M, g.N, s);
         else rc = ofx_gemm_launch_big(&k, kind, op_dtype, g.M, g.N, s);
         if (rc != OFX_OK) return rc;
     } else {
@@ -297,9 +277,9 @@ int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
         gm = gm < 1 ? 1 : (gm > 8 ? 8 : gm);
         k.group_m = gm;
         const bool can_split = g.slab && !producer && !g.row_stat;
-        const bool can64 = (kind == 5) || (kind == 1 && g_gemm_kernel == 0 && g.M > 64 && (long)k.tiles_m * k.tiles_n <= 384);
+        const bool can64 = (kind == GEMM_64) || (kind == GEMM_128 && g_gemm_kernel == GEMM_AUTO && g.M > 64 && (long)k.tiles_m * k.tiles_n <= 384);
         SmallPlan pl = plan_small(g.M, g.N, g.K, can_split, can64);
-        if (kind == 5) pl.tile64 = 1;
+        if (kind == GEMM_64) pl.tile64 = 1;
         const int splits = pl.splits;
         k.splits = splits; k.slab = (float*)g.slab; k.m_slab = g.M;
         k.kt_per_split = splits > 1 ? (g.K / BK + splits - 1) / splits : 0;

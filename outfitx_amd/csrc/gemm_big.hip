@@ -18,26 +18,10 @@ __global__ __launch_bounds__(64 * WR * WC, 2) void gemm_big_kernel(KArgs p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave / WC, wc = wave % WC;
 
-    int bid = blockIdx.x;
-    {
-        const int nx = 8, q = p.nwg / nx, r = p.nwg % nx, x = bid % nx, i = bid / nx;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-    }
     int tm, tn;
-    {
-        const int per_group = p.group_m * p.tiles_n;
-        const int gidx = bid / per_group, first = gidx * p.group_m;
-        const int gm = min(p.group_m, p.tiles_m - first);
-        const int r = bid - gidx * per_group;
-        tm = first + r % gm;
-        tn = r / gm;
-    }
+    grouped_tile(xcd_remap(blockIdx.x, p.nwg), p.group_m, p.tiles_m, p.tiles_n, tm, tn);
     const int m0 = tm * TM, n0 = tn * TN;
-    if (p.m_dev) {
-        const int m_live = *p.m_dev;
-        p.M = m_live < p.M ? m_live : p.M;
-        if (m0 >= p.M) return;
-    }
+    if (clamp_live_rows(p.m_dev, p.M, m0)) return;
 
     // LDS-DMA: chunks of 1 KiB = 8 rows x 128 B, swizzle on the source address
     const int lrow = lane >> 3, lchk = lane & 7;
@@ -137,10 +121,7 @@ static int launch_big(KArgs& k, int M, int N, hipStream_t s) {
     constexpr int TM = WR * 128, TN = WC * 64, NW = WR * WC;
     constexpr int LDSB = NST * (TM + TN) * BK * 2 + NW * EPI2_BYTES_PER_WAVE;
     static DeviceOnce attr;
-    TRY(attr.run([]() -> int {
-        OFX_HIP(hipFuncSetAttribute((const void*)gemm_big_kernel<T, WR, WC, NST>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-        return OFX_OK;
-    }));
+    TRY(set_max_dynamic_lds(attr, gemm_big_kernel<T, WR, WC, NST>, LDSB));
     k.tiles_n = N / TN; k.tiles_m = (M + TM - 1) / TM; k.nwg = k.tiles_m * k.tiles_n;
     OFX_PLAUNCH(true, (gemm_big_kernel<T, WR, WC, NST>), dim3(k.nwg), dim3(64 * NW), LDSB, s, k);
     return OFX_OK;
@@ -150,6 +131,6 @@ static int launch_big(KArgs& k, int M, int N, hipStream_t s) {
 
 int ofx_gemm_launch_big(void* kargs, int kind, int op_dtype, int M, int N, hipStream_t s) {
     KArgs& k = *(KArgs*)kargs;
-    if (kind == 2) return op_dtype == OFX_F16 ? launch_big<f16_t, 2, 4, 2>(k, M, N, s) : launch_big<bf16_t, 2, 4, 2>(k, M, N, s);
+    if (kind == GEMM_256) return op_dtype == OFX_F16 ? launch_big<f16_t, 2, 4, 2>(k, M, N, s) : launch_big<bf16_t, 2, 4, 2>(k, M, N, s);
     return op_dtype == OFX_F16 ? launch_big<f16_t, 2, 2, 1>(k, M, N, s) : launch_big<bf16_t, 2, 2, 1>(k, M, N, s);
 }

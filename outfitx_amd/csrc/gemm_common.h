@@ -1,11 +1,32 @@
 // Shared pieces of the GEMM translation units (gemm.hip: 128x128 kernel + dispatcher; gemm_big.hip: 256x256 / 256x128 tiles;
-// gemm_pp.hip: ping-pong 256x256; gemm_tn.hip: weight-gradient TN kernel): kernel arguments, the LDS-DMA helper and the fused
-// epilogues.  Everything here has internal linkage (anonymous namespace / templates); the files are split only so that they
-// compile in parallel.
+// gemm_pp.hip: ping-pong 256x256; gemm_w2.hip: dual-weight 256x256; gemm_w2f8.hip: the same with the fp8 correction product;
+// gemm_x3.hip: three-product 256x128; gemm_tn.hip: weight-gradient TN kernel) and of fused_qkv_attn.hip, which borrows the tile
+// constants and the block remap: the kernel kinds, kernel arguments, the tile walk (gemm_walk.h), the live-row clamp, the LDS-DMA
+// helpers and the fused epilogues.  Everything here has internal linkage (anonymous namespace / templates); the files are split only
+// so that they compile in parallel.
 #pragma once
 #include <type_traits>
 
+#include "gemm_walk.h"
 #include "ofx_common.h"
+
+// The NT GEMM kernels by number.  The same numbers are the values of ofx_tune(2, v) (g_gemm_kernel: 0 = the automatic choice; 6 forces
+// only the kernel of split-weight GEMMs) and the `kind` of the profile records (include/ofx.h), where 7 - no dispatcher kind - labels
+// the fused QKV projection + attention launch of fused_qkv_attn.hip.
+//   kind   tile      kernel                 notes
+//   1      128x128   gemm_128x128_kernel    4 waves; carries the split-K plans and, planned or forced, the 64-row variant
+//   2      256x256   gemm_big_kernel        8 waves, two LDS stages
+//   3      256x128   gemm_big_kernel        4 waves, register-resident k-tile, two blocks per CU
+//   4      256x256   gemm_pp_kernel         ping-pong wave groups (short K)
+//   5      64x128    gemm_128x128_kernel    the 64-row variant, forced (ofx_tune only)
+//   6      256x256   gemm_w2_kernel         dual weight [hi | lo] against one copy of A
+//   8      256x256   gemm_w2f8_kernel       kind 6 with the correction product on the fp8 matrix instruction (never forced: chosen from 6)
+//   9      256x128   gemm_x3_kernel         three products with the operand tiles loaded once (never forced: ofx_tune(15, v))
+enum GemmKind { GEMM_AUTO = 0, GEMM_128 = 1, GEMM_256 = 2, GEMM_256x128 = 3, GEMM_PP = 4, GEMM_64 = 5, GEMM_W2 = 6, GEMM_W2F8 = 8, GEMM_X3 = 9 };
+// the big-tile kernels live in their own translation units behind the ofx_gemm_launch_* functions at the end of this file
+inline bool gemm_kind_big_tile(int kind) {
+    return kind == GEMM_256 || kind == GEMM_256x128 || kind == GEMM_PP || kind == GEMM_W2 || kind == GEMM_W2F8 || kind == GEMM_X3;
+}
 
 namespace {
 
@@ -41,7 +62,27 @@ struct KArgs {
 __device__ __forceinline__ void glds16(const char* g, OFX_LDS char* l) {
     __builtin_amdgcn_global_load_lds((const OFX_GLB void*)g, (OFX_LDS void*)l, 16, 0, 0);
 }
+// LDS-DMA through a buffer resource: 16 bytes per lane from base + voff (per lane) + soff (uniform) to lds + 16 lane; against
+// global_load_lds this needs no 64-bit per-lane address (one VGPR offset that never changes + a scalar step offset)
+__device__ __forceinline__ void bload16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, OFX_LDS char* l) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (OFX_LDS void*)l, 16, (int)voff, (int)soff, 0, 0);
+}
+// (reads past `bytes` return zeros and stores past it are dropped: the A resource of a tile ends with the matrix, so rows beyond M
+// need no clamping)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const char* base, size_t bytes = 0x7fffffff) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)(bytes < 0x7fffffff ? bytes : 0x7fffffff), 0x00020000);
+}
 
+// Device-side live row count (KArgs::m_dev, pad-free varlen sets): M, the launch's upper bound, is clamped to it.  Returns whether
+// the tile whose first row is m0 then lies wholly past the live rows - block-uniform, such a block leaves at once.
+__device__ __forceinline__ bool clamp_live_rows(const int* m_dev, int& M, int m0 = 0) {
+    if (m_dev) {
+        const int m_live = *m_dev;
+        M = m_live < M ? m_live : M;
+        if (m0 >= M) return true;
+    }
+    return false;
+}
 
 // One wave drains its 64x64 fp32 sub-tile from LDS as whole row segments: 16 lanes x 16 B per row.
 template <typename T, int ACT>
@@ -346,8 +387,7 @@ __device__ __forceinline__ void epilogue_direct(const KArgs& p, f32x4 (&acc)[NP]
         *(OFX_LDS f32x4*)(st + 4 * lane) = pr;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
-    const size_t cbytes = (size_t)p.M * p.ldc * 2;
-    const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void*)p.C, 0, (int)(cbytes < 0x7fffffff ? cbytes : 0x7fffffff), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rc = make_rsrc(p.C, (size_t)p.M * p.ldc * 2);
     // this lane's bytes of pass 0, column-block pair 0: row gm0 + fr, column gn0 + (fq & 1) 16 + (fq >> 1) 8
     const unsigned vo = ((unsigned)(gm0 + fr) * (unsigned)p.ldc + (unsigned)(gn0 + (fq & 1) * 16 + (fq >> 1) * 8)) * 2u;
     const unsigned pass_bytes = 16u * (unsigned)p.ldc * 2u;

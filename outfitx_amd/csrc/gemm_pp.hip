@@ -21,26 +21,10 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(KArgs p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
 
-    int bid = blockIdx.x;
-    {
-        const int nx = 8, q = p.nwg / nx, r = p.nwg % nx, x = bid % nx, i = bid / nx;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-    }
     int tm, tn;
-    {
-        const int per_group = p.group_m * p.tiles_n;
-        const int gidx = bid / per_group, first = gidx * p.group_m;
-        const int gm = min(p.group_m, p.tiles_m - first);
-        const int r = bid - gidx * per_group;
-        tm = first + r % gm;
-        tn = r / gm;
-    }
+    grouped_tile(xcd_remap(blockIdx.x, p.nwg), p.group_m, p.tiles_m, p.tiles_n, tm, tn);
     const int m0 = tm * TM, n0 = tn * TN;
-    if (p.m_dev) {
-        const int m_live = *p.m_dev;
-        p.M = m_live < p.M ? m_live : p.M;
-        if (m0 >= p.M) return;
-    }
+    if (clamp_live_rows(p.m_dev, p.M, m0)) return;
 
     const int lrow = lane >> 3, lchk = lane & 7;
     const char* a_base = p.A + (size_t)m0 * p.lda * 2;
@@ -154,10 +138,7 @@ template <typename T>
 static int launch_pp(KArgs& k, int M, int N, hipStream_t s) {
     constexpr int LDSB = 2 * (256 + 256) * BK * 2 + 8 * EPI2_BYTES_PER_WAVE;
     static DeviceOnce attr;
-    TRY(attr.run([]() -> int {
-        OFX_HIP(hipFuncSetAttribute((const void*)gemm_pp_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-        return OFX_OK;
-    }));
+    TRY(set_max_dynamic_lds(attr, gemm_pp_kernel<T>, LDSB));
     k.tiles_n = N / 256; k.tiles_m = (M + 255) / 256; k.nwg = k.tiles_m * k.tiles_n;
     OFX_PLAUNCH(true, (gemm_pp_kernel<T>), dim3(k.nwg), dim3(512), LDSB, s, k);
     return OFX_OK;

@@ -33,23 +33,11 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_kernel(TnArgs p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
 
-    int bid = blockIdx.x;
-    {
-        const int nx = 8, q = p.nwg / nx, r = p.nwg % nx, x = bid % nx, i = bid / nx;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-    }
+    const int bid = xcd_remap(blockIdx.x, p.nwg);
     const int tiles = p.tiles_m * p.tiles_n;
-    const int split = bid / tiles;
+    const int split = bid / tiles;                       // the split index is peeled first: each split walks the tiles in the same order
     int tm, tn;
-    {
-        const int t = bid - split * tiles;
-        const int per_group = p.group_m * p.tiles_n;
-        const int gidx = t / per_group, first = gidx * p.group_m;
-        const int gm = min(p.group_m, p.tiles_m - first);
-        const int r = t - gidx * per_group;
-        tm = first + r % gm;
-        tn = r / gm;
-    }
+    grouped_tile(bid - split * tiles, p.group_m, p.tiles_m, p.tiles_n, tm, tn);
     const int m0 = tm * 256, n0 = tn * 256;
     int K = p.K;
     if (p.k_dev) { const int kl = *p.k_dev; K = kl < K ? kl : K; }

@@ -37,10 +37,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w2_kernel(KArgs p) {
     const int wr = wave >> 2, wc = wave & 3;
     const int Kh = p.K >> 1;                           // logical K; 2 Kh is the row stride of W = [hi | lo]
     p.K = Kh;                                          // the epilogues never read K; keep the logical value anyway
-    if (p.m_dev) {                                     // device-side live row count: the launcher runs one block per tile then
-        const int m_live = *p.m_dev;
-        p.M = m_live < p.M ? m_live : p.M;
-    }
+    clamp_live_rows(p.m_dev, p.M);                     // device-side live row count: the launcher runs one block per tile then
 
     // Persistent over tiles: block b runs tiles b, b + gridDim.x, ... (the launcher sizes the grid to one block per CU, or one block
     // per tile on small problems).  The k-steps are numbered across the block's tiles - step g lives in stage g % 3 - so the two fills
@@ -48,17 +45,10 @@ __global__ __launch_bounds__(512, 2) void gemm_w2_kernel(KArgs p) {
     // under the epilogue, whose staging sits in the stage of the tile's last step (the one stage no fill targets), and the next main
     // loop starts without a load-latency bubble.
     auto map_tile = [&](int vb, int& m0, int& n0) {
-        int bid = vb;
-        {
-            const int nx = 8, q = p.nwg / nx, r = p.nwg % nx, x = bid % nx, i = bid / nx;
-            bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-        }
-        const int per_group = p.group_m * p.tiles_n;
-        const int gidx = bid / per_group, first = gidx * p.group_m;
-        const int gm = min(p.group_m, p.tiles_m - first);
-        const int r = bid - gidx * per_group;
-        m0 = (first + r % gm) * TM;
-        n0 = (r / gm) * TN;
+        int tm, tn;
+        grouped_tile(xcd_remap(vb, p.nwg), p.group_m, p.tiles_m, p.tiles_n, tm, tn);
+        m0 = tm * TM;
+        n0 = tn * TN;
     };
     const unsigned lo_bytes = (unsigned)Kh * 2;
     const int nk = Kh / BK2;
@@ -219,22 +209,9 @@ template <typename T>
 static int launch_w2(KArgs& k, int M, int N, hipStream_t s) {
     constexpr int LDSB = 3 * 3 * 256 * 32 * 2;          // 144 KiB
     static DeviceOnce attr;
-    TRY(attr.run([]() -> int {
-        OFX_HIP(hipFuncSetAttribute((const void*)gemm_w2_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-        return OFX_OK;
-    }));
+    TRY(set_max_dynamic_lds(attr, gemm_w2_kernel<T>, LDSB));
     k.tiles_n = N / 256; k.tiles_m = (M + 255) / 256; k.nwg = k.tiles_m * k.tiles_n;
-    // one block per CU, each walking tiles b, b + grid, ... (g_w2_persist: -1 = the device's CU count, 0 = one block per tile, n = n blocks)
-    int persist = g_w2_persist;
-    if (persist < 0) {
-        static int cus[64] = {0};                      // per device ordinal; a benign race writes the same value
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        int& c = cus[dev & 63];
-        if (c == 0) { int v = 0; c = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256; }
-        persist = c;
-    }
-    const int grid = (persist && !k.m_dev && k.nwg > persist) ? persist : k.nwg;
+    const int grid = ofx_persistent_grid(k.nwg, g_w2_persist, k.m_dev != nullptr);
     OFX_PLAUNCH(true, (gemm_w2_kernel<T>), dim3(grid), dim3(512), LDSB, s, k);
     return OFX_OK;
 }

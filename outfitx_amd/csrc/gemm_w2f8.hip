@@ -53,16 +53,6 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef short i16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
-// LDS-DMA through a buffer resource: 16 bytes per lane from base + voff (per lane) + soff (uniform) to lds + 16 lane; against
-// global_load_lds this needs no 64-bit per-lane address (one VGPR offset that never changes + a scalar step offset)
-__device__ __forceinline__ void bload16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, OFX_LDS char* l) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (OFX_LDS void*)l, 16, (int)voff, (int)soff, 0, 0);
-}
-// (reads past `bytes` return zeros: the A resource of a tile ends with the matrix, so rows beyond M need no clamping)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const char* base, size_t bytes = 0x7fffffff) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)(bytes < 0x7fffffff ? bytes : 0x7fffffff), 0x00020000);
-}
-
 __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
     typedef f16_t T;
     typedef OpT<T>::v8 v8;
@@ -77,22 +67,12 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
     asm volatile("" : "+s"(grp));            // an opaque scalar: re-deriving it from threadIdx.x later costs a scratch reload, which drains the DMA queue
     const int Kh = p.K >> 1;                           // logical K; 2 Kh is the row stride (elements) of W = [hi | lo]
     p.K = Kh;
-    if (p.m_dev) {
-        const int m_live = *p.m_dev;
-        p.M = m_live < p.M ? m_live : p.M;
-    }
+    clamp_live_rows(p.m_dev, p.M);
     auto map_tile = [&](int vb, int& m0, int& n0) {
-        int bid = vb;
-        {
-            const int nx = 8, q = p.nwg / nx, r = p.nwg % nx, x = bid % nx, i = bid / nx;
-            bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-        }
-        const int per_group = p.group_m * p.tiles_n;
-        const int gidx = bid / per_group, first = gidx * p.group_m;
-        const int gm = min(p.group_m, p.tiles_m - first);
-        const int r = bid - gidx * per_group;
-        m0 = (first + r % gm) * TM;
-        n0 = (r / gm) * TN;
+        int tm, tn;
+        grouped_tile(xcd_remap(vb, p.nwg), p.group_m, p.tiles_m, p.tiles_n, tm, tn);
+        m0 = tm * TM;
+        n0 = tn * TN;
     };
     const int nk = Kh / BK2, nsup = nk >> 2;
     const int dst0 = wave * 2 * 1024;
@@ -361,22 +341,10 @@ int ofx_gemm_launch_w2f8(void* kargs, int M, int N, hipStream_t s) {
     KArgs& k = *(KArgs*)kargs;
     constexpr int LDSB = 4 * 2 * 256 * 32 * 2 + 256 * 128;              // 128 KiB of stages + the 32 KiB fp8 weight buffer = 160 KiB
     static DeviceOnce attr;
-    TRY(attr.run([]() -> int {
-        OFX_HIP(hipFuncSetAttribute((const void*)gemm_w2f8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-        return OFX_OK;
-    }));
+    TRY(set_max_dynamic_lds(attr, gemm_w2f8_kernel, LDSB));
     k.tiles_n = N / 256; k.tiles_m = (M + 255) / 256; k.nwg = k.tiles_m * k.tiles_n;
     k.epi_direct = g_epi_direct;
-    int persist = g_w2_persist;
-    if (persist < 0) {
-        static int cus[64] = {0};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        int& c = cus[dev & 63];
-        if (c == 0) { int v = 0; c = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256; }
-        persist = c;
-    }
-    const int grid = (persist && !k.m_dev && k.nwg > persist) ? persist : k.nwg;
+    const int grid = ofx_persistent_grid(k.nwg, g_w2_persist, k.m_dev != nullptr);
     OFX_PLAUNCH(true, gemm_w2f8_kernel, dim3(grid), dim3(512), LDSB, s, k);
     return OFX_OK;
 }

@@ -11,18 +11,11 @@
 // [A_hi 256 rows | A_lo 256 rows | W_hi 128 rows | W_lo 128 rows] x 64 B; per k-step and wave 6 LDS-DMA pieces (2 + 2 + 1 + 1), 16
 // fragment reads and 48 MFMAs.  Schedule, swizzle and persistence are gemm_w2.hip's: two wave groups one barrier slot apart, step t + 2
 // issued in iteration t, counted vmcnt(6), blocks walk tiles b, b + grid, ... with the next tile's first two steps fetched under
-// the epilogue; LDS-DMA through buffer resources as in gemm_w2f8.hip (rows past M read zeros).
+// the epilogue; LDS-DMA through buffer resources (bload16 / make_rsrc, gemm_common.h: rows past M read zeros).
 #include "gemm_common.h"
 
 extern int g_w2_persist, g_x3_persist;
 namespace {
-
-__device__ __forceinline__ void x3_bload16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, OFX_LDS char* l) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (OFX_LDS void*)l, 16, (int)voff, (int)soff, 0, 0);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t x3_rsrc(const char* base, size_t bytes = 0x7fffffff) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)(bytes < 0x7fffffff ? bytes : 0x7fffffff), 0x00020000);
-}
 
 template <typename T>
 __global__ __launch_bounds__(512, 2) void gemm_x3_kernel(KArgs p) {
@@ -37,22 +30,12 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_kernel(KArgs p) {
     asm volatile("" : "+s"(grp));
     const int Kl = p.K / 3;                             // logical depth; A rows are [hi | lo | hi] (3 Kl), W rows [hi | hi | lo]
     p.K = Kl;
-    if (p.m_dev) {                                      // device-side live row count: the launcher runs one block per tile then
-        const int m_live = *p.m_dev;
-        p.M = m_live < p.M ? m_live : p.M;
-    }
+    clamp_live_rows(p.m_dev, p.M);                      // device-side live row count: the launcher runs one block per tile then
     auto map_tile = [&](int vb, int& m0, int& n0) {
-        int bid = vb;
-        {
-            const int nx = 8, q = p.nwg / nx, r = p.nwg % nx, x = bid % nx, i = bid / nx;
-            bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-        }
-        const int per_group = p.group_m * p.tiles_n;
-        const int gidx = bid / per_group, first = gidx * p.group_m;
-        const int gm = min(p.group_m, p.tiles_m - first);
-        const int r = bid - gidx * per_group;
-        m0 = (first + r % gm) * TM;
-        n0 = (r / gm) * TN;
+        int tm, tn;
+        grouped_tile(xcd_remap(vb, p.nwg), p.group_m, p.tiles_m, p.tiles_n, tm, tn);
+        m0 = tm * TM;
+        n0 = tn * TN;
     };
     const int nk = Kl / BK2;
     const unsigned a_lo_off = (unsigned)Kl * 2, w_lo_off = (unsigned)Kl * 4;      // byte offsets of the lo column blocks in a row
@@ -79,18 +62,18 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_kernel(KArgs p) {
         int m1 = m0, n1 = n0;                           // the next tile (the block's last tile re-fills its own first steps: nobody reads them)
         if (has_next) map_tile(vb + (int)gridDim.x, m1, n1);
         const size_t a_row = (size_t)p.lda * 2, w_row = (size_t)Kl * 6;
-        const __amdgpu_buffer_rsrc_t r_a = x3_rsrc(p.A + (size_t)m0 * a_row, (size_t)(p.M - m0) * a_row), r_w = x3_rsrc(p.W + (size_t)n0 * w_row);
-        const __amdgpu_buffer_rsrc_t r_a1 = x3_rsrc(p.A + (size_t)m1 * a_row, (size_t)(p.M - m1) * a_row), r_w1 = x3_rsrc(p.W + (size_t)n1 * w_row);
+        const __amdgpu_buffer_rsrc_t r_a = make_rsrc(p.A + (size_t)m0 * a_row, (size_t)(p.M - m0) * a_row), r_w = make_rsrc(p.W + (size_t)n0 * w_row);
+        const __amdgpu_buffer_rsrc_t r_a1 = make_rsrc(p.A + (size_t)m1 * a_row, (size_t)(p.M - m1) * a_row), r_w1 = make_rsrc(p.W + (size_t)n1 * w_row);
         // k-step x of the tile walk (x >= nk: step x - nk of the next tile): A_hi, A_lo (2 pieces each), W_hi, W_lo (1 each)
         auto issue_step = [&](int x) {
             OFX_LDS char* stg = lds + ((base + x) % NST) * STAGE;
             const bool nx = x >= nk;
             const __amdgpu_buffer_rsrc_t ra = nx ? r_a1 : r_a, rw = nx ? r_w1 : r_w;
             const unsigned koff = (unsigned)(nx ? x - nk : x) * BK2 * 2;
-            x3_bload16(ra, a_off[0], koff, stg + wave * 2048); x3_bload16(ra, a_off[1], koff, stg + wave * 2048 + 1024);
-            x3_bload16(ra, a_off[0], koff + a_lo_off, stg + PA + wave * 2048); x3_bload16(ra, a_off[1], koff + a_lo_off, stg + PA + wave * 2048 + 1024);
-            x3_bload16(rw, w_off, koff, stg + 2 * PA + wave * 1024);
-            x3_bload16(rw, w_off, koff + w_lo_off, stg + 2 * PA + PW + wave * 1024);
+            bload16(ra, a_off[0], koff, stg + wave * 2048); bload16(ra, a_off[1], koff, stg + wave * 2048 + 1024);
+            bload16(ra, a_off[0], koff + a_lo_off, stg + PA + wave * 2048); bload16(ra, a_off[1], koff + a_lo_off, stg + PA + wave * 2048 + 1024);
+            bload16(rw, w_off, koff, stg + 2 * PA + wave * 1024);
+            bload16(rw, w_off, koff + w_lo_off, stg + 2 * PA + PW + wave * 1024);
         };
 
         f32x4 acc[4][4];
@@ -172,21 +155,10 @@ template <typename T>
 static int launch_x3(KArgs& k, int M, int N, hipStream_t s) {
     constexpr int LDSB = 3 * (2 * 256 + 2 * 128) * 32 * 2;          // 144 KiB
     static DeviceOnce attr;
-    TRY(attr.run([]() -> int {
-        OFX_HIP(hipFuncSetAttribute((const void*)gemm_x3_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB));
-        return OFX_OK;
-    }));
+    TRY(set_max_dynamic_lds(attr, gemm_x3_kernel<T>, LDSB));
     k.tiles_n = N / 128; k.tiles_m = (M + 255) / 256; k.nwg = k.tiles_m * k.tiles_n;
-    int persist = g_x3_persist == 1 ? g_w2_persist : 0;            // ofx_tune(16, 0): one block per tile (short-lived blocks: a side stream's GEMM then frees its CUs tile by tile)
-    if (persist < 0) {
-        static int cus[64] = {0};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        int& c = cus[dev & 63];
-        if (c == 0) { int v = 0; c = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256; }
-        persist = c;
-    }
-    const int grid = (persist && !k.m_dev && k.nwg > persist) ? persist : k.nwg;
+    // ofx_tune(16, 0): one block per tile (short-lived blocks: a side stream's GEMM then frees its CUs tile by tile)
+    const int grid = ofx_persistent_grid(k.nwg, g_x3_persist == 1 ? g_w2_persist : 0, k.m_dev != nullptr);
     OFX_PLAUNCH(true, (gemm_x3_kernel<T>), dim3(grid), dim3(512), LDSB, s, k);
     return OFX_OK;
 }

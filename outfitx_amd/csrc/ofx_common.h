@@ -178,6 +178,21 @@ struct DeviceOnce {
         return rc;
     }
 };
+// the common case: one kernel, one limit
+template <typename K>
+int set_max_dynamic_lds(DeviceOnce& once, K kernel, int bytes) {
+    return once.run([&]() -> int {
+        OFX_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        return OFX_OK;
+    });
+}
+
+// CU count of the CURRENT device, cached per device ordinal (256 if the query fails).
+int device_cu_count();
+// Grid of a kernel whose blocks can walk tiles b, b + grid, ... over nwg tiles.  persist: -1 = one block per CU of the current
+// device, 0 = one block per tile, n = n blocks.  A device-side row count (has_m_dev) always takes one block per tile: tiles past
+// the live rows leave at once.  Never more blocks than tiles.
+int ofx_persistent_grid(int nwg, int persist, bool has_m_dev);
 
 struct Bump {                                       // carve a caller-provided workspace
     char* base; size_t cap, off = 0; bool ok = true;

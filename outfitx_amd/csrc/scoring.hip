@@ -409,8 +409,7 @@ size_t ofx_l2_topk_ws(int nq, int np) {
 }
 
 static int dist_grid(int tiles_q, int tiles_p) {
-    static int cus = 0;
-    if (cus == 0) { int dev = 0, v = 0; (void)hipGetDevice(&dev); cus = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256; }
+    const int cus = device_cu_count();
     const int gx = std::max(1, std::min(tiles_p, (2 * cus + tiles_q - 1) / tiles_q));      // two blocks per CU over all panels
     return gx * tiles_q;
 }
