@@ -3,15 +3,12 @@
 // (1) attention_mfma: one wavefront per (sequence, head), whole sequence (S <= 64) in one tile —
 //     CLIP ViT-B/32 (S = 50, 12 heads) and CLIP text (S <= 64, causal ∧ key-padding, 8 heads);
 //     replaces HF CLIPAttention's softmax(QK^T/8 + mask)V (reached from clip_image_encoder.py:74-76,
-//     clip_text_encoder.py:56-58).  S^T = K·Q^T on v_mfma_f32_16x16x32 so a query's scores sit in
-//     one lane quad (wavefront softmax: in-lane + 2 shuffles); the S^T accumulators are re-used
-//     in place as the P operand of O^T = V^T·P^T (k-slot permutation, guide §3), V goes through
-//     LDS once and is read back transposed with ds_read_b64_tr_b16 (160-B rows: conflict-free).
+//     clip_text_encoder.py:56-58).  The wavefront's algorithm and lane maps: attn_wave.h.
 // (2) set_attention: fp32 VALU attention over an outfit's 1 + n items (S <= 32, 16 heads);
 //     replaces nn.MultiheadAttention's SDPA inside nn.TransformerEncoderLayer
 //     (src/models/outfit_x.py:137-140,165-168) with -inf on padded keys realised by pad-free
 //     compaction.  < 0.3 % of the path's FLOPs, kept exact.
-#include "ofx_common.h"
+#include "attn_wave.h"
 
 namespace {
 
@@ -27,13 +24,10 @@ struct AttnK {
     int split3_w;           // > 0: output rows are [hi(W) | lo(W) | hi(W)] (the A operand of a three-product K-concatenated GEMM), W = split3_w
 };
 
-constexpr int V_ROW = 160;                 // bytes per V row in LDS (64 x 2 B + 32 pad): tr-read conflict-free
-
 template <typename T, int NT>   // NT = ceil(S / 16) in {1, 2, 4}: number of 16-row query / key tiles
 __global__ __launch_bounds__(256, 3) void attention_mfma_kernel(AttnK a) {      // 3 blocks per CU: <= 168 registers per lane
     typedef typename OpT<T>::v8 v8;
-    typedef typename OpT<T>::v4 v4;
-    constexpr int KS = (NT + 1) / 2, VROWS = 32 * KS, VT = VROWS * V_ROW;
+    constexpr int KS = attn_ksteps(NT), VROWS = 32 * KS, VT = VROWS * ATTN_V_ROW;
     __shared__ __attribute__((aligned(16))) char smem[4 * VT];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int npairs = a.nseq * a.n_head;
@@ -55,7 +49,7 @@ __global__ __launch_bounds__(256, 3) void attention_mfma_kernel(AttnK a) {      
 #pragma unroll
         for (int e = 0; e < 8; ++e) val[e] = (T)0.0f;
         if (key < S) val = *(const v8*)(base + (size_t)key * a.ld + a.v_off + (lane & 7) * 8);
-        *(OFX_LDS v8*)(vl + key * V_ROW + (lane & 7) * 16) = val;
+        *(OFX_LDS v8*)(vl + key * ATTN_V_ROW + (lane & 7) * 16) = val;
     }
 
     // ---- K (A operand) and Q (B operand) fragments straight from global, rows clamped
@@ -86,17 +80,9 @@ __global__ __launch_bounds__(256, 3) void attention_mfma_kernel(AttnK a) {      
 
     // only_row0: query row 0 alone is wanted (pruned last layers: the CLS row / the set's prefix row) -> only query tile 0 is computed
     const int nu = a.only_row0 ? 1 : NT;
-    // ---- S^T[key][query]: st[t][u][r] = score(query 16u + r16, key 16t + 4q4 + r)
+    // ---- the wave-level core (attn_wave.h): S^T, [causal mask,] softmax -> P fragments, O^T = V^T . P^T and the store
     f32x4 st[NT][NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int u = 0; u < NT; ++u) {
-            if (u >= nu) continue;
-            f32x4 c = {neg[t][0], neg[t][1], neg[t][2], neg[t][3]};      // the mask rides in as the accumulator: -inf + finite = -inf
-            c = OpT<T>::mfma16(kf[t][0], qf[u][0], c);
-            st[t][u] = OpT<T>::mfma16(kf[t][1], qf[u][1], c);
-        }
+    attn_scores<T, NT>(st, kf, qf, neg, nu);
     if (a.causal) {                  // wave-uniform: the ViT never enters
 #pragma unroll
         for (int t = 0; t < NT; ++t)
@@ -106,102 +92,9 @@ __global__ __launch_bounds__(256, 3) void attention_mfma_kernel(AttnK a) {      
                 for (int r = 0; r < 4; ++r)
                     if (16 * t + 4 * q4 + r > 16 * u + r16) st[t][u][r] = -INFINITY;
     }
-
-    // ---- wavefront softmax per query column on the raw scores: p = exp2(s * c - max(s) * c), c = scale * log2 e > 0
-    // (one max, then one fma + v_exp_f32 + add per element); P written back normalised
-    const float sc = a.scale * 1.4426950408889634f;
     v8 pf[NT][KS];
-#pragma unroll
-    for (int u = 0; u < NT; ++u) {
-        if (u >= nu) continue;
-        const int query = 16 * u + r16;
-        float m = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) m = fmaxf(m, st[t][u][r]);
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
-        if (m == -INFINITY) m = 0.f;
-        const float mb = -m * sc;
-        float sum = 0.f;
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(st[t][u][r], sc, mb));      // arguments <= 0: no range fix-up needed
-                st[t][u][r] = e;
-                sum += e;
-            }
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
-        const float inv = __builtin_amdgcn_rcpf(sum);
-        if (a.drop.thresh) {            // dropout on the probabilities (training): same (row, col) counters as the fp32 set kernel
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) st[t][u][r] *= drop_mul(a.drop, pair, query * 32 + 16 * t + 4 * q4 + r);
-        }
-        // P fragment of k-step ks: element j <-> key 16(2ks + (j>>2)) + 4q4 + (j&3)
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pf[u][ks][j] = 2 * ks + (j >> 2) < NT ? (T)(st[(2 * ks + (j >> 2)) % NT][u][j & 3] * inv) : (T)0.0f;
-    }
-
-    // ---- O^T[d][query] = V^T · P^T; V fragments by transposed LDS reads (EXEC is all ones here)
-    f32x4 ot[4][NT];
-#pragma unroll
-    for (int nd = 0; nd < 4; ++nd) {
-        v8 vf[KS];
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2) {
-                const int key0 = 32 * ks + 16 * h2 + 4 * q4;
-                // d <-> MFMA row permutation: row m = r16 of tile nd carries d = 16 (m >> 2) + 4 nd + (m & 3), so after the MFMA a
-                // lane's 16 outputs of one query are 16 CONSECUTIVE columns (one 32-byte run per lane, 128 B per lane quad)
-                OFX_LDS s16x4* ap = (OFX_LDS s16x4*)(vl + (key0 + (r16 >> 2)) * V_ROW + (16 * (r16 & 3) + 4 * nd) * 2);
-                const s16x4 tr = __builtin_amdgcn_ds_read_tr16_b64_v4i16(ap);
-                const v4 trv = __builtin_bit_cast(v4, tr);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) vf[ks][4 * h2 + e] = trv[e];
-            }
-#pragma unroll
-        for (int u = 0; u < NT; ++u) {
-            if (u >= nu) continue;
-            f32x4 c = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) c = OpT<T>::mfma16(vf[ks], pf[u][ks], c);
-            ot[nd][u] = c;
-        }
-    }
-
-    // ---- store: ot[nd][u][r] = O[query 16u + r16][d = 16 q4 + 4 nd + r]: two 16-byte stores per lane and query
-    if (live) {
-#pragma unroll
-        for (int u = 0; u < NT; ++u) {
-            if (u >= nu) continue;
-            const int query = 16 * u + r16;
-            if (query < (a.only_row0 ? 1 : S)) {
-                T* op = (T*)a.out + (size_t)(row_first + query) * a.ldo + head * 64 + 16 * q4;
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    v8 o;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) o[e] = (T)ot[2 * h + (e >> 2)][u][e & 3];
-                    *(v8*)(op + 8 * h) = o;
-                    if (a.split3_w) {                                   // wave-uniform
-                        v8 lo;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) lo[e] = (T)(ot[2 * h + (e >> 2)][u][e & 3] - (float)o[e]);
-                        *(v8*)(op + a.split3_w + 8 * h) = lo;
-                        *(v8*)(op + 2 * a.split3_w + 8 * h) = o;
-                    }
-                }
-            }
-        }
-    }
+    attn_softmax_p<T, NT, true>(pf, st, a.scale, nu, a.drop, pair);      // varlen training: dropout on P, row = pair
+    attn_pv_store<T, NT>(vl, pf, nu, live, (T*)a.out, row_first, a.ldo, head * 64, a.only_row0 ? 1 : S, a.split3_w);      // dead waves store nothing
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -381,7 +274,7 @@ template <typename T, int NT>
 __global__ __launch_bounds__(256) void set_attention_bwd_mfma_kernel(AttnBwdK a) {
     typedef typename OpT<T>::v8 v8;
     typedef typename OpT<T>::v4 v4;
-    constexpr int KS = (NT + 1) / 2, VROWS = 32 * KS, VT = VROWS * V_ROW;
+    constexpr int KS = attn_ksteps(NT), VROWS = 32 * KS, VT = VROWS * ATTN_V_ROW;
     __shared__ __attribute__((aligned(16))) char smem[4 * 3 * VT];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int npairs = a.nseq * a.n_head;
@@ -416,9 +309,9 @@ __global__ __launch_bounds__(256) void set_attention_bwd_mfma_kernel(AttnBwdK a)
 #pragma unroll
             for (int e = 0; e < 4; ++e) { gv[e] = (T)g0[e]; gv[4 + e] = (T)g1[e]; }
         }
-        *(OFX_LDS v8*)(kl + row * V_ROW + (lane & 7) * 16) = kv;
-        *(OFX_LDS v8*)(ql + row * V_ROW + (lane & 7) * 16) = qv;
-        *(OFX_LDS v8*)(gl + row * V_ROW + (lane & 7) * 16) = gv;
+        *(OFX_LDS v8*)(kl + row * ATTN_V_ROW + (lane & 7) * 16) = kv;
+        *(OFX_LDS v8*)(ql + row * ATTN_V_ROW + (lane & 7) * 16) = qv;
+        *(OFX_LDS v8*)(gl + row * ATTN_V_ROW + (lane & 7) * 16) = gv;
     }
 
     // ---- row fragments (A or B operand with k = feature): K, Q, V from global (rows clamped), dO converted, zero for dead queries
@@ -549,15 +442,7 @@ __global__ __launch_bounds__(256) void set_attention_bwd_mfma_kernel(AttnBwdK a)
         for (int nd = 0; nd < 4; ++nd) {
             v8 af[KS];
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-                for (int h2 = 0; h2 < 2; ++h2) {
-                    const int row0 = 32 * ks + 16 * h2 + 4 * q4;
-                    OFX_LDS s16x4* ap = (OFX_LDS s16x4*)(img + (row0 + (r16 >> 2)) * V_ROW + (16 * nd + 4 * (r16 & 3)) * 2);
-                    const v4 trv = __builtin_bit_cast(v4, __builtin_amdgcn_ds_read_tr16_b64_v4i16(ap));
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) af[ks][4 * h2 + e] = trv[e];
-                }
+            for (int ks = 0; ks < KS; ++ks) af[ks] = attn_tr_frag<T>(img, 32 * ks, 16 * nd + 4 * (r16 & 3));
 #pragma unroll
             for (int u = 0; u < NT; ++u) {
                 f32x4 c = {0.f, 0.f, 0.f, 0.f};

@@ -10,11 +10,11 @@
 //      offset by one barrier slot), 8 waves x (128 x 48) accumulators;
 //   2. epilogue INTO LDS: (LayerNorm-fold row statistics, column sums,) bias, rounding to the operand type; Q and K as 144-byte
 //      rows, V as 160-byte rows (conflict-free for ds_read_b128 / ds_read_b64_tr_b16) over the now idle stages: "LDS-staged K/V";
-//   3. waves 0 .. G-1 each run one image's attention exactly as attention_mfma_kernel does (S^T = K Q^T on the matrix core, a
-//      query's scores in one lane quad: wavefront softmax; P re-used in place as the operand of O^T = V^T P^T; V by transposed
-//      LDS reads) with every fragment read from LDS, and store the image's [S x 64] output slice.
+//   3. waves 0 .. G-1 each run one image's attention - the wave-level core of attn_wave.h, the one attention_mfma_kernel runs - with
+//      every fragment read from LDS, and store the image's [S x 64] output slice.
 // Block order (bijective XCD remap, then units of 6 image groups x half the heads): the blocks resident on an XCD share six 384 KB
 // activation tiles and six heads' weights (4.1 MB, the size of that XCD's L2).
+#include "attn_wave.h"
 #include "gemm_common.h"
 
 namespace {
@@ -31,9 +31,11 @@ struct FusedK {
 };
 
 constexpr int FQ_TM = 256, FQ_TN = 192, FQ_STAGE = (FQ_TM + FQ_TN) * BK * 2;      // 57344
-constexpr int FQ_QK_ROW = 144, FQ_V_ROW = 160;
+constexpr int FQ_QK_ROW = 144;                                                    // bytes per Q / K row in LDS; V rows: ATTN_V_ROW
+constexpr int FQ_NT = 4;                                                          // 16-row key / query tiles of the attention tail (S <= 64)
+static_assert(FQ_TN == 3 * ATTN_D && 16 * FQ_NT == ATTN_D, "the tail runs the attention core at NT = 4 on one head's 64 q, 64 k and 64 v columns");
 constexpr int FQ_Q_OFF = 0, FQ_K_OFF = FQ_TM * FQ_QK_ROW, FQ_V_OFF = 2 * FQ_TM * FQ_QK_ROW;      // 0, 36864, 73728; V ends at 114688 = 2 stages
-constexpr int FQ_LDS = 2 * FQ_STAGE + 16 * FQ_V_ROW;                               // + 16 zeroed V rows behind the last image (keys S .. 63 of image G-1)
+constexpr int FQ_LDS = 2 * FQ_STAGE + 16 * ATTN_V_ROW;                             // + 16 zeroed V rows behind the last image (keys S .. 63 of image G-1)
 // Dual-weight variant (W2 = true: Wqkv rows are [hi(Wm) | lo(Wm)], the split weights of DESIGN.md section 2): the main loop of
 // gemm_w2.hip - BK = 32, three stages [A 256 rows | W_hi 192 rows | W_lo 192 rows] x 64 B, the two wave groups offset by one barrier
 // slot, 48 MFMAs (8 A fragments x 3 column tiles x {hi, lo}) per wave and step against 14 fragment reads - then the same epilogue
@@ -158,11 +160,11 @@ __global__ __launch_bounds__(512, 2) void fused_qkv_attn_kernel(FusedK p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                           // every stage read and every (clamped) fill is done: the stages become q | k | v
     // the V pad rows lie inside stage 2 here: zero them now (the barrier before the attention publishes them)
-    if (tid < 16 * FQ_V_ROW / 16) *(OFX_LDS f32x4*)(lds + 2 * FQ_STAGE + tid * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (tid < 16 * ATTN_V_ROW / 16) *(OFX_LDS f32x4*)(lds + 2 * FQ_STAGE + tid * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
     } else {
     // ------------------------------------------------------------------ single-product main loop (ping-pong, BK = 64, two stages)
     // zero the V pad rows once (never touched by the stages)
-    if (tid < 16 * FQ_V_ROW / 16) *(OFX_LDS f32x4*)(lds + 2 * FQ_STAGE + tid * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (tid < 16 * ATTN_V_ROW / 16) *(OFX_LDS f32x4*)(lds + 2 * FQ_STAGE + tid * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int lrow = lane >> 3, lchk = lane & 7;
     const char* a_base = p.X + (size_t)m0 * p.ldx * 2;
@@ -279,7 +281,7 @@ __global__ __launch_bounds__(512, 2) void fused_qkv_attn_kernel(FusedK p) {
             f32x4 cs4 = {0.f, 0.f, 0.f, 0.f};
             if (p.row_stat) cs4 = *(const f32x4*)(p.col_sum + gn);
             OFX_LDS char* reg = lds + (which == 0 ? FQ_Q_OFF : which == 1 ? FQ_K_OFF : FQ_V_OFF);
-            const int stride = which == 2 ? FQ_V_ROW : FQ_QK_ROW;
+            const int stride = which == 2 ? ATTN_V_ROW : FQ_QK_ROW;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int row = wr * 128 + i * 16 + fr;
@@ -296,12 +298,12 @@ __global__ __launch_bounds__(512, 2) void fused_qkv_attn_kernel(FusedK p) {
 
     // ---- attention: wave w < n_live_img owns image w of the group (rows w*S ..), head `head`
     if (wave >= n_live_img) return;
-    constexpr int NT = 4, KS = 2;
+    constexpr int NT = FQ_NT;
     const int S = p.S, r0 = wave * S;
     const int r16 = lane & 15, q4 = lane >> 4;
     OFX_LDS char* ql = lds + FQ_Q_OFF + r0 * FQ_QK_ROW;
     OFX_LDS char* kl = lds + FQ_K_OFF + r0 * FQ_QK_ROW;
-    OFX_LDS char* vl = lds + FQ_V_OFF + r0 * FQ_V_ROW;
+    OFX_LDS char* vl = lds + FQ_V_OFF + r0 * ATTN_V_ROW;
     v8 kf[NT][2], qf[NT][2];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
@@ -318,82 +320,12 @@ __global__ __launch_bounds__(512, 2) void fused_qkv_attn_kernel(FusedK p) {
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) neg[t][r] = (16 * t + 4 * q4 + r >= S) ? -INFINITY : 0.f;
+    // the wave-level core (attn_wave.h): every query tile live, no dropout, plain output rows
     f32x4 st[NT][NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int u = 0; u < NT; ++u) {
-            f32x4 c = {neg[t][0], neg[t][1], neg[t][2], neg[t][3]};
-            c = OpT<T>::mfma16(kf[t][0], qf[u][0], c);
-            st[t][u] = OpT<T>::mfma16(kf[t][1], qf[u][1], c);
-        }
-    const float sc = p.scale * 1.4426950408889634f;
-    v8 pf[NT][KS];
-#pragma unroll
-    for (int u = 0; u < NT; ++u) {
-        float m = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) m = fmaxf(m, st[t][u][r]);
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
-        if (m == -INFINITY) m = 0.f;
-        const float mb = -m * sc;
-        float sum = 0.f;
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(st[t][u][r], sc, mb));
-                st[t][u][r] = e;
-                sum += e;
-            }
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
-        const float inv = __builtin_amdgcn_rcpf(sum);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pf[u][ks][j] = (T)(st[2 * ks + (j >> 2)][u][j & 3] * inv);
-    }
-    f32x4 ot[4][NT];
-#pragma unroll
-    for (int nd = 0; nd < 4; ++nd) {
-        v8 vf[KS];
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2) {
-                const int key0 = 32 * ks + 16 * h2 + 4 * q4;
-                OFX_LDS s16x4* ap = (OFX_LDS s16x4*)(vl + (key0 + (r16 >> 2)) * FQ_V_ROW + (16 * (r16 & 3) + 4 * nd) * 2);
-                const v4 trv = __builtin_bit_cast(v4, __builtin_amdgcn_ds_read_tr16_b64_v4i16(ap));
-#pragma unroll
-                for (int e = 0; e < 4; ++e) vf[ks][4 * h2 + e] = trv[e];
-            }
-#pragma unroll
-        for (int u = 0; u < NT; ++u) {
-            f32x4 c = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) c = OpT<T>::mfma16(vf[ks], pf[u][ks], c);
-            ot[nd][u] = c;
-        }
-    }
-    const int row_first = m0 + r0;
-#pragma unroll
-    for (int u = 0; u < NT; ++u) {
-        const int query = 16 * u + r16;
-        if (query < S) {
-            T* op = (T*)p.out + (size_t)(row_first + query) * p.ldo + head * 64 + 16 * q4;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                v8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (T)ot[2 * h + (e >> 2)][u][e & 3];
-                *(v8*)(op + 8 * h) = o;
-            }
-        }
-    }
+    attn_scores<T, NT>(st, kf, qf, neg, NT);
+    v8 pf[NT][attn_ksteps(NT)];
+    attn_softmax_p<T, NT, false>(pf, st, p.scale, NT);
+    attn_pv_store<T, NT>(vl, pf, NT, true, (T*)p.out, m0 + r0, p.ldo, head * 64, S, 0);
 }
 
 }  // namespace

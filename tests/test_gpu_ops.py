@@ -558,8 +558,8 @@ def test_attention_f32_fixed_length_causal_and_key_mask(S, causal, masked):
 @pytest.mark.parametrize("n,S,H", [(1, 50, 12), (5, 50, 12), (13, 50, 12), (7, 64, 4), (9, 33, 2), (8, 41, 2), (13, 43, 2)])
 def test_fused_qkv_projection_attention(fold, dt, n, S, H):
     """The fused QKV-projection + attention kernel (q | k | v staged in LDS only) against (a) the unfused pair ofx_gemm ->
-    ofx_attention on the same operands - the same arithmetic in the same order, so equal to the rounding of q | k | v - and
-    (b) float64 arithmetic on the operand-rounded inputs.  Image counts below, at and above one block's group (5 at S = 50,
+    ofx_attention on the same operands - the same arithmetic in the same order by construction: both kernels run the one
+    wave-level attention core of csrc/attn_wave.h, so equal to the rounding of q | k | v - and (b) float64 arithmetic on the operand-rounded inputs.  Image counts below, at and above one block's group (5 at S = 50,
     ragged tail), sequence lengths at both ends of the supported range, with and without the LayerNorm-fold epilogue."""
     g = np.random.default_rng(n * 7 + S + H + fold)
     W = H * 64
