@@ -346,6 +346,23 @@ int ofx_attention(const void* qkv, void* out, const int64_t* key_mask, int nseq,
                   int ldo, int k_off, int v_off, int mask_ld, int causal, float scale, int op_dtype, ofx_stream stream);
 int ofx_set_attention(const float* qkv, void* out, const int* cu_seqlens, int nseq, int n_head, int D, int ldo,
                       int out_kind, int max_len, int only_row0, float scale, int op_dtype, ofx_stream stream);
+/* The attention kernels of the training step, one call each (both settings of knob 7).  q | k | v and dqkv are operand-type rows [rows, 3 D]
+ * (the tape's layout), sequence b = rows cu_seqlens[b] .. cu_seqlens[b + 1] (1 .. max_len of them, never none), head h at columns 64 h.
+ * Dropout on the attention probabilities is site `site` of (dropout_p, seed): mask element (b * n_head + h, query * 32 + key), the values
+ * ofx_dropout_mask returns for the same arguments; dropout_p = 0 is no dropout, dropout needs max_len <= 32 (OFX_ESHAPE).  NULL pointers,
+ * nseq <= 0 and dropout_p outside [0, 1) are OFX_EINVAL; a refused call launches nothing.
+ *   ofx_attention_varlen: the MFMA forward (knob 7 = 1): out [rows, ldo] operand type; only_row0: query row 0 of every sequence alone
+ *     is computed and stored (row cu_seqlens[b]), the other rows of out are not written.
+ *   ofx_set_attention_op: the VALU forward (knob 7 = 0), ofx_set_attention on operand-type q | k | v.
+ *   ofx_set_attention_bwd: d_o fp32 [rows, D], or [nseq, D] with only_row0 (the gradient of query row 0 of every sequence; the other
+ *     queries have none); dqkv = dq | dk | dv, all rows of every sequence written (dq rows > 0 are zero under only_row0);
+ *     mfma 1 / 0 = the MFMA / the VALU kernel; max_len <= 32. */
+int ofx_attention_varlen(const void* qkv, void* out, const int* cu_seqlens, int nseq, int max_len, int n_head, int ld, int ldo, int k_off,
+                         int v_off, int only_row0, float scale, float dropout_p, unsigned seed, int site, int op_dtype, ofx_stream stream);
+int ofx_set_attention_op(const void* qkv, void* out, const int* cu_seqlens, int nseq, int n_head, int D, int ldo, int out_kind, int max_len,
+                         int only_row0, float scale, float dropout_p, unsigned seed, int site, int op_dtype, ofx_stream stream);
+int ofx_set_attention_bwd(const void* qkv, const float* d_o, void* dqkv, const int* cu_seqlens, int nseq, int n_head, int D, int max_len,
+                          int only_row0, float scale, float dropout_p, unsigned seed, int site, int mfma, int op_dtype, ofx_stream stream);
 /* Fused QKV projection + scaled-dot-product attention of a CLIP ViT layer (HF CLIPAttention's q/k/v_proj + softmax(q k^T * scale) v,
  * reached from clip_image_encoder.py:74-76), q | k | v staged in LDS only: X [nseq * seq_len, ldx] operand type, Wqkv [3 width, width]
  * (q | k | v rows), bias [3 width]; optional LayerNorm-fold consumer inputs row_stat [rows, 2] (mean, rstd) + col_sum [3 width];

@@ -1406,6 +1406,30 @@ extern "C" int ofx_set_attention(const float* qkv, void* out, const int* cu_seql
     SetAttnArgs a{qkv, out, cu_seqlens, nseq, n_head, D, ldo, out_kind, max_len, only_row0, scale};
     return ofx_launch_set_attention(a, op_dtype, (hipStream_t)stream);
 }
+// the training step's attention kernels (either setting of ofx_tune(7, v)), with the dropout site built as the step builds it
+static bool train_attn_args_ok(const void* a, const void* b, const void* c, int nseq, float dropout_p) {
+    return a && b && c && nseq > 0 && dropout_p >= 0.f && dropout_p < 1.f;
+}
+extern "C" int ofx_attention_varlen(const void* qkv, void* out, const int* cu_seqlens, int nseq, int max_len, int n_head, int ld, int ldo, int k_off,
+                                    int v_off, int only_row0, float scale, float dropout_p, unsigned seed, int site, int op_dtype, ofx_stream stream) {
+    OFX_REQUIRE(train_attn_args_ok(qkv, out, cu_seqlens, nseq, dropout_p), OFX_EINVAL, "attention_varlen: bad argument");
+    AttnArgs a{qkv, out, nullptr, nseq, max_len, n_head, ld, ldo, k_off, v_off, 0, 0, scale};
+    a.cu_seqlens = cu_seqlens; a.only_row0 = only_row0 ? 1 : 0; a.drop = make_drop(dropout_p, seed, (unsigned)site);
+    return ofx_launch_attention_mfma(a, op_dtype, (hipStream_t)stream);
+}
+extern "C" int ofx_set_attention_op(const void* qkv, void* out, const int* cu_seqlens, int nseq, int n_head, int D, int ldo, int out_kind, int max_len,
+                                    int only_row0, float scale, float dropout_p, unsigned seed, int site, int op_dtype, ofx_stream stream) {
+    OFX_REQUIRE(train_attn_args_ok(qkv, out, cu_seqlens, nseq, dropout_p) && n_head > 0, OFX_EINVAL, "set_attention_op: bad argument");
+    SetAttnArgs a{qkv, out, cu_seqlens, nseq, n_head, D, ldo, out_kind, max_len, only_row0 ? 1 : 0, scale};
+    a.drop = make_drop(dropout_p, seed, (unsigned)site); a.qkv_op = 1;
+    return ofx_launch_set_attention(a, op_dtype, (hipStream_t)stream);
+}
+extern "C" int ofx_set_attention_bwd(const void* qkv, const float* d_o, void* dqkv, const int* cu_seqlens, int nseq, int n_head, int D, int max_len,
+                                     int only_row0, float scale, float dropout_p, unsigned seed, int site, int mfma, int op_dtype, ofx_stream stream) {
+    OFX_REQUIRE(train_attn_args_ok(qkv, d_o, dqkv, nseq, dropout_p) && cu_seqlens && n_head > 0, OFX_EINVAL, "set_attention_bwd: bad argument");
+    const auto launch = mfma ? ofx_launch_set_attention_bwd_mfma : ofx_launch_set_attention_bwd;
+    return launch(qkv, d_o, dqkv, cu_seqlens, nseq, n_head, D, max_len, scale, op_dtype, make_drop(dropout_p, seed, (unsigned)site), only_row0 ? 1 : 0, (hipStream_t)stream);
+}
 extern "C" int ofx_attention_f32(const float* qkv, void* out, const int64_t* key_mask, int nseq, int seq_len, int n_head, int D, int ldo, int out_kind,
                                  int mask_ld, int causal, float scale, int op_dtype, ofx_stream stream) {
     SetAttnArgs a{qkv, out, nullptr, nseq, n_head, D, ldo, out_kind, seq_len, 0, scale};

@@ -270,6 +270,14 @@ struct AttnBwdK {
     DropArgs drop;
 };
 
+// dP . m as a ROUNDED product in both orientations.  The softmax backward subtracts rowsum(P . dP), summed in the T orientation, from dP
+// in both; left to the compiler, the N orientation fused this product into that subtraction (an fma on the unrounded product) while the
+// T orientation rounded it, and a set of one row (P = 1, dS = dP - dP) got dK = the product's rounding error instead of zero.
+__device__ __forceinline__ float drop_dp(float dp, float mk) {
+#pragma clang fp contract(off)
+    return dp * mk;
+}
+
 template <typename T, int NT>
 __global__ __launch_bounds__(256) void set_attention_bwd_mfma_kernel(AttnBwdK a) {
     typedef typename OpT<T>::v8 v8;
@@ -386,7 +394,7 @@ __global__ __launch_bounds__(256) void set_attention_bwd_mfma_kernel(AttnBwdK a)
             for (int r = 0; r < 4; ++r) {
                 const float mk = a.drop.thresh ? drop_mul(a.drop, pair, query * 32 + 16 * t + 4 * q4 + r) : 1.0f;
                 const float p = sT[t][u][r] * inv;
-                const float dp = pT[t][u][r] * mk;
+                const float dp = drop_dp(pT[t][u][r], mk);
                 sT[t][u][r] = p; pT[t][u][r] = dp;
                 dot += p * dp;
             }
@@ -419,7 +427,7 @@ __global__ __launch_bounds__(256) void set_attention_bwd_mfma_kernel(AttnBwdK a)
                 const int query = 16 * u + 4 * q4 + r, key = 16 * t + r16;
                 const float mk = a.drop.thresh ? drop_mul(a.drop, pair, query * 32 + key) : 1.0f;
                 const float p = key < S ? exp2f(sN[u][t][r] * sc - mq[r]) * iq[r] : 0.f;
-                const float dp = pN[u][t][r] * mk;
+                const float dp = drop_dp(pN[u][t][r], mk);           // the same bits as in the T orientation, where q_dot was summed
                 sN[u][t][r] = p * mk;                                // dropped-out P
                 pN[u][t][r] = p * (dp - dq[r]) * a.scale;            // dS
             }
@@ -468,6 +476,7 @@ __global__ __launch_bounds__(256) void set_attention_bwd_mfma_kernel(AttnBwdK a)
 int ofx_launch_attention_mfma(const AttnArgs& g, int op_dtype, hipStream_t s) {
     OFX_REQUIRE(g.seq_len >= 1 && g.seq_len <= 64, OFX_ESHAPE, "attention: seq_len=%d must be in [1,64]", g.seq_len);
     OFX_REQUIRE(g.nseq > 0 && g.n_head > 0, OFX_ESHAPE, "attention: nseq=%d n_head=%d", g.nseq, g.n_head);
+    OFX_REQUIRE(g.seq_len <= 32 || !g.drop.thresh, OFX_ESHAPE, "attention: dropout columns are keyed query * 32 + key");
     OFX_REQUIRE(g.ld % 8 == 0 && g.ldo % 4 == 0 && g.k_off % 8 == 0 && g.v_off % 8 == 0, OFX_ESHAPE, "attention: strides must keep 16-byte alignment");
     OFX_REQUIRE((uintptr_t)g.qkv % 16 == 0 && (uintptr_t)g.out % 8 == 0, OFX_EINVAL, "attention: misaligned pointers");
     AttnK k;

@@ -10,6 +10,7 @@ Tolerances: the step computes with single-product MFMA operands like the referen
   bf16 : per-parameter                           <= 3e-2, loss / logits 1e-2
 (q|k|v stay in the operand type between the in_proj GEMM and the attention, as under torch autocast.)
 """
+import contextlib
 import warnings
 
 import numpy as np
@@ -107,14 +108,36 @@ def test_cp_train_step_vs_reference_golden(prec, gtol, ltol, fused_loss):
         assert np.mean(np.abs(du - dr) > 0.1 * float(g["lr"])) <= 0.01, k
 
 
-@pytest.mark.parametrize("n,Lp,n_layers", [([2, 9, 16, 1, 5, 7], 16, None), ([31, 1, 22, 30], 31, None), ([1, 4, 2], 4, 1)],
-                         ids=["n0-16", "n1-31", "n2-4-one_layer"])
-def test_train_step_matches_torch_autograd_of_the_same_module(n, Lp, n_layers):
+@contextlib.contextmanager
+def attention_path(attn):
+    """The training step's attention kernels: 'mfma' = ofx_tune(7, 1), the default; 'valu' = ofx_tune(7, 0), the fp32-arithmetic set
+    kernels on the operand-type q | k | v.  Restores the default."""
+    from outfitx_amd import _lib as L
+    lib = L.load()
+    L.check(lib.ofx_tune(7, {"mfma": 1, "valu": 0}[attn]))
+    try:
+        yield
+    finally:
+        lib.ofx_tune(7, 1)
+
+
+_SETS = [([2, 9, 16, 1, 5, 7], 16, None), ([31, 1, 22, 30], 31, None), ([1, 4, 2], 4, 1)]
+
+
+@pytest.mark.parametrize("n,Lp,n_layers,attn", [c + ("mfma",) for c in _SETS] + [c + ("valu",) for c in _SETS],
+                         ids=["n0-16", "n1-31", "n2-4-one_layer", "n0-16-valu", "n1-31-valu", "n2-4-one_layer-valu"])
+def test_train_step_matches_torch_autograd_of_the_same_module(n, Lp, n_layers, attn):
     """Independent check on fresh inputs: the same nn.TransformerEncoder (plain PyTorch fp32, run on the GPU box's CPU)
     with the same weights -> autograd gradients; ours (f16 operands) within 5e-3 per parameter.  The second case runs the
     longest sets the kernels take (31 items + prefix = 32 rows: the SMAX = 32 attention variants).  The third is a one-layer
     model, whose only layer is the pruned last layer AND layer 0 of the backward (no layer below to hand a linear2 bias
-    gradient or a dropout site to); it checks the CIR head's gradients the same way as the CP head's."""
+    gradient or a dropout site to); it checks the CIR head's gradients the same way as the CP head's.  Each on both attention
+    paths of the training step (the -valu ids: ofx_tune(7, 0))."""
+    with attention_path(attn):
+        _train_step_vs_torch_autograd(n, Lp, n_layers)
+
+
+def _train_step_vs_torch_autograd(n, Lp, n_layers):
     from src.models.datatypes import OutfitCompatibilityPredictionTask as CP, OutfitComplementaryItemRetrievalTask as CIR
     n = np.array(n)
     B = len(n)
@@ -230,25 +253,30 @@ def test_dropout_masks_are_stateless_and_have_the_right_rate():
     assert torch.equal(dropout_mask(0.0, 1, 0, 4, 8, torch.device("cuda")), torch.ones(4, 8, device="cuda"))
 
 
-def test_dropout_training_step_matches_torch_autograd_with_the_same_masks():
+@pytest.mark.parametrize("attn", ["mfma", "valu"])
+@pytest.mark.parametrize("n,Lp", [([3, 8, 1, 5, 6], 8), ([20, 3, 31, 1, 17], 31)], ids=["n8", "n31"])
+def test_dropout_training_step_matches_torch_autograd_with_the_same_masks(n, Lp, attn):
     """Train-mode dropout 0.3 (the reference default, transformer_config.py:16) at all five kinds of site.  The masks are
     exported from the library and replayed in a float64 torch re-statement of the same network; logits and every
-    parameter gradient must agree (f16 operands: 5e-3)."""
+    parameter gradient must agree (f16 operands: 5e-3).  On both attention paths of the training step; the second set of
+    lengths (77 rows, sets of up to 32) runs the two-tile (NT = 2) / SMAX = 32 attention kernels under dropout."""
     from outfitx_amd.engine import dropout_mask
     from src.models.datatypes import OutfitCompatibilityPredictionTask as CP
     p = 0.3
-    n = np.array([3, 8, 1, 5, 6])
-    B, Lp = len(n), 8
+    n = np.array(n)
+    B = len(n)
     emb, mask = synth.outfit_batch(777, B, Lp, n)
     m = make_model("f16", dropout=p)
-    torch.manual_seed(99)
     up = torch.linspace(-1.0, 2.0, B)
-    y = m(task=CP, outfit_embedding=cu(emb), outfit_mask=cu(mask))
-    (y.squeeze(-1) * up.cuda()).sum().backward()
-    pp, seed = m.last_dropout
-    assert pp == p
-    torch.manual_seed(99)
-    y2 = m(task=CP, outfit_embedding=cu(emb), outfit_mask=cu(mask))
+    with attention_path(attn):
+        torch.manual_seed(99)
+        y = m(task=CP, outfit_embedding=cu(emb), outfit_mask=cu(mask))
+        (y.squeeze(-1) * up.cuda()).sum().backward()
+        pp, seed = m.last_dropout
+        assert pp == p
+        torch.manual_seed(99)
+        y2 = m(task=CP, outfit_embedding=cu(emb), outfit_mask=cu(mask))
+        torch.cuda.synchronize()
     assert torch.equal(y, y2), "same torch seed -> same masks"
     ours = {k: v.grad.detach().cpu().double() for k, v in trainable(m).items() if v.grad is not None}
     dev = torch.device("cuda")
