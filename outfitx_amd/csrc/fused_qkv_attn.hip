@@ -36,10 +36,11 @@ constexpr int FQ_NT = 4;                                                        
 static_assert(FQ_TN == 3 * ATTN_D && 16 * FQ_NT == ATTN_D, "the tail runs the attention core at NT = 4 on one head's 64 q, 64 k and 64 v columns");
 constexpr int FQ_Q_OFF = 0, FQ_K_OFF = FQ_TM * FQ_QK_ROW, FQ_V_OFF = 2 * FQ_TM * FQ_QK_ROW;      // 0, 36864, 73728; V ends at 114688 = 2 stages
 constexpr int FQ_LDS = 2 * FQ_STAGE + 16 * ATTN_V_ROW;                             // + 16 zeroed V rows behind the last image (keys S .. 63 of image G-1)
-// Dual-weight variant (W2 = true: Wqkv rows are [hi(Wm) | lo(Wm)], the split weights of DESIGN.md section 2): the main loop of
-// gemm_w2.hip - BK = 32, three stages [A 256 rows | W_hi 192 rows | W_lo 192 rows] x 64 B, the two wave groups offset by one barrier
-// slot, 48 MFMAs (8 A fragments x 3 column tiles x {hi, lo}) per wave and step against 14 fragment reads - then the same epilogue
-// and attention.  The q | k | v image (117,248 B incl. the V pad rows) lies inside the three stages (122,880 B).
+// Dual-weight variant (W2 = true: Wqkv rows are [hi(Wm) | lo(Wm)], the split weights of DESIGN.md section 2): the counted-wait
+// ping-pong of gemm_pingpong.h, as gemm_w2.hip runs it - BK = 32, three stages [A 256 rows | W_hi 192 rows | W_lo 192 rows] x 64 B,
+// the two wave groups offset by one barrier slot, 48 MFMAs (8 A fragments x 3 column tiles x {hi, lo}) per wave and step against 14
+// fragment reads - then the same epilogue and attention.  The q | k | v image (117,248 B incl. the V pad rows) lies inside the
+// three stages (122,880 B).
 constexpr int FQ2_BK = 32, FQ2_A = FQ_TM * FQ2_BK * 2, FQ2_W = FQ_TN * FQ2_BK * 2, FQ2_STAGE = FQ2_A + 2 * FQ2_W, FQ2_NST = 3;   // 16384, 12288, 40960
 constexpr int FQ2_LDS = FQ2_NST * FQ2_STAGE;
 static_assert(FQ2_LDS >= FQ_LDS, "q | k | v image must fit the dual-weight stages");
@@ -75,8 +76,9 @@ __global__ __launch_bounds__(512, 2) void fused_qkv_attn_kernel(FusedK p) {
     const int fr = lane & 15, fq = lane >> 4;
 
     if constexpr (W2) {
-    // ------------------------------------------------------------------ dual-weight main loop (see gemm_w2.hip for the slot schedule)
-    const int prow = lane >> 2, pchk = (lane & 3) ^ ((4 - (lane >> 4)) & 3);
+    // ------------------------------------------------------------------ dual-weight main loop (gemm_pingpong.h: the slot schedule)
+    const PpLane32 L(lane);
+    const int prow = L.prow, pchk = L.pchk;
     const char* a_base = p.X + (size_t)m0 * p.ldx * 2;
     const char* w_base = p.Wqkv + (size_t)head * 64 * (2 * p.Wm) * 2;          // row stride 2 Wm elements: [hi | lo]
     unsigned a_off[2], w_off[3];
@@ -107,56 +109,22 @@ __global__ __launch_bounds__(512, 2) void fused_qkv_attn_kernel(FusedK p) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) glds16(wk + w_off[i], base + w_dst[i]);
     };
-    const int fchk = (fq ^ ((4 - (fr >> 2)) & 3)) * 16;
-    const int a_frag = (wr * 128 + fr) * 64 + fchk;
-    const int w_frag = FQ2_A + (wc * 48 + fr) * 64 + fchk;
+    const int a_frag = (wr * 128 + fr) * 64 + L.fchk;
+    const int w_frag = FQ2_A + (wc * 48 + fr) * 64 + L.fchk;
     v8 af[8], wh[3], wl[3];
-#define FQ2_READ(STG)                                                                                            \
-    {                                                                                                            \
-        OFX_LDS char* base_ = lds + (STG) * FQ2_STAGE;                                                           \
-        _Pragma("unroll") for (int j = 0; j < 3; ++j) wh[j] = *(OFX_LDS v8*)(base_ + w_frag + j * 16 * 64);       \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) af[i] = *(OFX_LDS v8*)(base_ + a_frag + i * 16 * 64);       \
-        _Pragma("unroll") for (int j = 0; j < 3; ++j) wl[j] = *(OFX_LDS v8*)(base_ + FQ2_W + w_frag + j * 16 * 64); \
-    }
-#define FQ2_MFMA()                                                                                               \
-    {                                                                                                            \
-        __builtin_amdgcn_s_setprio(1);                                                                           \
-        _Pragma("unroll") for (int m = 0; m < 48; ++m) {                                                         \
-            const int i = m / 6, j = m % 3;                                                                      \
-            acc[i][j] = OpT<T>::mfma16((m % 6) >= 3 ? wl[j] : wh[j], af[i], acc[i][j]);                          \
-        }                                                                                                        \
-        __builtin_amdgcn_s_setprio(0);                                                                           \
-    }
+    auto read = [&](int t) { pp_w2_read<3>(lds + (t % FQ2_NST) * FQ2_STAGE, a_frag, w_frag, FQ2_W, af, wh, wl); };
+    auto mfma = [&] { pp_w2_mfma<T, 3>(acc, af, wh, wl); };
     issue_all(0); issue_all(1);
     asm volatile("s_waitcnt vmcnt(5)" ::: "memory");            // step 0 landed (my pieces)
     __builtin_amdgcn_s_barrier();
+    // iteration t issues step t + 2 (5 pieces per wave: they stay in flight over the counted wait), reads and multiplies step t
     if (wr == 0) {
-        for (int t = 0; t < nk; ++t) {
-            issue_all(t + 2);
-            FQ2_READ(t % FQ2_NST)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            FQ2_MFMA()
-            asm volatile("s_waitcnt vmcnt(5)" ::: "memory");    // my pieces of step t+1 landed (step t+2 stays in flight)
-            __builtin_amdgcn_s_barrier();
-        }
-        __builtin_amdgcn_s_barrier();
+        for (int t = 0; t < nk; ++t) pp_slot<0, 5>([&] { issue_all(t + 2); }, [&] { read(t); }, mfma);
+        pp_group_end<0>();
     } else {
-        __builtin_amdgcn_s_barrier();
-        for (int t = 0; t < nk; ++t) {
-            issue_all(t + 2);
-            FQ2_READ(t % FQ2_NST)
-            asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            FQ2_MFMA()
-            __builtin_amdgcn_s_barrier();
-        }
+        pp_group_begin<1>();
+        for (int t = 0; t < nk; ++t) pp_slot<1, 5>([&] { issue_all(t + 2); }, [&] { read(t); }, mfma);
     }
-#undef FQ2_READ
-#undef FQ2_MFMA
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                           // every stage read and every (clamped) fill is done: the stages become q | k | v
     // the V pad rows lie inside stage 2 here: zero them now (the barrier before the attention publishes them)

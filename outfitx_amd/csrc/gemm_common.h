@@ -1,12 +1,14 @@
 // Shared pieces of the GEMM translation units (gemm.hip: 128x128 kernel + dispatcher; gemm_big.hip: 256x256 / 256x128 tiles;
 // gemm_pp.hip: ping-pong 256x256; gemm_w2.hip: dual-weight 256x256; gemm_w2f8.hip: the same with the fp8 correction product;
 // gemm_x3.hip: three-product 256x128; gemm_tn.hip: weight-gradient TN kernel) and of fused_qkv_attn.hip, which borrows the tile
-// constants and the block remap: the kernel kinds, kernel arguments, the tile walk (gemm_walk.h), the live-row clamp, the LDS-DMA
-// helpers and the fused epilogues.  Everything here has internal linkage (anonymous namespace / templates); the files are split only
-// so that they compile in parallel.
+// constants and the block remap: the kernel kinds, kernel arguments, the tile walk (gemm_walk.h), the two-wave-group main loop
+// (gemm_pingpong.h: slot protocol, BK = 32 lane constants, persistent walk, dual-weight step), the live-row clamp, the LDS-DMA
+// helpers and the fused epilogues.  Everything here has internal linkage (anonymous namespace / templates); the files are split
+// only so that they compile in parallel.
 #pragma once
 #include <type_traits>
 
+#include "gemm_pingpong.h"
 #include "gemm_walk.h"
 #include "ofx_common.h"
 

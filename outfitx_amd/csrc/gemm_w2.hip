@@ -7,20 +7,10 @@
 // single-product kernels read 12 fragments per 32 MFMAs), so the loop is bound by the matrix pipe, not by the LDS port.
 // Used for the CLIP GEMMs whose weight rounding dominates the end-to-end error (fc2, out-proj, patch embedding: DESIGN.md §2).
 //
-// Structure (the ping-pong kernel's, gemm_pp.hip, at BK = 32 with three 48 KiB stages):
-//   waves 0-3 (group 0, rows 0-127) and 4-7 (group 1) run the same per-step program offset by ONE barrier slot: on every SIMD
-//   one wave reads its 16 fragments while the other runs its 64 MFMAs and issues its 6 LDS-DMA pieces of a later step.
-//     slot:      0     1         2         3         4         5
-//     group 0:  [W0]  [R0 I2]   [M0]      [R1 I3]   [M1]      [R2 I4]  ...   I(s) = issue step s into stage s % 3
-//     group 1:  [W0]  [  ]      [R0 I2]   [M0]      [R1 I3]   [M1]     ...
-//   Step s is read in slots 2s+1 (group 0) and 2s+2 (group 1); its stage is refilled with step s+3 in slots 2s+3 / 2s+4 (WAR: both
-//   groups' reads ended before the barrier that closes slot 2s+2).  Every wave waits for its own pieces of step s (counted
-//   vmcnt(6): the youngest step stays in flight) before the barrier that closes slot 2s; step s is first read in slot 2s+1 (RAW).
-// Persistent over tiles (one block per CU; ofx_tune(11, 0) = one block per tile): steps are numbered across the block's tiles, the
-// fills of steps nk and nk + 1 fetch the next tile's first two steps under the current epilogue (see the kernel body).
-// LDS image of a stage: [A 256 rows | W_hi 256 rows | W_lo 256 rows] x 64 B; a wave-instruction moves 16 rows x 64 B; the 16-B
-// chunk c of row r sits at slot c ^ f(r >> 2), f(g) = (-g) & 3, applied on the DMA source address and on the ds_read_b128 side:
-// conflict-free for the hardware's lane groups of ds_read_b128 (MI355X_MICROARCH.md, LDS table).
+// Structure: the counted-wait ping-pong of gemm_pingpong.h at BK = 32 with three 48 KiB stages [A 256 rows | W_hi 256 rows | W_lo 256
+// rows] x 64 B, persistent over tiles (one block per CU; ofx_tune(11, 0) = one block per tile).  Per step and wave 6 LDS-DMA pieces
+// (counted vmcnt(6): the youngest step stays in flight), 16 fragment reads, 64 MFMAs; iteration t issues step t + 2, so the fills of
+// steps nk and nk + 1 fetch the next tile's first two steps under the current epilogue (see the kernel body).
 #include "gemm_common.h"
 
 extern int g_w2_persist;
@@ -39,34 +29,21 @@ __global__ __launch_bounds__(512, 2) void gemm_w2_kernel(KArgs p) {
     p.K = Kh;                                          // the epilogues never read K; keep the logical value anyway
     clamp_live_rows(p.m_dev, p.M);                     // device-side live row count: the launcher runs one block per tile then
 
-    // Persistent over tiles: block b runs tiles b, b + gridDim.x, ... (the launcher sizes the grid to one block per CU, or one block
-    // per tile on small problems).  The k-steps are numbered across the block's tiles - step g lives in stage g % 3 - so the two fills
-    // that used to be redundant at the end of a tile (steps nk, nk + 1) fetch the NEXT tile's first two steps instead: they land
-    // under the epilogue, whose staging sits in the stage of the tile's last step (the one stage no fill targets), and the next main
-    // loop starts without a load-latency bubble.
-    auto map_tile = [&](int vb, int& m0, int& n0) {
-        int tm, tn;
-        grouped_tile(xcd_remap(vb, p.nwg), p.group_m, p.tiles_m, p.tiles_n, tm, tn);
-        m0 = tm * TM;
-        n0 = tn * TN;
-    };
     const unsigned lo_bytes = (unsigned)Kh * 2;
     const int nk = Kh / BK2;
     const int dst0 = wave * 2 * 1024;
 
-    int vb = blockIdx.x, m0, n0;
-    map_tile(vb, m0, n0);
-    if (m0 >= p.M) return;                              // only with m_dev (one block per tile)
-    int base = 0;                                       // (global index of the current tile's step 0) mod 3
-    bool first = true;
+    PpWalk<NST, TM, TN> w(p.nwg, p.group_m, p.tiles_m, p.tiles_n, nk);
+    if (w.m0 >= p.M) return;                            // only with m_dev (one block per tile)
     for (;;) {
-        const bool has_next = vb + (int)gridDim.x < p.nwg;     // its first two steps are fetched by this tile's last two fills
+        const bool has_next = w.has_next();             // its first two steps are fetched by this tile's last two fills
+        const int m0 = w.m0, n0 = w.n0;
         // Lane constants are re-derived per tile from an opaque copy of the lane id: kept live across the epilogue they cost more
         // registers than the kernel has (spills), recomputing them costs a few dozen VALU operations per ~50 us tile.
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        // LDS-DMA pieces: 16 rows x 64 B; lane l -> row l >> 2, physical slot l & 3 <- logical chunk (l & 3) ^ f(row >> 2)
-        const int prow = ln >> 2, pchk = (ln & 3) ^ ((4 - (ln >> 4)) & 3);
+        const PpLane32 L(ln);
+        const int prow = L.prow, pchk = L.pchk;
         unsigned w_off[2];                                  // tile-independent
 #pragma unroll
         for (int i = 0; i < 2; ++i) w_off[i] = ((unsigned)((wave * 2 + i) * 16 + prow) * (2 * Kh) + pchk * 8) * 2;
@@ -75,10 +52,8 @@ __global__ __launch_bounds__(512, 2) void gemm_w2_kernel(KArgs p) {
             const int rr = mt + row < p.M ? row : p.M - 1 - mt;
             return ((unsigned)rr * p.lda + pchk * 8) * 2;
         };
-        const int fr = ln & 15, fq = ln >> 4;
-        const int fchk = (fq ^ ((4 - (fr >> 2)) & 3)) * 16;
-        const int a_frag = (wr * 128 + fr) * 64 + fchk;
-        const int w_frag = PART + (wc * 64 + fr) * 64 + fchk;
+        const int a_frag = (wr * 128 + L.fr) * 64 + L.fchk;
+        const int w_frag = PART + (wc * 64 + L.fr) * 64 + L.fchk;
         const char* a_base = p.A + (size_t)m0 * p.lda * 2;
         const char* w_base = p.W + (size_t)n0 * (2 * Kh) * 2;
         unsigned a_off[2];
@@ -92,17 +67,17 @@ __global__ __launch_bounds__(512, 2) void gemm_w2_kernel(KArgs p) {
         else glds16((WK) + lo_bytes + w_off[(Q) - 4], (BASE) + 2 * PART + dst0 + ((Q) - 4) * 1024);     \
     }
         auto issue_cur = [&](int step) {                // a step of the current tile (step < nk)
-            OFX_LDS char* sbase = lds + ((base + step) % NST) * STAGE;
+            OFX_LDS char* sbase = lds + w.stage(step) * STAGE;
             const char* ak = a_base + (size_t)step * BK2 * 2;
             const char* wk = w_base + (size_t)step * BK2 * 2;
 #pragma unroll
             for (int q = 0; q < 6; ++q) OFX_W2_PIECE(q, ak, a_off[0], a_off[1], wk, sbase)
         };
         auto issue_next = [&](int j) {                  // step nk + j: the next tile's step j, in the stage of this tile's step nk + j - 3
-            OFX_LDS char* sbase = lds + ((base + nk + j) % NST) * STAGE;
+            OFX_LDS char* sbase = lds + w.stage(nk + j) * STAGE;
             if (has_next) {
                 int m1, n1;
-                map_tile(vb + (int)gridDim.x, m1, n1);
+                w.next_origin(m1, n1);
                 const char* ak = p.A + (size_t)m1 * p.lda * 2 + (size_t)j * BK2 * 2;
                 const char* wk = p.W + (size_t)n1 * (2 * Kh) * 2 + (size_t)j * BK2 * 2;
                 const unsigned n0_ = a_offset(m1, 0), n1_ = a_offset(m1, 1);
@@ -123,84 +98,41 @@ __global__ __launch_bounds__(512, 2) void gemm_w2_kernel(KArgs p) {
             for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         v8 af[8], wh[4], wl[4];
 
-#define OFX_W2_READ(STEP)                                                                                    \
-    {                                                                                                        \
-        OFX_LDS char* base_ = lds + ((base + (STEP)) % NST) * STAGE;                                         \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) wh[j] = *(OFX_LDS v8*)(base_ + w_frag + j * 16 * 64);   \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) af[i] = *(OFX_LDS v8*)(base_ + a_frag + i * 16 * 64);   \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) wl[j] = *(OFX_LDS v8*)(base_ + PART + w_frag + j * 16 * 64); \
-    }
-    // 64 MFMAs (per A fragment: 4 hi then 4 lo): nothing else in the stream - the LDS-DMA pieces are issued from the READ slots,
-    // where the wave would otherwise wait for its fragments (an LDS-DMA issue costs the issuing wave ~100 cycles; threaded through
-    // the MFMAs it cost 0.3 us of every 0.8 us slot)
-#define OFX_W2_MFMA()                                                                                        \
-    {                                                                                                        \
-        __builtin_amdgcn_s_setprio(1);                                                                       \
-        _Pragma("unroll") for (int m = 0; m < 64; ++m) {                                                     \
-            const int i = (m >> 3) & 7, j = m & 3;                                                           \
-            acc[i][j] = OpT<T>::mfma16((m & 4) ? wl[j] : wh[j], af[i], acc[i][j]);                           \
-        }                                                                                                    \
-        __builtin_amdgcn_s_setprio(0);                                                                       \
-    }
+        auto read = [&](int step) { pp_w2_read<4>(lds + w.stage(step) * STAGE, a_frag, w_frag, PART, af, wh, wl); };
+        auto mfma = [&] { pp_w2_mfma<T, 4>(acc, af, wh, wl); };
 
-        if (first) {
+        if (w.first) {
             issue_cur(0); issue_cur(1);
             asm volatile("s_waitcnt vmcnt(6)" ::: "memory");        // step 0 landed (my pieces)
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // steps 0 and 1 (fetched under the previous epilogue) and that epilogue's stores
         }
         __builtin_amdgcn_s_barrier();                               // ---- end of slot 0
-        // One iteration of group 0 (slots 2t+1, 2t+2) / group 1 (slots 2t+2, 2t+3): ISSUE refills the stage of step t-1 (both groups
-        // have read it) with step t+2, before the reads (760 vs 775 us on the fc2 shape with the DMA after them); the last two
-        // iterations of a tile are peeled so that the steady-state body carries no next-tile logic.
-#define OFX_W2_ITER_G0(T_, ISSUE)                                                                                \
-        {                                                                                                        \
-            ISSUE;                                                                                               \
-            OFX_W2_READ(T_)                                                                                      \
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                   \
-            __builtin_amdgcn_sched_barrier(0);                                                                   \
-            __builtin_amdgcn_s_barrier();                                                                        \
-            OFX_W2_MFMA()                                                                                        \
-            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");    /* my pieces of step t+1 landed (step t+2 stays in flight) */ \
-            __builtin_amdgcn_s_barrier();                                                                        \
-        }
-#define OFX_W2_ITER_G1(T_, ISSUE)                                                                                \
-        {                                                                                                        \
-            ISSUE;                                                                                               \
-            OFX_W2_READ(T_)                                                                                      \
-            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");    /* my pieces of step t+1 landed: group 0 reads them in slot 2t+3 */ \
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                   \
-            __builtin_amdgcn_sched_barrier(0);                                                                   \
-            __builtin_amdgcn_s_barrier();                                                                        \
-            OFX_W2_MFMA()                                                                                        \
-            __builtin_amdgcn_s_barrier();                                                                        \
-        }
+        // Iteration t refills the stage of step t-1 (both groups have read it) with step t+2; the last two iterations of a tile are
+        // peeled so that the steady-state body carries no next-tile logic.  (The two groups are written out: one generic lambda over the
+        // group, as gemm_x3 has it, laid the peeled fills out once more here.)
         if (wr == 0) {
-            for (int t = 0; t < nk - 2; ++t) OFX_W2_ITER_G0(t, issue_cur(t + 2))
-            OFX_W2_ITER_G0(nk - 2, issue_next(0))
-            OFX_W2_ITER_G0(nk - 1, issue_next(1))
-            __builtin_amdgcn_s_barrier();                           // group 1's last MFMA slot begins: every read of this tile is done
+            for (int t = 0; t < nk - 2; ++t) pp_slot<0, 6>([&] { issue_cur(t + 2); }, [&] { read(t); }, mfma);
+            pp_slot<0, 6>([&] { issue_next(0); }, [&] { read(nk - 2); }, mfma);
+            pp_slot<0, 6>([&] { issue_next(1); }, [&] { read(nk - 1); }, mfma);
+            pp_group_end<0>();
         } else {
-            __builtin_amdgcn_s_barrier();                           // slot 1: group 0 reads step 0
-            for (int t = 0; t < nk - 2; ++t) OFX_W2_ITER_G1(t, issue_cur(t + 2))
-            OFX_W2_ITER_G1(nk - 2, issue_next(0))
-            OFX_W2_ITER_G1(nk - 1, issue_next(1))
+            pp_group_begin<1>();
+            for (int t = 0; t < nk - 2; ++t) pp_slot<1, 6>([&] { issue_cur(t + 2); }, [&] { read(t); }, mfma);
+            pp_slot<1, 6>([&] { issue_next(0); }, [&] { read(nk - 2); }, mfma);
+            pp_slot<1, 6>([&] { issue_next(1); }, [&] { read(nk - 1); }, mfma);
         }
-#undef OFX_W2_ITER_G0
-#undef OFX_W2_ITER_G1
-#undef OFX_W2_READ
-#undef OFX_W2_MFMA
 #undef OFX_W2_PIECE
         // Epilogue staging: the stage of this tile's LAST step - read by everybody before the barriers above, and the one stage
         // the fills of steps nk, nk + 1 (the next tile's first steps, still landing) do not target.
-        OFX_LDS char* estage = lds + ((base + nk - 1) % NST) * STAGE;
+        OFX_LDS char* estage = lds + w.epilogue_stage() * STAGE;
         OFX_LDS char* ep = estage + wave * EPI2_BYTES_PER_WAVE;
         const int gm0 = m0 + wr * 128, gn0 = n0 + wc * 64;
         OFX_LDS float* st = nullptr;
         if (p.row_stat && p.out_kind != 0) st = (OFX_LDS float*)(estage + 8 * EPI2_BYTES_PER_WAVE + wave * 1024);
         epilogue2_dispatch<T>(p, ep, acc, gm0, gn0, ln, st);
         if (!has_next) break;
-        vb += gridDim.x; map_tile(vb, m0, n0); base = (base + nk) % NST; first = false;
+        w.advance();
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // the last tile's redundant fills have landed before the wave ends
 }

@@ -26,7 +26,7 @@
 //   * per-row weight scales (E8M0, max |lo| 2^sw in [128, 256)) ride in as the instruction's per-lane scale operand, the activation
 //     scale (2^0: the e5m2 image needs none) as the other one.
 //
-// Structure: gemm_w2.hip's ping-pong (two wave groups one barrier slot apart, BK = 32, counted vmcnt, persistent over tiles) with FOUR
+// Structure: the counted-wait ping-pong of gemm_pingpong.h (two wave groups one barrier slot apart, BK = 32, persistent over tiles) with FOUR
 // 32 KiB stages [A | W_hi] and ONE 32 KiB buffer for the current super-step's fp8 weights (160 KiB in all).  The kernels of this
 // family take time in proportion to the bytes they stage through LDS (~16-20 B/clk/CU: gemm_w2 with 48 KiB per k-step, this kernel
 // with 40 KiB, the single-product kernels with 32 KiB; DESIGN.md section 3.1: the fill itself needs that long, and every LDS-DMA
@@ -68,30 +68,24 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
     const int Kh = p.K >> 1;                           // logical K; 2 Kh is the row stride (elements) of W = [hi | lo]
     p.K = Kh;
     clamp_live_rows(p.m_dev, p.M);
-    auto map_tile = [&](int vb, int& m0, int& n0) {
-        int tm, tn;
-        grouped_tile(xcd_remap(vb, p.nwg), p.group_m, p.tiles_m, p.tiles_n, tm, tn);
-        m0 = tm * TM;
-        n0 = tn * TN;
-    };
     const int nk = Kh / BK2, nsup = nk >> 2;
     const int dst0 = wave * 2 * 1024;
     const float a_scale = 1.0f;                        // the e5m2 activation image: f16's exponent range, unscaled (E8M0 byte 127 = 2^0)
     const int a_e8 = 127;
 
-    int vb = blockIdx.x, m0, n0;
-    map_tile(vb, m0, n0);
-    if (m0 >= p.M) return;
-    int base = 0;                                       // (global index of the current tile's step 0) mod 4
-    bool first = true, full_prev = false;
+    PpWalk<NST, TM, TN> w(p.nwg, p.group_m, p.tiles_m, p.tiles_n, nk);
+    if (w.m0 >= p.M) return;
+    bool full_prev = false;
     // per-row E8M0 scale bytes of this wave's 128 columns: 8 bytes per lane (fragment j -> byte j); the NEXT tile's are requested before
     // the epilogue, so that their latency is not paid at the top of every tile
-    unsigned long long sc8 = *(const unsigned long long*)(p.w8_scale + ((size_t)((n0 >> 7) + wc) * 16 + (lane & 15)) * 8);
+    unsigned long long sc8 = *(const unsigned long long*)(p.w8_scale + ((size_t)((w.n0 >> 7) + wc) * 16 + (lane & 15)) * 8);
     for (;;) {
-        const bool has_next = vb + (int)gridDim.x < p.nwg;
+        const bool has_next = w.has_next();
+        const int m0 = w.m0, n0 = w.n0;
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        // f16 pieces: 16 rows x 64 B; lane l -> row l >> 2, physical slot l & 3 <- logical chunk (l & 3) ^ f(row >> 2)
+        // f16 pieces: 16 rows x 64 B; lane l -> row l >> 2, physical slot l & 3 <- logical chunk (l & 3) ^ f(row >> 2) - the kernel's own
+        // copy of PpLane32 (gemm_pingpong.h): built through the struct it takes 244 VGPRs instead of 242
         const int prow = ln >> 2, pchk = (ln & 3) ^ ((4 - (ln >> 4)) & 3);
         unsigned w_off[2];
 #pragma unroll
@@ -112,8 +106,8 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
         unsigned a_off[2];                                  // tile-independent too: rows past M read zeros through the sized resource
 #pragma unroll
         for (int i = 0; i < 2; ++i) a_off[i] = ((unsigned)((wave * 2 + i) * 16 + prow) * p.lda + pchk * 8) * 2;
-        int m1 = m0, n1 = n0;                               // the next tile (the block's last tile re-fills its own first steps: nobody reads them)
-        if (has_next) map_tile(vb + (int)gridDim.x, m1, n1);
+        int m1, n1;
+        w.next_origin(m1, n1);
         int sc_lo = (int)(unsigned)sc8, sc_hi = (int)(unsigned)(sc8 >> 32);
 
         // LDS-DMA pieces: the two A and two W_hi pieces of a k-step (KOFF = its byte offset in the k-contiguous rows) and quarter Q of
@@ -130,7 +124,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
         const __amdgpu_buffer_rsrc_t r_a1 = make_rsrc(p.A + (size_t)m1 * a_row, (size_t)(p.M - m1) * a_row), r_w1 = make_rsrc(p.W + (size_t)n1 * (2 * Kh) * 2);
         // k-step x of the tile walk: a step of this tile, or (x >= nk) step x - nk of the next one - a scalar select of resource and offset
         auto issue_step = [&](int x) {
-            OFX_LDS char* stg = lds + ((base + x) % NST) * STAGE;
+            OFX_LDS char* stg = lds + w.stage(x) * STAGE;
             const bool nx = x >= nk;
             const __amdgpu_buffer_rsrc_t ra = nx ? r_a1 : r_a, rw = nx ? r_w1 : r_w;
             OFX_F8_ISSUE_AW(ra, rw, a_off[0], a_off[1], (unsigned)(nx ? x - nk : x) * BK2 * 2, stg)
@@ -146,12 +140,13 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) a8[i] = i32x8{0, 0, 0, 0, 0, 0, 0, 0};
 
-#define OFX_F8_READ(STEP)                                                                                     \
-    {                                                                                                         \
-        OFX_LDS char* base_ = lds + ((base + (STEP)) % NST) * STAGE;                                          \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j) wh[j] = *(OFX_LDS v8*)(base_ + w_frag + j * 16 * 64);    \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) af[i] = *(OFX_LDS v8*)(base_ + a_frag + i * 16 * 64);    \
-    }
+        auto read = [&](int step) {
+            OFX_LDS char* stg = lds + w.stage(step) * STAGE;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) wh[j] = *(OFX_LDS v8*)(stg + w_frag + j * 16 * 64);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) af[i] = *(OFX_LDS v8*)(stg + a_frag + i * 16 * 64);
+        };
         // 32 f16 MFMAs + the conversion of the four A fragments into bytes 8 S .. 8 S + 7 of their fp8 images (S = step & 3, static)
 #define OFX_F8_CVT1(I, S)                                                                                      \
     {                                                                                                         \
@@ -199,7 +194,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
         __builtin_amdgcn_s_setprio(0);                                                                        \
     }
 
-        if (first) {                                                // group 1 runs one step further ahead (see the schedule below)
+        if (w.first) {                                                // group 1 runs one step further ahead (see the schedule below)
             issue_step(0); issue_step(1);
             if (grp == 0) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");        // step 0 landed (my pieces)
             else { issue_step(2); asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }
@@ -215,60 +210,25 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
         asm volatile("" : "+v"(sc_lo), "+v"(sc_hi));                  // the scale load is waited for HERE, not inside the counted-vmcnt loop
         asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1");     // MODE.FP16_OVFL: the f16 -> fp8 conversion clamps at the format's largest finite value (e5m2: 57,344; e4m3: 448) instead of inf / NaN
         __builtin_amdgcn_s_barrier();                               // ---- end of slot 0
-        // One iteration of group 0 (slots 2t+1, 2t+2) / group 1 (slots 2t+2, 2t+3), as in gemm_w2.hip; NV = the LDS-DMA pieces the
-        // iteration issues: its counted wait leaves exactly those in flight (everything issued by earlier iterations has landed: an
-        // iteration t fills steps t + 2 / t + 3, read from iteration t + 2 on, and the fp8 quarters are read two iterations later at
-        // the earliest).  The fp8 product of a super-step runs at the end of the MFMA slot of its fourth k-step.
-#define OFX_F8_ITER_G0(T_, S_, NV, ISSUE, TAIL)                                                                  \
-        {                                                                                                        \
-            ISSUE;                                                                                               \
-            OFX_F8_READ(T_)                                                                                      \
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                   \
-            __builtin_amdgcn_sched_barrier(0);                                                                   \
-            __builtin_amdgcn_s_barrier();                                                                        \
-            OFX_F8_MFMA16(S_)                                                                                    \
-            TAIL                                                                                                 \
-            asm volatile("s_waitcnt vmcnt(" #NV ")" ::: "memory");                                               \
-            __builtin_amdgcn_s_barrier();                                                                        \
-        }
-#define OFX_F8_ITER_G1(T_, S_, NV, ISSUE, TAIL)                                                                  \
-        {                                                                                                        \
-            ISSUE;                                                                                               \
-            OFX_F8_READ(T_)                                                                                      \
-            asm volatile("s_waitcnt vmcnt(" #NV ")" ::: "memory");                                               \
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                   \
-            __builtin_amdgcn_sched_barrier(0);                                                                   \
-            __builtin_amdgcn_s_barrier();                                                                        \
-            OFX_F8_MFMA16(S_)                                                                                    \
-            TAIL                                                                                                 \
-            __builtin_amdgcn_s_barrier();                                                                        \
-        }
-#define OFX_F8_W8_ALL(U) OFX_F8_ISSUE_W8(U, 0) OFX_F8_ISSUE_W8(U, 1) OFX_F8_ISSUE_W8(U, 2) OFX_F8_ISSUE_W8(U, 3)
-        if (grp == 0) {
+        // One iteration of a group = pp_slot (gemm_pingpong.h); NV = the LDS-DMA pieces the iteration issues: its counted wait leaves
+        // exactly those in flight (everything issued by earlier iterations has landed: an iteration t fills steps t + 2 / t + 3, read
+        // from iteration t + 2 on, and the fp8 quarters are read two iterations later at the earliest).  The fp8 product of a
+        // super-step runs at the end of the MFMA slot of its fourth k-step.
+        auto run = [&](auto G) {
+            constexpr int g = G.value;
+            pp_group_begin<g>();
             int u = 0;
             do {                                                    // nsup >= 1: no trip-count guard (its flag ended up spilled, and a scratch reload drains the DMA queue)
                 const int t = 4 * u;
-                OFX_F8_ITER_G0(t, 0, 8, issue_step(t + 2); issue_step(t + 3), )
-                OFX_F8_ITER_G0(t + 1, 1, 4, OFX_F8_W8_ALL(u), )
-                OFX_F8_ITER_G0(t + 2, 2, 4, issue_step(t + 4), )
-                OFX_F8_ITER_G0(t + 3, 3, 4, issue_step(t + 5), OFX_F8_MFMA8())
+                pp_slot<g, g ? 4 : 8>([&] { if (g == 0) issue_step(t + 2); issue_step(t + 3); }, [&] { read(t); }, [&] { OFX_F8_MFMA16(0) });
+                pp_slot<g, 4>([&] { OFX_F8_ISSUE_W8(u, 0) OFX_F8_ISSUE_W8(u, 1) OFX_F8_ISSUE_W8(u, 2) OFX_F8_ISSUE_W8(u, 3) }, [&] { read(t + 1); }, [&] { OFX_F8_MFMA16(1) });
+                pp_slot<g, 4>([&] { issue_step(t + 4); }, [&] { read(t + 2); }, [&] { OFX_F8_MFMA16(2) });
+                pp_slot<g, g ? 8 : 4>([&] { issue_step(t + 5); if (g == 1) issue_step(t + 6); }, [&] { read(t + 3); }, [&] { OFX_F8_MFMA16(3) }, [&] { OFX_F8_MFMA8() });
             } while (++u < nsup);
-            __builtin_amdgcn_s_barrier();                           // closes group 1's last MFMA slot: every read of this tile's stages and fp8 buffer is done
-        } else {
-            __builtin_amdgcn_s_barrier();                           // slot 1: group 0 reads step 0
-            int u = 0;
-            do {                                                    // nsup >= 1: no trip-count guard (its flag ended up spilled, and a scratch reload drains the DMA queue)
-                const int t = 4 * u;
-                OFX_F8_ITER_G1(t, 0, 4, issue_step(t + 3), )
-                OFX_F8_ITER_G1(t + 1, 1, 4, OFX_F8_W8_ALL(u), )
-                OFX_F8_ITER_G1(t + 2, 2, 4, issue_step(t + 4), )
-                OFX_F8_ITER_G1(t + 3, 3, 8, issue_step(t + 5); issue_step(t + 6), OFX_F8_MFMA8())
-            } while (++u < nsup);
-        }
-#undef OFX_F8_W8_ALL
-#undef OFX_F8_ITER_G0
-#undef OFX_F8_ITER_G1
-#undef OFX_F8_READ
+            pp_group_end<g>();
+        };
+        if (grp == 0) run(std::integral_constant<int, 0>());
+        else run(std::integral_constant<int, 1>());
 #undef OFX_F8_MFMA16
 #undef OFX_F8_MFMA8
 #undef OFX_F8_MF
@@ -279,7 +239,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
         asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 0");     // the epilogue's f32 -> f16 casts keep the default overflow behaviour
         // Epilogue staging: the stage of this tile's LAST k-step (every read of it is over, no fill targets it); statistics slots of the
         // LayerNorm-fold consumers: the fp8 buffer (idle until the next tile's first iterations refill it, behind the barrier of its slot 0).
-        OFX_LDS char* estage = lds + ((base + nk - 1) % NST) * STAGE;
+        OFX_LDS char* estage = lds + w.epilogue_stage() * STAGE;
         OFX_LDS char* ep = estage + wave * EPI2_BYTES_PER_WAVE;
         const int gm0 = m0 + wr * 64, gn0 = n0 + wc * 128;
         OFX_LDS float* st = nullptr;
@@ -292,7 +252,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
         }
         if (!has_next) break;
         full_prev = m0 + TM <= p.M;
-        vb += gridDim.x; map_tile(vb, m0, n0); base = (base + nk) % NST; first = false;
+        w.advance();
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // the last tile's redundant fills have landed before the wave ends
 }

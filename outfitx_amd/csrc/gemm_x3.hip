@@ -9,9 +9,9 @@
 //
 // 256 x 128 tile, 8 waves as 4 x 2 of 64 x 64 wave tiles (64 accumulator VGPRs), BK = 32, three 48 KiB stages
 // [A_hi 256 rows | A_lo 256 rows | W_hi 128 rows | W_lo 128 rows] x 64 B; per k-step and wave 6 LDS-DMA pieces (2 + 2 + 1 + 1), 16
-// fragment reads and 48 MFMAs.  Schedule, swizzle and persistence are gemm_w2.hip's: two wave groups one barrier slot apart, step t + 2
-// issued in iteration t, counted vmcnt(6), blocks walk tiles b, b + grid, ... with the next tile's first two steps fetched under
-// the epilogue; LDS-DMA through buffer resources (bload16 / make_rsrc, gemm_common.h: rows past M read zeros).
+// fragment reads and 48 MFMAs.  Schedule, swizzle and persistence: gemm_pingpong.h (counted-wait family) - step t + 2 issued in
+// iteration t, counted vmcnt(6), the next tile's first two steps fetched under the epilogue; LDS-DMA through buffer resources
+// (bload16 / make_rsrc, gemm_common.h: rows past M read zeros).
 #include "gemm_common.h"
 
 extern int g_w2_persist, g_x3_persist;
@@ -31,42 +31,31 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_kernel(KArgs p) {
     const int Kl = p.K / 3;                             // logical depth; A rows are [hi | lo | hi] (3 Kl), W rows [hi | hi | lo]
     p.K = Kl;
     clamp_live_rows(p.m_dev, p.M);                      // device-side live row count: the launcher runs one block per tile then
-    auto map_tile = [&](int vb, int& m0, int& n0) {
-        int tm, tn;
-        grouped_tile(xcd_remap(vb, p.nwg), p.group_m, p.tiles_m, p.tiles_n, tm, tn);
-        m0 = tm * TM;
-        n0 = tn * TN;
-    };
     const int nk = Kl / BK2;
     const unsigned a_lo_off = (unsigned)Kl * 2, w_lo_off = (unsigned)Kl * 4;      // byte offsets of the lo column blocks in a row
 
-    int vb = blockIdx.x, m0, n0;
-    map_tile(vb, m0, n0);
-    if (m0 >= p.M) return;
-    int base = 0;                                       // (global index of the current tile's step 0) mod 3
-    bool first = true;
+    PpWalk<NST, TM, TN> w(p.nwg, p.group_m, p.tiles_m, p.tiles_n, nk);
+    if (w.m0 >= p.M) return;
     for (;;) {
-        const bool has_next = vb + (int)gridDim.x < p.nwg;
+        const bool has_next = w.has_next();
+        const int m0 = w.m0, n0 = w.n0;
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        // pieces: 16 rows x 64 B; lane l -> row l >> 2, physical slot l & 3 <- logical chunk (l & 3) ^ f(row >> 2), f(g) = (-g) & 3
-        const int prow = ln >> 2, pchk = (ln & 3) ^ ((4 - (ln >> 4)) & 3);
+        const PpLane32 L(ln);
         unsigned a_off[2];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) a_off[i] = ((unsigned)((wave * 2 + i) * 16 + prow) * p.lda + pchk * 8) * 2;
-        const unsigned w_off = ((unsigned)(wave * 16 + prow) * (3 * Kl) + pchk * 8) * 2;
-        const int fr = ln & 15, fq = ln >> 4;
-        const int fchk = (fq ^ ((4 - (fr >> 2)) & 3)) * 16;
-        const int a_frag = (wr * 64 + fr) * 64 + fchk;
-        const int w_frag = 2 * PA + (wc * 64 + fr) * 64 + fchk;
-        int m1 = m0, n1 = n0;                           // the next tile (the block's last tile re-fills its own first steps: nobody reads them)
-        if (has_next) map_tile(vb + (int)gridDim.x, m1, n1);
+        for (int i = 0; i < 2; ++i) a_off[i] = ((unsigned)((wave * 2 + i) * 16 + L.prow) * p.lda + L.pchk * 8) * 2;
+        const unsigned w_off = ((unsigned)(wave * 16 + L.prow) * (3 * Kl) + L.pchk * 8) * 2;
+        const int a_frag = (wr * 64 + L.fr) * 64 + L.fchk;
+        const int w_frag = 2 * PA + (wc * 64 + L.fr) * 64 + L.fchk;
+        int m1, n1;
+        w.next_origin(m1, n1);
         const size_t a_row = (size_t)p.lda * 2, w_row = (size_t)Kl * 6;
         const __amdgpu_buffer_rsrc_t r_a = make_rsrc(p.A + (size_t)m0 * a_row, (size_t)(p.M - m0) * a_row), r_w = make_rsrc(p.W + (size_t)n0 * w_row);
         const __amdgpu_buffer_rsrc_t r_a1 = make_rsrc(p.A + (size_t)m1 * a_row, (size_t)(p.M - m1) * a_row), r_w1 = make_rsrc(p.W + (size_t)n1 * w_row);
         // k-step x of the tile walk (x >= nk: step x - nk of the next tile): A_hi, A_lo (2 pieces each), W_hi, W_lo (1 each)
         auto issue_step = [&](int x) {
-            OFX_LDS char* stg = lds + ((base + x) % NST) * STAGE;
+            OFX_LDS char* stg = lds + w.stage(x) * STAGE;
             const bool nx = x >= nk;
             const __amdgpu_buffer_rsrc_t ra = nx ? r_a1 : r_a, rw = nx ? r_w1 : r_w;
             const unsigned koff = (unsigned)(nx ? x - nk : x) * BK2 * 2;
@@ -83,70 +72,53 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_kernel(KArgs p) {
             for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         v8 ah[4], al[4], wh[4], wl[4];
 
-#define OFX_X3_READ(STEP)                                                                                     \
-    {                                                                                                         \
-        OFX_LDS char* base_ = lds + ((base + (STEP)) % NST) * STAGE;                                          \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) { wh[j] = *(OFX_LDS v8*)(base_ + w_frag + j * 1024); wl[j] = *(OFX_LDS v8*)(base_ + PW + w_frag + j * 1024); } \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) { ah[i] = *(OFX_LDS v8*)(base_ + a_frag + i * 1024); al[i] = *(OFX_LDS v8*)(base_ + PA + a_frag + i * 1024); } \
-    }
-    // 48 MFMAs: per (activation fragment, weight fragment) hi.hi, lo.hi, hi.lo
-#define OFX_X3_MFMA()                                                                                         \
-    {                                                                                                         \
-        __builtin_amdgcn_s_setprio(1);                                                                        \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                         \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                   \
-                acc[i][j] = OpT<T>::mfma16(wh[j], ah[i], acc[i][j]);                                          \
-                acc[i][j] = OpT<T>::mfma16(wh[j], al[i], acc[i][j]);                                          \
-                acc[i][j] = OpT<T>::mfma16(wl[j], ah[i], acc[i][j]);                                          \
-            }                                                                                                 \
-        __builtin_amdgcn_s_setprio(0);                                                                        \
-    }
-        if (first) {
+        auto read = [&](int step) {
+            OFX_LDS char* stg = lds + w.stage(step) * STAGE;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { wh[j] = *(OFX_LDS v8*)(stg + w_frag + j * 1024); wl[j] = *(OFX_LDS v8*)(stg + PW + w_frag + j * 1024); }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { ah[i] = *(OFX_LDS v8*)(stg + a_frag + i * 1024); al[i] = *(OFX_LDS v8*)(stg + PA + a_frag + i * 1024); }
+        };
+        // 48 MFMAs: per (activation fragment, weight fragment) hi.hi, lo.hi, hi.lo
+        auto mfma = [&]() {
+            __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    acc[i][j] = OpT<T>::mfma16(wh[j], ah[i], acc[i][j]);
+                    acc[i][j] = OpT<T>::mfma16(wh[j], al[i], acc[i][j]);
+                    acc[i][j] = OpT<T>::mfma16(wl[j], ah[i], acc[i][j]);
+                }
+            __builtin_amdgcn_s_setprio(0);
+        };
+        if (w.first) {
             issue_step(0); issue_step(1);
             asm volatile("s_waitcnt vmcnt(6)" ::: "memory");        // step 0 landed (my pieces)
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // steps 0 and 1 (fetched under the previous epilogue) and that epilogue's stores
         }
         __builtin_amdgcn_s_barrier();                               // ---- end of slot 0
-        // group 0: slots 2t+1 (issue step t+2, read step t) and 2t+2 (multiply); group 1 one slot later (gemm_w2.hip)
-        if (grp == 0) {
+        // iteration t: issue step t + 2, read and multiply step t; the wait leaves the 6 pieces of step t + 2 in flight
+        auto run = [&](auto G) {
+            pp_group_begin<G.value>();
             int t = 0;
             do {
-                issue_step(t + 2);
-                OFX_X3_READ(t)
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-                OFX_X3_MFMA()
-                asm volatile("s_waitcnt vmcnt(6)" ::: "memory");    // my pieces of step t+1 landed (step t+2 stays in flight)
-                __builtin_amdgcn_s_barrier();
+                pp_slot<G.value, 6>([&] { issue_step(t + 2); }, [&] { read(t); }, mfma);
             } while (++t < nk);
-            __builtin_amdgcn_s_barrier();                           // closes group 1's last MFMA slot: every read of this tile's stages is done
-        } else {
-            __builtin_amdgcn_s_barrier();                           // slot 1: group 0 reads step 0
-            int t = 0;
-            do {
-                issue_step(t + 2);
-                OFX_X3_READ(t)
-                asm volatile("s_waitcnt vmcnt(6)" ::: "memory");    // my pieces of step t+1 landed: group 0 reads them in slot 2t+3
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-                OFX_X3_MFMA()
-                __builtin_amdgcn_s_barrier();
-            } while (++t < nk);
-        }
-#undef OFX_X3_READ
-#undef OFX_X3_MFMA
+            pp_group_end<G.value>();
+        };
+        if (grp == 0) run(std::integral_constant<int, 0>());
+        else run(std::integral_constant<int, 1>());
         // Epilogue staging: the stage of this tile's LAST step (8 x 4 KiB + the LayerNorm-fold statistics slots behind them); the fills of
         // steps nk, nk + 1 (the next tile's first steps, still landing) target the other two stages.
-        OFX_LDS char* estage = lds + ((base + nk - 1) % NST) * STAGE;
+        OFX_LDS char* estage = lds + w.epilogue_stage() * STAGE;
         OFX_LDS char* ep = estage + wave * EPI2_BYTES_PER_WAVE;
         OFX_LDS float* st = nullptr;
         if (p.row_stat && p.out_kind != 0) st = (OFX_LDS float*)(estage + 8 * EPI2_BYTES_PER_WAVE + wave * 1024);
         epilogue2_dispatch<T, 4, 4, 0>(p, ep, acc, m0 + wr * 64, n0 + wc * 64, ln, st);
         if (!has_next) break;
-        vb += gridDim.x; map_tile(vb, m0, n0); base = (base + nk) % NST; first = false;
+        w.advance();
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // the last tile's redundant fills have landed before the wave ends
 }

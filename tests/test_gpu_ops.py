@@ -116,6 +116,90 @@ def test_gemm_split_weights_persistent_grid_is_bit_identical_to_one_block_per_ti
     assert rel_err(outs[0].cpu().numpy(), A.double().cpu().numpy() @ Wv.T + bias.cpu().numpy()) < 2e-5
 
 
+def _recorded_kinds(lib):
+    """Kernel kinds (GemmKind, csrc/gemm_common.h) of the GEMM launches since ofx_profile_enable(1)."""
+    recs = (L.ProfRecord * 16)()
+    n = lib.ofx_profile_records(recs, 16)
+    ms, fl, cnt = (C.c_double * 4)(), (C.c_double * 4)(), (C.c_longlong * 4)()
+    L.check(lib.ofx_profile_read(ms, fl, cnt))
+    return [recs[i].kind for i in range(n)]
+
+
+PERSIST_M = 1300       # five full 256-row panels and one of 20 rows; with three column tiles 18 tiles: grids of 5 and 7 blocks walk 2-4 tiles each
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("K", [64, 128, 192])
+def test_gemm_three_products_persistent_grid_is_bit_identical_to_one_block_per_tile(dt, K):
+    """gemm_x3_kernel's walk over tiles (gemm_pingpong.h: PpWalk): one block per tile (knob 11 = 0) and odd grids of 5 and 7 blocks, in
+    which every block walks 2-4 of the 18 tiles, must agree bit for bit, and with float64 arithmetic on the rounded operands (the
+    criterion of test_gemm_three_products_from_operand_tiles_loaded_once, fp32 output + bias).  Logical depths: 64 (two k-steps, the
+    shallowest: both steps of a tile come from the previous tile's fills), 128 (four: `base` runs through every residue mod 3) and
+    192 (six) - the dispatcher takes three-product depths in multiples of 64 only (3 K must be a multiple of the 64-deep k-tile of
+    the K-concatenated kernels), so 128 and 192 stand for the 96 and 160 one would pick from the kernel alone."""
+    M, N = PERSIST_M, 384
+    g = np.random.default_rng(K + 1)
+    td = torch.bfloat16 if dt == "bf16" else torch.float16
+    Af = torch.from_numpy(g.standard_normal((M, K), dtype=np.float32)).cuda()
+    hi = Af.to(td); lo = (Af - hi.float()).to(td)
+    A3 = torch.cat([hi, lo, hi], 1).contiguous()
+    Wf = dev((g.standard_normal((N, K), dtype=np.float32) / np.float32(np.sqrt(K))).astype(np.float32))
+    W3 = torch.empty(N, 3 * K, dtype=td, device="cuda")
+    lib = L.load()
+    L.check(lib.ofx_convert(Wf.data_ptr(), W3.data_ptr(), N, K, 2, DT[dt], stream()))
+    whi, wlo = W3[:, :K].double(), W3[:, 2 * K:].double()
+    bias = dev(g.standard_normal(N, dtype=np.float32))
+    want = (hi.double() @ whi.T + lo.double() @ whi.T + hi.double() @ wlo.T).cpu().numpy() + bias.double().cpu().numpy()
+    outs = []
+    lib.ofx_tune(15, 2)
+    lib.ofx_profile_enable(1)
+    try:
+        for persist in (0, 5, 7):
+            lib.ofx_tune(11, persist)
+            out = torch.full((M, N), float("nan"), device="cuda")
+            L.check(lib.ofx_gemm_x3(A3.data_ptr(), W3.data_ptr(), out.data_ptr(), bias.data_ptr(), None, M, N, K, 3 * K, N, 0, 0, 0, DT[dt], stream()))
+            torch.cuda.synchronize()
+            outs.append(out)
+        kinds = _recorded_kinds(lib)
+    finally:
+        lib.ofx_profile_enable(0); lib.ofx_tune(11, -1); lib.ofx_tune(15, 1)
+    assert kinds == [9, 9, 9]                                        # gemm_x3_kernel ran, not the K-concatenated path (whose grid is no walk)
+    assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+    assert rel_err(outs[0].double().cpu().numpy(), want) < 2e-5
+
+
+@pytest.mark.parametrize("K", [128, 256, 384])
+def test_gemm_split_weights_fp8_correction_persistent_grid_is_bit_identical_to_one_block_per_tile(K):
+    """gemm_w2f8_kernel's walk over tiles (four stages, one to three 128-deep super-steps per tile): the same three grids bit for bit,
+    and the criterion of test_gemm_split_weights_fp8_correction - exact arithmetic on the quantised operands."""
+    M, N = PERSIST_M, 768
+    g = np.random.default_rng(K + 2)
+    A = to_op(g.standard_normal((M, K), dtype=np.float32), "f16")
+    W2, _ = _split_w((g.standard_normal((N, K), dtype=np.float32) / np.float32(np.sqrt(K))).astype(np.float32), "f16")
+    W8, sc, lo_seen, _ = _pack_lo8(W2, N, K)
+    bias = dev(g.standard_normal(N, dtype=np.float32))
+    res = dev(g.standard_normal((M, N), dtype=np.float32))
+    lib = L.load()
+    outs = []
+    lib.ofx_tune(2, 6)
+    lib.ofx_profile_enable(1)
+    try:
+        for persist in (0, 5, 7):
+            lib.ofx_tune(11, persist)
+            out = torch.full((M, N), float("nan"), device="cuda")
+            L.check(lib.ofx_gemm_w2f8(A.data_ptr(), W2.data_ptr(), W8.data_ptr(), sc.data_ptr(), out.data_ptr(), bias.data_ptr(), res.data_ptr(), M, N, K, K, N, N, 0, 0, stream()))
+            torch.cuda.synchronize()
+            outs.append(out)
+        kinds = _recorded_kinds(lib)
+    finally:
+        lib.ofx_profile_enable(0); lib.ofx_tune(11, -1); lib.ofx_tune(2, 0)
+    assert kinds == [8, 8, 8]                                        # gemm_w2f8_kernel ran, not gemm_w2_kernel
+    assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+    A8 = A.float().clamp(-57344.0, 57344.0).to(torch.float8_e5m2).double().cpu().numpy()
+    want = A.double().cpu().numpy() @ W2[:, :K].double().cpu().numpy().T + A8 @ lo_seen.T + bias.cpu().numpy() + res.cpu().numpy()
+    assert rel_err(outs[0].cpu().numpy(), want) < 2e-5
+
+
 def test_profile_records_carry_shape_kernel_and_algorithmic_bytes():
     """ofx_profile_records (what bench.py's roofline block is built from): a GEMM launch is recorded with its logical shape, the
     kernel that ran, its products per term and the ALGORITHMIC HBM bytes its own epilogue configuration implies - A once, the weight
