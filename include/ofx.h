@@ -329,6 +329,10 @@ int ofx_gemm_x3(const void* A3, const void* W3, void* C, const float* bias, cons
 int ofx_pack_lo8(const void* W2, void* W8, void* scale8, int N, int K, ofx_stream stream);
 int ofx_gemm_w2f8(const void* A, const void* W2, const void* W8, const void* scale8, void* C, const float* bias, const float* resid, int M, int N, int K,
                   int lda, int ldc, int ldr, int act, int out_kind, ofx_stream stream);
+/* The same as a LayerNorm-fold consumer, as the ViT layers launch it for qkv and fc1: C [M, ldc >= N] in the operand type (f16) =
+ * act( (A hi^T + bf8(A) fp8(lo)^T - col_sum[n] mean[m]) rstd[m] + bias[n] ), row_stat [M, 2] = (mean, rstd) per row, col_sum [N].  No residual. */
+int ofx_gemm_w2f8_fold(const void* A, const void* W2, const void* W8, const void* scale8, void* C, const float* bias, const float* row_stat, const float* col_sum,
+                       int M, int N, int K, int lda, int ldc, int act, ofx_stream stream);
 /* Weight-gradient GEMM of the training step: C[M,N] fp32 = sum_k A[k, m] * B[k, n]; A [K, lda] and B [K, ldb] row-major
  * operand-type matrices whose ROW index is contracted (dW = dY^T X without transposed copies).  M, N multiples of 256.
  * k_dev: optional device-side live row count (<= K).  Both operands must be readable up to round_up(K, 64) rows.

@@ -1372,6 +1372,13 @@ extern "C" int ofx_gemm_w2f8(const void* A, const void* W2, const void* W8, cons
     GemmArgs g = op_gemm(A, W2, C, bias, resid, M, N, 2 * K, lda, ldc, ldr, act, out_kind); g.a_wrap = K; g.W8 = W8; g.w8_scale = scale8;
     return ofx_launch_gemm(g, OFX_F16, (hipStream_t)stream);
 }
+extern "C" int ofx_gemm_w2f8_fold(const void* A, const void* W2, const void* W8, const void* scale8, void* C, const float* bias, const float* row_stat, const float* col_sum,
+                                  int M, int N, int K, int lda, int ldc, int act, ofx_stream stream) {
+    OFX_REQUIRE(row_stat && col_sum, OFX_EINVAL, "gemm_w2f8_fold: row_stat and col_sum are required");
+    GemmArgs g = op_gemm(A, W2, C, bias, nullptr, M, N, 2 * K, lda, ldc, 0, act, OFX_OUT_OP); g.a_wrap = K; g.W8 = W8; g.w8_scale = scale8;
+    g.row_stat = row_stat; g.col_sum = col_sum; g.stat_ld = 1;
+    return ofx_launch_gemm(g, OFX_F16, (hipStream_t)stream);
+}
 extern "C" size_t ofx_gemm_splitk_ws(int M, int N, int K) { return ofx_gemm_splitk_bytes(M, N, K); }
 extern "C" int ofx_gemm_splitk(const void* A, const void* W, void* C, const float* bias, const float* resid, int M, int N, int K,
                                int lda, int ldc, int ldr, int act, int out_kind, int op_dtype, void* slab, size_t slab_bytes, ofx_stream stream) {

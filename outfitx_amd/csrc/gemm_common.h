@@ -161,6 +161,9 @@ __device__ __forceinline__ void epilogue(const KArgs& p, OFX_LDS float* ep, int 
 // once, so the LDS-DMA of k-tile t+2 is issued before the 64 MFMAs of k-tile t and two k-tiles
 // (128 KiB per CU) stay in flight.  LDS: 2 stages x 64 KiB + 32 KiB epilogue staging = 160 KiB.
 constexpr int EPI2_BYTES_PER_WAVE = 16 * 64 * 4;       // 16 rows x 64 fp32, XOR-swizzled, no padding
+// A wave's prefetched per-tile epilogue constants (gemm_w2f8.hip requests them at the top of a tile), as floats in its private LDS slot:
+// row r's (mean, rstd) at 2 r (64 rows), the bias of column c at EPI_CONST_BIAS + c and its column sum at EPI_CONST_CSUM + c (128 columns)
+constexpr int EPI_CONST_BIAS = 128, EPI_CONST_CSUM = 256, EPI_CONST_BYTES_PER_WAVE = 2048;
 
 // Epilogue of the 128x64 wave tile: 8 passes of 16 rows through the wave's private LDS staging (XOR-swizzled
 // 16-B chunks), leaving as whole 128/256-byte row segments with 16-byte stores (the store tail is issue-bound:
@@ -179,9 +182,11 @@ __device__ __forceinline__ float act_apply(float v) {
 // rewritten in place with per-segment statistics - no fp32 copy of the stream.
 // NP x 16 rows by 64 columns of the wave's accumulators: acc[i][J0 + j], i < NP passes, j < 4 column fragments (the 128x64 wave tile
 // is NP = 8, JW = 4, J0 = 0; a 64x128 wave tile drains as two halves NP = 4, JW = 8, J0 = 0 / 4).
+// cst: the wave's slot of prefetched per-tile constants (EPI_CONST_*; gn0 = the slot's first column + 16 J0, and st == cst: the row
+// statistics are in it already), or null: bias, column sums and row statistics come from memory.
 template <typename T, int ACT, int FOLD = 0, int RAMP = 0, int NP = 8, int JW = 4, int J0 = 0>
 __device__ __forceinline__ void epilogue2(const KArgs& p, OFX_LDS char* ep, f32x4 (&acc)[NP][JW], int gm0, int gn0, int lane,
-                                          OFX_LDS float* st = nullptr) {
+                                          OFX_LDS float* st = nullptr, OFX_LDS const float* cst = nullptr) {
     typedef typename OpT<T>::v8 v8;
     const int fr = lane & 15, fq = lane >> 4;
     if (FOLD != 3 && p.out_kind == 0) {
@@ -189,7 +194,8 @@ __device__ __forceinline__ void epilogue2(const KArgs& p, OFX_LDS char* ep, f32x
         const int chunk = lane & 15, rsub = lane >> 4;
         const int gn = gn0 + chunk * 4;
         f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
-        if (p.bias) bias4 = *(const f32x4*)(p.bias + gn);
+        if (cst) bias4 = *(OFX_LDS const f32x4*)(cst + EPI_CONST_BIAS + J0 * 16 + chunk * 4);
+        else if (p.bias) bias4 = *(const f32x4*)(p.bias + gn);
         const bool has_res = p.resid != nullptr;
         f32x4 res[DEPTH + 1][4];
         auto fetch = [&](int pass, f32x4 (&dst)[4]) {
@@ -246,14 +252,20 @@ __device__ __forceinline__ void epilogue2(const KArgs& p, OFX_LDS char* ep, f32x
         const int c8 = lane & 7, rsub = lane >> 3;          // 8 columns per lane, 8 rows per wave-instruction
         const int gn = gn0 + c8 * 8;
         f32x4 b0 = {0.f, 0.f, 0.f, 0.f}, b1 = b0;
-        if (p.bias) { b0 = *(const f32x4*)(p.bias + gn); b1 = *(const f32x4*)(p.bias + gn + 4); }
         f32x4 cs0 = {0.f, 0.f, 0.f, 0.f}, cs1 = cs0;
-        if (FOLD == 2) { cs0 = *(const f32x4*)(p.col_sum + gn); cs1 = *(const f32x4*)(p.col_sum + gn + 4); }
+        if (cst) {
+            OFX_LDS const float* cc = cst + J0 * 16 + c8 * 8;
+            b0 = *(OFX_LDS const f32x4*)(cc + EPI_CONST_BIAS); b1 = *(OFX_LDS const f32x4*)(cc + EPI_CONST_BIAS + 4);
+            if (FOLD == 2) { cs0 = *(OFX_LDS const f32x4*)(cc + EPI_CONST_CSUM); cs1 = *(OFX_LDS const f32x4*)(cc + EPI_CONST_CSUM + 4); }
+        } else {
+            if (p.bias) { b0 = *(const f32x4*)(p.bias + gn); b1 = *(const f32x4*)(p.bias + gn + 4); }
+            if (FOLD == 2) { cs0 = *(const f32x4*)(p.col_sum + gn); cs1 = *(const f32x4*)(p.col_sum + gn + 4); }
+        }
         // FOLD 2 with a staging slot: the wave's 128 (mean, rstd) pairs go through LDS - one 16-byte global load per lane (rows
         // 2 lane, 2 lane + 1) instead of an 8-byte global load per row, lane and pass (the epilogues are bound by their memory
         // instructions)
         const bool st_lds = FOLD == 2 && st != nullptr;
-        if (st_lds) {
+        if (st_lds && !cst) {
             const int ra = min(gm0 + 2 * lane, p.M - 1), rb = min(gm0 + 2 * lane + 1, p.M - 1);
             f32x4 pr;
             if (p.stat_ld == 1 && rb == ra + 1) pr = *(const f32x4*)(p.row_stat + 2 * (size_t)ra);
@@ -370,25 +382,15 @@ __device__ __forceinline__ void epilogue2(const KArgs& p, OFX_LDS char* ep, f32x
 // 8 consecutive columns of block B (tools/permlane_probe.hip pins the instruction's row mapping).  A store instruction then covers 16 rows x 64 contiguous
 // bytes; the two column-block pairs of a 64-column half complete every 128-byte line back to back.  Stores go through a buffer resource sized to the M
 // valid rows: rows past M fall outside it and are dropped by the hardware (no per-row predicate, no clamping).  FOLD: 0 bias (+ activation), 2 LayerNorm-fold
-// consumer ((acc - colsum mean) rstd + bias', row statistics through the wave's 1 KiB LDS slot `st` as in epilogue2).
+// consumer ((acc - colsum mean) rstd + bias').  Every constant - row statistics, bias, column sums - comes from the wave's LDS slot `cst` (EPI_CONST_*),
+// which the kernel fills from registers requested at the top of the tile: no global load, hence no vector-memory wait, between the main loop and the stores.
 template <typename T, int ACT, int FOLD, int NP, int JW>
-__device__ __forceinline__ void epilogue_direct(const KArgs& p, f32x4 (&acc)[NP][JW], int gm0, int gn0, int lane, OFX_LDS float* st) {
+__device__ __forceinline__ void epilogue_direct(const KArgs& p, f32x4 (&acc)[NP][JW], int gm0, int gn0, int lane, OFX_LDS const float* cst) {
     static_assert(JW % 4 == 0 && (FOLD == 0 || FOLD == 2), "whole 64-column halves; bias or LayerNorm-fold consumer");
     typedef T t2 __attribute__((ext_vector_type(2)));
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     const int fr = lane & 15, fq = lane >> 4;
-    if (FOLD == 2) {            // the wave's (mean, rstd) pairs: one 16-byte load per lane (rows 2 lane, 2 lane + 1) -> LDS slot
-        const int ra = min(gm0 + 2 * lane, p.M - 1), rb = min(gm0 + 2 * lane + 1, p.M - 1);
-        f32x4 pr;
-        if (p.stat_ld == 1 && rb == ra + 1) pr = *(const f32x4*)(p.row_stat + 2 * (size_t)ra);
-        else {
-            const f32x2 a2 = *(const f32x2*)(p.row_stat + 2 * (size_t)ra * p.stat_ld), b2 = *(const f32x2*)(p.row_stat + 2 * (size_t)rb * p.stat_ld);
-            pr = f32x4{a2[0], a2[1], b2[0], b2[1]};
-        }
-        *(OFX_LDS f32x4*)(st + 4 * lane) = pr;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
     const __amdgpu_buffer_rsrc_t rc = make_rsrc(p.C, (size_t)p.M * p.ldc * 2);
     // this lane's bytes of pass 0, column-block pair 0: row gm0 + fr, column gn0 + (fq & 1) 16 + (fq >> 1) 8
     const unsigned vo = ((unsigned)(gm0 + fr) * (unsigned)p.ldc + (unsigned)(gn0 + (fq & 1) * 16 + (fq >> 1) * 8)) * 2u;
@@ -398,14 +400,14 @@ __device__ __forceinline__ void epilogue_direct(const KArgs& p, f32x4 (&acc)[NP]
         f32x4 bb[4], cs[4];
 #pragma unroll
         for (int jb = 0; jb < 4; ++jb) {
-            const int gn = gn0 + (h * 4 + jb) * 16 + fq * 4;
-            bb[jb] = p.bias ? *(const f32x4*)(p.bias + gn) : f32x4{0.f, 0.f, 0.f, 0.f};
-            cs[jb] = FOLD == 2 ? *(const f32x4*)(p.col_sum + gn) : f32x4{0.f, 0.f, 0.f, 0.f};
+            OFX_LDS const float* cc = cst + (h * 4 + jb) * 16 + fq * 4;
+            bb[jb] = *(OFX_LDS const f32x4*)(cc + EPI_CONST_BIAS);
+            cs[jb] = FOLD == 2 ? *(OFX_LDS const f32x4*)(cc + EPI_CONST_CSUM) : f32x4{0.f, 0.f, 0.f, 0.f};
         }
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
             float mu = 0.f, rs = 1.f;
-            if (FOLD == 2) { const f32x2 ms = *(OFX_LDS f32x2*)(st + 2 * (i * 16 + fr)); mu = ms[0]; rs = ms[1]; }
+            if (FOLD == 2) { const f32x2 ms = *(OFX_LDS const f32x2*)(cst + 2 * (i * 16 + fr)); mu = ms[0]; rs = ms[1]; }
 #pragma unroll
             for (int jp = 0; jp < 2; ++jp) {
                 f32x4 va = acc[i][h * 4 + 2 * jp], vb = acc[i][h * 4 + 2 * jp + 1];
@@ -427,12 +429,11 @@ __device__ __forceinline__ void epilogue_direct(const KArgs& p, f32x4 (&acc)[NP]
 }
 
 template <typename T, int NP, int JW>
-__device__ __forceinline__ bool epilogue_direct_dispatch(const KArgs& p, f32x4 (&acc)[NP][JW], int gm0, int gn0, int lane, OFX_LDS float* st) {
+__device__ __forceinline__ bool epilogue_direct_dispatch(const KArgs& p, f32x4 (&acc)[NP][JW], int gm0, int gn0, int lane, OFX_LDS const float* cst) {
     if (!p.epi_direct || p.out_kind != 1 || p.resid || p.xlo || p.aux_out || p.drop.thresh || p.n_valid != p.N) return false;
     if ((size_t)p.M * p.ldc * 2 >= 0x7fffffff) return false;
-#define OFX_EPD(ACT_, FOLD_) { epilogue_direct<T, ACT_, FOLD_, NP, JW>(p, acc, gm0, gn0, lane, st); return true; }
+#define OFX_EPD(ACT_, FOLD_) { epilogue_direct<T, ACT_, FOLD_, NP, JW>(p, acc, gm0, gn0, lane, cst); return true; }
     if (p.row_stat) {
-        if (!st) return false;
         switch (p.act) {
             case OFX_ACT_QUICK_GELU: OFX_EPD(OFX_ACT_QUICK_GELU, 2)
             case OFX_ACT_GELU: OFX_EPD(OFX_ACT_GELU, 2)
@@ -451,27 +452,27 @@ __device__ __forceinline__ bool epilogue_direct_dispatch(const KArgs& p, f32x4 (
 
 template <typename T, int NP = 8, int JW = 4, int J0 = 0>
 __device__ __forceinline__ void epilogue2_dispatch(const KArgs& p, OFX_LDS char* ep, f32x4 (&acc)[NP][JW], int gm0, int gn0, int lane,
-                                                   OFX_LDS float* st = nullptr) {
+                                                   OFX_LDS float* st = nullptr, OFX_LDS const float* cst = nullptr) {
     if (p.row_stat) {                                  // LayerNorm-fold consumer: towers only (no residual, no dropout, no tape)
         switch (p.act) {
-            case OFX_ACT_QUICK_GELU: epilogue2<T, OFX_ACT_QUICK_GELU, 2, 0, NP, JW, J0>(p, ep, acc, gm0, gn0, lane, st); break;
-            case OFX_ACT_GELU: epilogue2<T, OFX_ACT_GELU, 2, 0, NP, JW, J0>(p, ep, acc, gm0, gn0, lane, st); break;
-            default: epilogue2<T, OFX_ACT_NONE, 2, 0, NP, JW, J0>(p, ep, acc, gm0, gn0, lane, st); break;
+            case OFX_ACT_QUICK_GELU: epilogue2<T, OFX_ACT_QUICK_GELU, 2, 0, NP, JW, J0>(p, ep, acc, gm0, gn0, lane, st, cst); break;
+            case OFX_ACT_GELU: epilogue2<T, OFX_ACT_GELU, 2, 0, NP, JW, J0>(p, ep, acc, gm0, gn0, lane, st, cst); break;
+            default: epilogue2<T, OFX_ACT_NONE, 2, 0, NP, JW, J0>(p, ep, acc, gm0, gn0, lane, st, cst); break;
         }
         return;
     }
     if (p.xlo) {                                       // LayerNorm-fold producer: (xb_out, xlo) stream + stat_part (ofx_launch_gemm checks the triple)
-        epilogue2<T, OFX_ACT_NONE, 3, 1, NP, JW, J0>(p, ep, acc, gm0, gn0, lane);
+        epilogue2<T, OFX_ACT_NONE, 3, 1, NP, JW, J0>(p, ep, acc, gm0, gn0, lane, nullptr, cst);
         return;
     }
     switch (p.act) {
-        case OFX_ACT_QUICK_GELU: epilogue2<T, OFX_ACT_QUICK_GELU, 0, 0, NP, JW, J0>(p, ep, acc, gm0, gn0, lane); break;
-        case OFX_ACT_GELU: epilogue2<T, OFX_ACT_GELU, 0, 0, NP, JW, J0>(p, ep, acc, gm0, gn0, lane); break;
-        case OFX_ACT_MISH: epilogue2<T, OFX_ACT_MISH, 0, 0, NP, JW, J0>(p, ep, acc, gm0, gn0, lane); break;
-        case OFX_ACT_MISH_GRAD: epilogue2<T, OFX_ACT_MISH_GRAD, 0, 0, NP, JW, J0>(p, ep, acc, gm0, gn0, lane); break;
+        case OFX_ACT_QUICK_GELU: epilogue2<T, OFX_ACT_QUICK_GELU, 0, 0, NP, JW, J0>(p, ep, acc, gm0, gn0, lane, nullptr, cst); break;
+        case OFX_ACT_GELU: epilogue2<T, OFX_ACT_GELU, 0, 0, NP, JW, J0>(p, ep, acc, gm0, gn0, lane, nullptr, cst); break;
+        case OFX_ACT_MISH: epilogue2<T, OFX_ACT_MISH, 0, 0, NP, JW, J0>(p, ep, acc, gm0, gn0, lane, nullptr, cst); break;
+        case OFX_ACT_MISH_GRAD: epilogue2<T, OFX_ACT_MISH_GRAD, 0, 0, NP, JW, J0>(p, ep, acc, gm0, gn0, lane, nullptr, cst); break;
         default:      // fp32 residual outputs (out-proj / fc2): ramped residual prefetch, +1.2 % on those GEMMs (tools/gemm_bench.py)
-            if (p.resid && p.out_kind == 0) epilogue2<T, OFX_ACT_NONE, 0, 1, NP, JW, J0>(p, ep, acc, gm0, gn0, lane);
-            else epilogue2<T, OFX_ACT_NONE, 0, 0, NP, JW, J0>(p, ep, acc, gm0, gn0, lane);
+            if (p.resid && p.out_kind == 0) epilogue2<T, OFX_ACT_NONE, 0, 1, NP, JW, J0>(p, ep, acc, gm0, gn0, lane, nullptr, cst);
+            else epilogue2<T, OFX_ACT_NONE, 0, 0, NP, JW, J0>(p, ep, acc, gm0, gn0, lane, nullptr, cst);
             break;
     }
 }

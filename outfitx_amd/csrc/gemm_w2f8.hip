@@ -42,7 +42,8 @@
 //   x(c) = (((c >> 1) & 3) << 1) | (c >> 3): conflict-free for ds_read_b128's lane groups with 128-byte rows (each lane reads the two
 //   chunks 2 g, 2 g + 1 of row lane & 15).
 // Epilogue staging: the stage of the tile's last k-step (8 x 4 KiB; the other three hold the next tile's first steps); the
-// LayerNorm-fold statistics slots sit in the fp8 buffer, which is idle between the tile's last fp8 slot and the next tile's refill.
+// waves' slots of epilogue constants (8 x 2 KiB: row statistics, bias, column sums) sit in the fp8 buffer, which is idle between the
+// tile's last fp8 slot and the next tile's refill.
 #include "gemm_common.h"
 
 extern int g_w2_persist, g_epi_direct;
@@ -109,6 +110,20 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
         int m1, n1;
         w.next_origin(m1, n1);
         int sc_lo = (int)(unsigned)sc8, sc_hi = (int)(unsigned)(sc8 >> 32);
+        // The epilogue's constants of this wave's 64 x 128 sub-tile, requested HERE: lane l takes row l's (mean, rstd), lanes 0-31 four biases
+        // each, lanes 32-63 four column sums each (six registers).  A load at the epilogue's own top is waited for with everything older in
+        // the vector-memory queue - the next tile's first k-steps of LDS-DMA, issued just before - and one per 64-column half also with the
+        // stores of the half before.  From inline assembly, so that the compiler plants no vmcnt(0) of its own where the values are used: in
+        // issue order they are older than every piece of iteration 0, whose counted wait (the first tile: the wait below) retires them.
+        f32x2 ep_ms = {0.f, 1.f};
+        f32x4 ep_c4 = {0.f, 0.f, 0.f, 0.f};
+        {
+            const float* sp = p.row_stat + 2 * (size_t)min(m0 + wr * 64 + ln, p.M - 1) * p.stat_ld;
+            if (p.row_stat) asm volatile("global_load_dwordx2 %0, %1, off" : "+v"(ep_ms) : "v"(sp) : "memory");
+            const float* cb = p.row_stat && ln >= 32 ? p.col_sum : p.bias;
+            const float* cp = cb + n0 + wc * 128 + (ln & 31) * 4;
+            if (cb) asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(ep_c4) : "v"(cp) : "memory");
+        }
 
         // LDS-DMA pieces: the two A and two W_hi pieces of a k-step (KOFF = its byte offset in the k-contiguous rows) and quarter Q of
         // this wave's rows of super-step SUP's fp8 weights
@@ -237,18 +252,20 @@ __global__ __launch_bounds__(512, 2) void gemm_w2f8_kernel(KArgs p) {
 #undef OFX_F8_ISSUE_AW
 #undef OFX_F8_ISSUE_W8
         asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 0");     // the epilogue's f32 -> f16 casts keep the default overflow behaviour
-        // Epilogue staging: the stage of this tile's LAST k-step (every read of it is over, no fill targets it); statistics slots of the
-        // LayerNorm-fold consumers: the fp8 buffer (idle until the next tile's first iterations refill it, behind the barrier of its slot 0).
+        // Epilogue staging: the stage of this tile's LAST k-step (every read of it is over, no fill targets it); the slots of epilogue
+        // constants: the fp8 buffer (idle until the next tile's first iterations refill it, behind the barrier of its slot 0).
         OFX_LDS char* estage = lds + w.epilogue_stage() * STAGE;
         OFX_LDS char* ep = estage + wave * EPI2_BYTES_PER_WAVE;
         const int gm0 = m0 + wr * 64, gn0 = n0 + wc * 128;
-        OFX_LDS float* st = nullptr;
-        if (p.row_stat && p.out_kind != 0) st = (OFX_LDS float*)(lds + W8BASE + wave * 1024);
+        OFX_LDS float* cst = (OFX_LDS float*)(lds + W8BASE + wave * EPI_CONST_BYTES_PER_WAVE);
+        *(OFX_LDS f32x2*)(cst + 2 * ln) = ep_ms;                       // row ln
+        *(OFX_LDS f32x4*)(cst + EPI_CONST_BIAS + 4 * ln) = ep_c4;      // lanes 32-63 land at EPI_CONST_CSUM + 4 (ln - 32)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         sc8 = *(const unsigned long long*)(p.w8_scale + ((size_t)((n1 >> 7) + wc) * 16 + (ln & 15)) * 8);     // the next tile's scale bytes (this tile's own again on the last one)
-        OFX_LDS float* st2 = (p.row_stat && p.out_kind != 0) ? st : nullptr;
-        if (!epilogue_direct_dispatch<T, 4, 8>(p, acc, gm0, gn0, ln, st2)) {
-            epilogue2_dispatch<T, 4, 8, 0>(p, ep, acc, gm0, gn0, ln, st);
-            epilogue2_dispatch<T, 4, 8, 4>(p, ep, acc, gm0, gn0 + 64, ln, st);
+        OFX_LDS float* st = (p.row_stat && p.out_kind != 0) ? cst : nullptr;
+        if (!epilogue_direct_dispatch<T, 4, 8>(p, acc, gm0, gn0, ln, cst)) {
+            epilogue2_dispatch<T, 4, 8, 0>(p, ep, acc, gm0, gn0, ln, st, cst);
+            epilogue2_dispatch<T, 4, 8, 4>(p, ep, acc, gm0, gn0 + 64, ln, st, cst);
         }
         if (!has_next) break;
         full_prev = m0 + TM <= p.M;
