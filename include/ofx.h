@@ -258,6 +258,39 @@ size_t ofx_set_rank_loss_ws_bytes(int B, int K, int D);
 int ofx_set_rank_loss(const float* y, const float* y_hat, const float* neg, const uint8_t* neg_mask, int B, int K, int D, float margin,
                       float upstream, float* loss, float* dy_hat, float* d_pos, float* d_neg, void* ws, size_t ws_bytes, ofx_stream stream);
 
+/* ------------------------------------------------------------------ optimizer step ---------- */
+/* The accumulation boundary of the trainers (compatibility_prediction_trainer.py:70-80 = complementary_item_retrieval_trainer.py:89-99):
+ * torch.nn.utils.clip_grad_norm_(max_norm) -> torch.optim.AdamW step (amsgrad off, maximize off) -> zero the gradient, over ONE flat
+ * fp32 gradient arena (outfitx_amd/trainer.py FlatGrads).  Stateless (no handle): with ofx_*_train_bwd* writing the gradients, a caller
+ * without torch can train.
+ *   grad, exp_avg, exp_avg_sq: arenas of n_arena floats in the same layout - every tensor starts at a multiple of 64 floats, the gaps
+ *   between tensors are padding (zero).  The parameters stay wherever the caller keeps them: segments[i] says that arena floats
+ *   [offset, offset + numel) belong to the fp32 tensor at `param`.  The table is a DEVICE array, sorted by offset, non-overlapping, every
+ *   offset a multiple of 64 and every param 16-byte aligned; it is only read, so it can be built once.  The host cannot see it and
+ *   checks none of this.
+ *   g     = grad_scale * grad                        (whole arena, padding included; grad_scale = 1 / world folds the mean over ranks in)
+ *   norm  = ||g||_2;  *grad_norm = norm              (before clipping, what clip_grad_norm_ returns)
+ *   norm not finite:  *skipped = 1, grad := 0, and the parameters, both moments and *step are left as they were
+ *   otherwise:        *skipped = 0;  t = *step + 1;  *step = t      (*step is a float, as torch keeps it; 0 before the first step)
+ *                     g *= min(max_norm / (norm + 1e-6), 1)
+ *                     param *= 1 - lr * weight_decay
+ *                     exp_avg += (g - exp_avg) * (1 - beta1);   exp_avg_sq = beta2 * exp_avg_sq + (1 - beta2) * g * g
+ *                     param -= lr / (1 - beta1^t) * exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - beta2^t) + eps)
+ *                     grad := 0                      (every float of the arena, padding included)
+ *   Element arithmetic is fp32; the sum of squares, 1 - lr * weight_decay, the bias corrections 1 - beta^t and the clip coefficient
+ *   (from the fp32 norm it reports) are computed in double from the double arguments, as torch computes them from Python floats.
+ *   Nothing is read or written beyond param + numel; the moments' padding is not written.  grad_norm, skipped, step: 1 element each.
+ * Supported: 1 <= n_segments <= 1024, n_arena > 0 and a multiple of 64 (else OFX_ESHAPE); a NULL pointer, or grad / exp_avg /
+ * exp_avg_sq / ws not 16-byte aligned: OFX_EINVAL; ws_bytes below the size function: OFX_EWORKSPACE.  A rejected call launches nothing.
+ * Workspace: the size function below (0 for an unsupported n_arena); contents need not survive the call.  Two launches on `stream`, no
+ * allocation, copy or wait (capturable); deterministic - no atomics, two calls from the same state return the same bits
+ * (outfitx_amd/csrc/optim.hip). */
+typedef struct ofx_opt_segment { float* param; long long offset; long long numel; } ofx_opt_segment;
+size_t ofx_adamw_step_ws_bytes(long long n_arena);
+int ofx_adamw_step(const ofx_opt_segment* segments, int n_segments, float* grad, float* exp_avg, float* exp_avg_sq, long long n_arena,
+                   float* step, double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm, double grad_scale,
+                   float* grad_norm, int* skipped, void* ws, size_t ws_bytes, ofx_stream stream);
+
 /* ------------------------------------------------------------------ profiling --------------- */
 /* HIP-event timing of every launch, by category {0 GEMM, 1 norm/embed, 2 attention, 3 other}.
  * enable(mask) clears and starts recording the categories in the bit mask (1 GEMM | 2 norm | 4 attention | 8 other; 0 = off); read() waits for the events (host sync) and returns the

@@ -108,6 +108,10 @@ class ModelDesc(C.Structure):
         "proj_dim", "tower_precision")] + [("ln_eps", C.c_float)] + [(n, C.c_int) for n in ("vit_w2_mask", "txt_x3", "proj_x3", "vit_x3", "txt_w2_mask", "vit_w2_qkv_layers", "vit_w2_fc1_layers", "vit_w2_out_layers", "vit_w2_fc2_layers")]
 
 
+class OptSegment(C.Structure):          # ofx_opt_segment: 24 bytes, three 8-byte words
+    _fields_ = [("param", C.c_void_p), ("offset", C.c_longlong), ("numel", C.c_longlong)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("cat", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("kind", C.c_int), ("kmul", C.c_int), ("ms", C.c_float), ("flops", C.c_double), ("bytes", C.c_double)]
 
@@ -157,6 +161,8 @@ SIGNATURES = {
     "ofx_focal_loss_ex": (_i, [_vp, _vp, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "ofx_set_rank_loss_ws_bytes": (_sz, [_i, _i, _i]),
     "ofx_set_rank_loss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ofx_adamw_step_ws_bytes": (_sz, [C.c_longlong]),
+    "ofx_adamw_step": (_i, [_vp, _i, _vp, _vp, _vp, C.c_longlong, _vp] + [C.c_double] * 7 + [_vp, _vp, _vp, _sz, _vp]),
     "ofx_profile_enable": (None, [_i]),
     "ofx_profile_read": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
     "ofx_profile_records": (_i, [C.POINTER(ProfRecord), _i]),

@@ -156,6 +156,10 @@ int ofx_launch_focal_loss(const float* logits, const float* labels, int B, float
 size_t ofx_set_rank_loss_ws(int B, int K);
 int ofx_launch_set_rank_loss(const float* y, const float* y_hat, const float* neg, const uint8_t* mask, int B, int K, int D, float margin, float upstream,
                              float* loss, float* dy_hat, float* d_pos, float* d_neg, void* ws, hipStream_t s);
+size_t ofx_adamw_step_ws(long long n_arena);
+int ofx_launch_adamw_step(const ofx_opt_segment* segments, int n_segments, float* grad, float* exp_avg, float* exp_avg_sq, long long n_arena,
+                          float* step, double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm, double grad_scale,
+                          float* grad_norm, int* skipped, void* ws, hipStream_t s);
 int ofx_launch_cp_head_bwd(const float* dlogits, const float* w_or_rows, const int* cu, float* dX, void* dXb, float* db, int B, int D, int op_dtype,
                            const DropArgs& head, const DropArgs& below, hipStream_t s, int accumulate = 0);
 int ofx_launch_fitb(const float* y, const float* cand, int B, int C, int D, int64_t* idx, float* dist, hipStream_t s);
@@ -1317,6 +1321,21 @@ extern "C" int ofx_set_rank_loss(const float* y, const float* y_hat, const float
                 "set_rank_loss: y, y_hat, neg, dy_hat and ws must be 16-byte aligned");
     OFX_REQUIRE(ws_bytes >= ofx_set_rank_loss_ws(B, K), OFX_EWORKSPACE, "set_rank_loss: workspace %zu < %zu bytes", ws_bytes, ofx_set_rank_loss_ws(B, K));
     return ofx_launch_set_rank_loss(y, y_hat, neg, neg_mask, B, K, D, margin, upstream, loss, dy_hat, d_pos, d_neg, ws, (hipStream_t)stream);
+}
+
+static bool adamw_shape_ok(long long n_arena) { return n_arena > 0 && n_arena % 64 == 0; }
+extern "C" size_t ofx_adamw_step_ws_bytes(long long n_arena) { return adamw_shape_ok(n_arena) ? ofx_adamw_step_ws(n_arena) : 0; }
+extern "C" int ofx_adamw_step(const ofx_opt_segment* segments, int n_segments, float* grad, float* exp_avg, float* exp_avg_sq, long long n_arena,
+                              float* step, double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm, double grad_scale,
+                              float* grad_norm, int* skipped, void* ws, size_t ws_bytes, ofx_stream stream) {
+    OFX_REQUIRE(segments && grad && exp_avg && exp_avg_sq && step && grad_norm && skipped && ws, OFX_EINVAL, "adamw_step: NULL argument");
+    OFX_REQUIRE(n_segments >= 1 && n_segments <= 1024, OFX_ESHAPE, "adamw_step: n_segments = %d; needs 1 <= n_segments <= 1024", n_segments);
+    OFX_REQUIRE(adamw_shape_ok(n_arena), OFX_ESHAPE, "adamw_step: n_arena = %lld; needs a positive multiple of 64", n_arena);
+    OFX_REQUIRE((((uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)ws) & 15) == 0 && ((uintptr_t)segments & 7) == 0, OFX_EINVAL,
+                "adamw_step: grad, exp_avg, exp_avg_sq and ws must be 16-byte aligned, segments 8-byte aligned");
+    OFX_REQUIRE(ws_bytes >= ofx_adamw_step_ws(n_arena), OFX_EWORKSPACE, "adamw_step: workspace %zu < %zu bytes", ws_bytes, ofx_adamw_step_ws(n_arena));
+    return ofx_launch_adamw_step(segments, n_segments, grad, exp_avg, exp_avg_sq, n_arena, step, lr, beta1, beta2, eps, weight_decay, max_norm,
+                                 grad_scale, grad_norm, skipped, ws, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------- tuning

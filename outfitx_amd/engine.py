@@ -460,6 +460,41 @@ def set_rank_loss(y: torch.Tensor, y_hat: torch.Tensor, neg: torch.Tensor, neg_m
     return loss, dy
 
 
+ADAMW_WG_FLOATS = 4096      # arena floats one workgroup of ofx_adamw_step covers per stride step (optim.hip OPT_WG_FLOATS); grid = min(ceil(n / this), 2048)
+
+
+def adamw_step_ws_bytes(n_arena: int) -> int:
+    return int(L.load().ofx_adamw_step_ws_bytes(int(n_arena)))
+
+
+def adamw_step(segments: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, step: torch.Tensor,
+               lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, max_norm: float, grad_scale: float,
+               grad_norm: torch.Tensor, skipped: torch.Tensor, ws: Optional[torch.Tensor] = None) -> None:
+    """clip_grad_norm_(max_norm) -> AdamW -> zero over a flat gradient arena, two launches on the current stream (ofx_adamw_step; semantics
+    in include/ofx.h).  segments: int64 [n, 3] DEVICE rows (param data_ptr, arena offset, numel), sorted by offset (`optim.segment_table`);
+    grad / exp_avg / exp_avg_sq: fp32 arenas of the same length (a multiple of 64); step, grad_norm: 1-element fp32, skipped: 1-element
+    int32, all on the arena's device; ws: uint8 workspace of adamw_step_ws_bytes(n) (allocated when None).  Everything is updated in
+    place; nothing is returned and nothing waits."""
+    lib = L.load()
+    dev = grad.device
+    if dev.type != "cuda":
+        raise L.OfxError("adamw_step needs HIP tensors; there is no CPU path")
+    for name, t, dt in (("segments", segments, torch.int64), ("grad", grad, torch.float32), ("exp_avg", exp_avg, torch.float32),
+                        ("exp_avg_sq", exp_avg_sq, torch.float32), ("step", step, torch.float32), ("grad_norm", grad_norm, torch.float32),
+                        ("skipped", skipped, torch.int32)):
+        if t.device != dev or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"adamw_step: {name} must be a contiguous {dt} tensor on {dev}")
+    n = grad.numel()
+    if segments.dim() != 2 or segments.shape[1] != 3 or exp_avg.numel() != n or exp_avg_sq.numel() != n:
+        raise ValueError(f"adamw_step: segments {tuple(segments.shape)} is not [n, 3], or the arenas differ in length")
+    if ws is None:
+        ws = torch.empty(max(lib.ofx_adamw_step_ws_bytes(n), 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.ofx_adamw_step(_ptr(segments), segments.shape[0], _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), n, _ptr(step), float(lr),
+                                   float(beta1), float(beta2), float(eps), float(weight_decay), float(max_norm), float(grad_scale),
+                                   _ptr(grad_norm), _ptr(skipped), _ptr(ws), ws.numel(), _stream(dev)), "ofx_adamw_step")
+
+
 def topk_merge(idx_parts: torch.Tensor, dist_parts: torch.Tensor):
     """[parts,nq,k] per-shard candidates (global indices) -> ([nq,k] idx, [nq,k] dist), ascending, ties -> smaller idx."""
     lib = L.load()

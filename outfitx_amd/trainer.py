@@ -52,6 +52,7 @@ class CPTrainConfig:
     div_factor: float = 25.0
     final_div_factor: float = 1e4
     fused_optimizer: bool = True      # torch.optim.AdamW(fused=True): one multi-tensor kernel per step
+    hip_optimizer: bool = False       # optim.FlatAdamW: clip + AdamW + zero over the arena as one ofx_adamw_step call (HIP devices only)
 
 
 @dataclass
@@ -67,6 +68,7 @@ class CIRTrainConfig:
     div_factor: float = 25.0
     final_div_factor: float = 1e4
     fused_optimizer: bool = True
+    hip_optimizer: bool = False       # as CPTrainConfig.hip_optimizer
 
 
 class FlatGrads:
@@ -173,7 +175,13 @@ def gather_epoch(local_y: torch.Tensor, local_labels: torch.Tensor, local_loss: 
 class FlatGradTrainer:
     """What the CP and the CIR loop share: the flat gradient arena, gradient-sink mode of the HIP model, per-layer gradient slices,
     the overlapped mean over the ranks, and the accumulation-boundary step (clip -> AdamW -> OneCycleLR -> zero).  `cfg` carries
-    learning_rate, accumulation_steps, n_epochs, max_grad_norm, pct_start, div_factor, final_div_factor, fused_optimizer."""
+    learning_rate, accumulation_steps, n_epochs, max_grad_norm, pct_start, div_factor, final_div_factor, fused_optimizer, hip_optimizer.
+
+    cfg.hip_optimizer: the optimizer is optim.FlatAdamW over the arena - norm, clip, AdamW and the zeroing are ONE ofx_adamw_step call
+    (two launches), and the division by the world size rides in it as grad_scale.  `last_grad_norm` is then the kernel's norm tensor and
+    `last_step_skipped` its flag (1: the norm was not finite, the gradient was dropped and parameters, moments and step count were left
+    alone); both stay on the device.  The OneCycleLR schedule advances whether or not the step was skipped: the schedule counts
+    accumulation windows, and finding out would cost a host synchronisation per step."""
 
     # OutfitX._outfit_tensors() entries that are NOT on the task's path (sink_ready ignores them): CP skips target_item_image_emb, cir_ffn
     _sink_skip = (1, 4)
@@ -187,13 +195,19 @@ class FlatGradTrainer:
         self.loss_fn = loss_fn
         dev = self.grads.flat.device
         fused = c.fused_optimizer and dev.type == "cuda"
-        self.optimizer = torch.optim.AdamW(self.grads.params, lr=c.learning_rate, **({"fused": True} if fused else {}))
+        self.hip_optimizer = bool(getattr(c, "hip_optimizer", False))
+        if self.hip_optimizer:
+            from .optim import FlatAdamW                     # raises on a CPU arena: no quiet fall-back to torch's AdamW
+            self.optimizer = FlatAdamW(self.grads, lr=c.learning_rate, max_norm=c.max_grad_norm)
+        else:
+            self.optimizer = torch.optim.AdamW(self.grads.params, lr=c.learning_rate, **({"fused": True} if fused else {}))
         self.scheduler = torch.optim.lr_scheduler.OneCycleLR(
             optimizer=self.optimizer, max_lr=c.learning_rate, epochs=c.n_epochs,
             steps_per_epoch=math.ceil(steps_per_epoch / c.accumulation_steps), pct_start=c.pct_start, anneal_strategy="cos",
             div_factor=c.div_factor, final_div_factor=c.final_div_factor)
         self.steps_per_epoch = steps_per_epoch
         self.last_grad_norm: Optional[torch.Tensor] = None
+        self.last_step_skipped: Optional[torch.Tensor] = None       # hip_optimizer only: 0-d int32 on the device
         # outfitx_amd.OutfitX: let the backward kernels add straight into the arena views (no per-tensor accumulate kernels);
         # valid because nothing here relies on autograd hooks (DDP would)
         if hasattr(model, "_cp_train_forward"):
@@ -237,13 +251,17 @@ class FlatGradTrainer:
     def _reduce_mean(self, overlapped: bool) -> None:
         """Mean of the gradient arena over the ranks.  overlapped: layer l's slice is reduced on the side stream as soon as its event
         fires (the backward of the layers below is still running on the main stream); else slice by slice after the backward (CPU /
-        gloo, stub models) or as one collective when the model has no layer structure.  Same sums either way."""
+        gloo, stub models) or as one collective when the model has no layer structure.  Same sums either way.  With hip_optimizer only
+        the SUM is formed here: FlatAdamW applies 1 / world as its grad_scale."""
         world = self._world()
         if world <= 1:
             return
         flat = self.grads.flat
         if not self.layer_slices:
-            self.grads.all_reduce_mean_(self.group)
+            if self.hip_optimizer:
+                dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.group)
+            else:
+                self.grads.all_reduce_mean_(self.group)
             return
         works = []
         if overlapped:
@@ -263,7 +281,8 @@ class FlatGradTrainer:
         else:
             for lo, hi in list(reversed(self.layer_slices)) + list(self.rest_slices):
                 dist.all_reduce(flat[lo:hi], op=dist.ReduceOp.SUM, group=self.group)
-        flat.div_(world)
+        if not self.hip_optimizer:
+            flat.div_(world)
 
     def _backward_and_step(self, loss: torch.Tensor, step: int) -> None:
         """(loss / accumulation_steps).backward(); on every accumulation_steps-th micro-batch or the epoch's last: mean over the
@@ -273,12 +292,24 @@ class FlatGradTrainer:
         overlapped = boundary and self._arm_overlap()
         (loss / c.accumulation_steps).backward()
         if boundary:
-            self._reduce_mean(overlapped)
-            self.last_grad_norm = self.grads.clip_norm_(c.max_grad_norm)
+            self._boundary_step(overlapped)
+
+    def _boundary_step(self, overlapped: bool) -> None:
+        """The end of an accumulation window, on whatever the arena holds: mean over the ranks -> clip -> optimizer step -> scheduler
+        step -> zero -> the model re-packs its operand copies on its next forward.  hip_optimizer: clip, step and zero are FlatAdamW's
+        one call; the scheduler steps even when that call skipped a non-finite gradient (class docstring)."""
+        self._reduce_mean(overlapped)
+        if self.hip_optimizer:
+            self.optimizer.grad_scale = 1.0 / self._world()
+            self.optimizer.step()
+            self.last_grad_norm, self.last_step_skipped = self.optimizer.grad_norm, self.optimizer.skipped
+            self.scheduler.step()
+        else:
+            self.last_grad_norm = self.grads.clip_norm_(self.cfg.max_grad_norm)
             self.optimizer.step()
             self.scheduler.step()
             self.grads.zero_()
-            getattr(self.model, "mark_weights_changed", lambda: None)()     # fused optimizers do not bump tensor versions
+        getattr(self.model, "mark_weights_changed", lambda: None)()         # fused optimizers do not bump tensor versions
 
 
 class CPTrainer(FlatGradTrainer):

@@ -17,6 +17,15 @@ timings.  `loss_kernel_GBps` is (B K D 4 + 3 B D 4) bytes - neg read once, y / y
 
     python tools/bench_train.py --task cir [--cir-batches 256,3072] [--negatives 10] [--loss-reps 30]
 
+The CP run also times the accumulation BOUNDARY alone at the CP arena's real size (51.3 M floats) in its two forms, alternating in
+one process, medians over --boundary-reps device-event timings after a warm-up: `ms_boundary_torch` (vector_norm -> mul_ -> fused AdamW
+over the per-tensor views -> zero_, plus the div_ by the world size when there is more than one rank) and `ms_boundary_hip`
+(optim.FlatAdamW: one ofx_adamw_step call).  `boundary_bytes_*` are the bytes each form has to move, computed here from the arena's
+length n: 44 n (52 n with the world divide) and 36 n; `boundary_GBps_*` the resulting rates; `us_boundary_hip_norm_pass` /
+`us_boundary_hip_update_pass` the device times of the call's two kernels (torch.profiler, one step; absent if it records none).
+`ms_step_dp_hip` / `ms_step_dp_accum4_hip` are the trainer steps with CPTrainConfig(hip_optimizer=True).  The line is also written to
+--boundary-out when given (profiles/optimizer_step_bench.json).
+
 --eager also times the same step written with plain torch modules (nn.TransformerEncoder under bf16 autocast, what the
 reference's trainer executes) on the same GPU, for a like-for-like ratio.  Prints one JSON line.
 """
@@ -44,20 +53,65 @@ def timed(fn, steps, warmup):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
-def median_ms(fns, reps, warmup):
-    """Device-event time of each callable, the callables ALTERNATING inside every repetition -> list of medians (ms)."""
+def median_ms(fns, reps, warmup, prep=None):
+    """Device-event time of each callable, the callables ALTERNATING inside every repetition -> list of medians (ms).  prep (optional)
+    runs before every timed call, outside the timed span."""
     for _ in range(warmup):
         for fn in fns:
+            if prep:
+                prep()
             fn()
     torch.cuda.synchronize()
     ts = [[] for _ in fns]
     for _ in range(reps):
         for i, fn in enumerate(fns):
+            if prep:
+                prep()
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record(); fn(); b.record()
             b.synchronize()
             ts[i].append(a.elapsed_time(b))
     return [float(np.median(t)) for t in ts]
+
+
+def boundary_bench(params, world, reps, res):
+    """The accumulation boundary alone, torch's sequence against the one ofx_adamw_step call, on a freshly filled arena of the real size."""
+    from outfitx_amd.optim import FlatAdamW
+    from outfitx_amd.trainer import FlatGrads
+    grads = FlatGrads(params)
+    flat, n = grads.flat, grads.flat.numel()
+    opt_t = torch.optim.AdamW(grads.params, lr=2e-5, fused=True)
+    opt_h = FlatAdamW(grads, lr=2e-5, max_norm=1.0)
+    opt_h.grad_scale = 1.0 / world
+    fill = torch.randn(n, device=flat.device) * 1e-3            # norm about 7: every timed boundary clips
+    for o, p in zip(grads.offsets, grads.params):               # keep the padding zero, as the backward leaves it
+        fill[o + p.numel():o + (p.numel() + 63) // 64 * 64] = 0
+
+    def torch_form():
+        if world > 1:
+            flat.div_(world)
+        grads.clip_norm_(1.0)
+        opt_t.step()
+        grads.zero_()
+
+    t_t, t_h = median_ms([torch_form, opt_h.step], reps, 5, prep=lambda: flat.copy_(fill))
+    b_t, b_h = (52 if world > 1 else 44) * n, 36 * n
+    res.update(boundary_floats=n, boundary_reps=reps, ms_boundary_torch=t_t, ms_boundary_hip=t_h, boundary_bytes_torch=b_t, boundary_bytes_hip=b_h,
+               boundary_GBps_torch=b_t / (t_t * 1e-3) / 1e9, boundary_GBps_hip=b_h / (t_h * 1e-3) / 1e9, boundary_torch_over_hip=t_t / t_h)
+    try:                                                        # device time of each of the call's two kernels
+        from torch.profiler import ProfilerActivity, profile
+        flat.copy_(fill)
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            opt_h.step()
+            torch.cuda.synchronize()
+        for e in prof.events():
+            for key, name in (("adamw_norm_kernel", "us_boundary_hip_norm_pass"), ("adamw_update_kernel", "us_boundary_hip_update_pass")):
+                if key in e.name:
+                    res[name] = float(getattr(e, "device_time", 0.0) or getattr(e, "cuda_time", 0.0))
+    except Exception as e:                                      # noqa: BLE001 - the per-kernel split is a diagnostic; the medians above are the result
+        res["boundary_profile_error"] = repr(e)[:200]
+    del opt_t, opt_h, grads
 
 
 def eager_set_rank_loss(batch_y, batch_y_hat, batch_negative_samples, batch_negative_mask, margin=2.0):
@@ -126,6 +180,8 @@ def main():
     ap.add_argument("--cir-batches", default="256,3072")
     ap.add_argument("--negatives", type=int, default=10)
     ap.add_argument("--loss-reps", type=int, default=30)
+    ap.add_argument("--boundary-reps", type=int, default=30)
+    ap.add_argument("--boundary-out", default="", help="also write the JSON line to this file (CP task)")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--items", type=int, default=8)
     ap.add_argument("--pad", type=int, default=16)
@@ -193,6 +249,15 @@ def main():
         def dp_step():
             tr.micro_step(batch, k[0]); k[0] += 1
         res["ms_step_dp" if acc == 1 else "ms_step_dp_accum4"] = timed(dp_step, a.steps if acc == 1 else 4 * max(a.steps // 4, 1), a.warmup if acc == 1 else 4)
+        del tr
+    for acc in (1, 4):                                          # the same steps with the fused boundary (CPTrainConfig.hip_optimizer)
+        tr = CPTrainer(m, steps_per_epoch=10 ** 9, cfg=CPTrainConfig(accumulation_steps=acc, hip_optimizer=True), params=params)
+        k = [0]
+        def dp_step_hip():
+            tr.micro_step(batch, k[0]); k[0] += 1
+        res["ms_step_dp_hip" if acc == 1 else "ms_step_dp_accum4_hip"] = timed(dp_step_hip, a.steps if acc == 1 else 4 * max(a.steps // 4, 1), a.warmup if acc == 1 else 4)
+        del tr
+    boundary_bench(params, world, a.boundary_reps, res)
     res["world"] = world
     res["outfits_per_s_dp"] = world * a.batch / res["ms_step_dp"] * 1e3
     rows = int(np.sum(n_items) + a.batch) if a.polyvore else a.batch * (a.items + 1)
@@ -227,6 +292,9 @@ def main():
         res["speedup_vs_torch_eager"] = res["ms_step_torch_eager_bf16"] / res["ms_step"]
     if int(os.environ.get("RANK", "0")) == 0:
         print(json.dumps(res))
+        if a.boundary_out:
+            with open(a.boundary_out, "w") as f:
+                f.write(json.dumps(res) + "\n")
     if world > 1:
         dist.destroy_process_group()
 
