@@ -155,6 +155,23 @@ int ofx_fitb_argmin(const float* y_hat, const float* cand, int B, int C, int D, 
  * ordered as if it were absent.  A query that holds one gets k distinct in-range rows with non-finite distances, nothing more. */
 int ofx_l2_topk(ofx_handle* h, const float* Q, const float* P, int nq, int np, int D, int k, int64_t index_base,
                 int64_t* idx, float* dist, void* ws, size_t ws_bytes, ofx_stream stream);
+/* Row I per category pool (the validation / test loops, complementary_item_retrieval_trainer.py:192-249, and demo/app.py:184-190): every query
+ * searches the pool of its own group only; all groups in one launch sequence (two row-norm launches, one distance launch, one select launch),
+ * no host synchronisation.  Q [nq,D]: the queries, each group's contiguous; P [np,D]: all pools concatenated.
+ * panels: DEVICE int [n_panels][4] = (q_lo, q_hi, p_lo, p_hi), 16-byte aligned: query rows [q_lo, q_hi), at most 128, search pool rows [p_lo, p_hi)
+ * and nothing else.  Precondition, not checked: panels ascend in q_lo, are disjoint and cover [0, nq); max_group_rows >= every p_hi - p_lo.  The
+ * kernels clamp what the table holds into [0, nq), [0, np) and max_group_rows, so a wrong table gives wrong results, never an access out of bounds.
+ * idx int64 [nq,k] = rows of P, dist fp32 [nq,k]: per query the bits of the flat call on its own pool with index_base = p_lo (ascending, ties ->
+ * smaller row, non-finite rows last within the pool).  A pool of fewer than k rows: its rows in order, then idx -1 / dist +inf.
+ * gt int64 [nq] (a row of P, < 0 = none) with gt_pos int [nq], both or neither: gt_pos[q] = the j with idx[q,j] == gt[q], else k (also for gt < 0),
+ * written by the select from the keys it holds; recall@K = count(gt_pos < K) / count(gt >= 0) for every K <= k.
+ * Checked: no NULL among Q, P, panels, idx, dist, ws and the alignment of Q, P, panels (OFX_EINVAL); D a multiple of 32, 1 <= k <= 128,
+ * n_panels >= 1, max_group_rows >= 1 (OFX_ESHAPE); ws_bytes >= the _ws figure below for nq, np, max_group_rows (OFX_EWORKSPACE, it holds the
+ * norms of all np pool rows, hence np); a rejected call launches nothing. */
+size_t ofx_l2_topk_grouped_ws(int nq, int np, int max_group_rows);
+int ofx_l2_topk_grouped(ofx_handle* h, const float* Q, const float* P, int nq, int np, int D, int k, const int* panels, int n_panels,
+                        int max_group_rows, const int64_t* gt, int64_t* idx, float* dist, int* gt_pos, void* ws, size_t ws_bytes,
+                        ofx_stream stream);
 /* Merge `parts` candidate lists (after the RCCL all-gather of per-shard top-k): in [parts,nq,k], each list ascending, rows unique across lists.
  * parts * k <= 1024 (else OFX_ESHAPE).  Ordered by (distance bits, global index): NaN distances sort last here as well. */
 int ofx_topk_merge(const int64_t* idx_in, const float* dist_in, int parts, int nq, int k, int64_t* idx, float* dist,

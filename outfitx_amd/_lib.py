@@ -139,6 +139,8 @@ SIGNATURES = {
     "ofx_clip_text_fwd": (_i, [_vp, _vp, _vp, C.POINTER(_i), _i, _i, _vp, _i, _i, _i, _vp, _sz, _vp]),
     "ofx_fitb_argmin": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "ofx_l2_topk": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "ofx_l2_topk_grouped_ws": (_sz, [_i, _i, _i]),
+    "ofx_l2_topk_grouped": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ofx_topk_merge": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "ofx_clip_preprocess_ws": (_sz, [_vp, _vp, _i, _i, _i]),
     "ofx_clip_preprocess": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -166,6 +166,8 @@ int ofx_launch_fitb(const float* y, const float* cand, int B, int C, int D, int6
 int ofx_launch_l2_topk(const float* Q, const float* P, int nq, int np, int D, int k, int64_t index_base, int64_t* idx,
                        float* dist, void* ws, size_t ws_bytes, hipStream_t s);
 size_t ofx_l2_topk_ws(int nq, int np);
+int ofx_launch_l2_topk_grouped(const float* Q, const float* P, int nq, int np, int D, int k, const int* panels, int n_panels, int max_group_rows,
+                               const int64_t* gt, int64_t* idx, float* dist, int* gt_pos, void* ws, size_t ws_bytes, hipStream_t s);
 int ofx_launch_topk_merge(const int64_t* idx_in, const float* dist_in, int parts, int nq, int k, int64_t* idx, float* dist,
                           hipStream_t s);
 
@@ -985,6 +987,10 @@ extern "C" int ofx_fitb_argmin(const float* y, const float* cand, int B, int C, 
 extern "C" int ofx_l2_topk(ofx_handle*, const float* Q, const float* P, int nq, int np, int D, int k, int64_t index_base,
                            int64_t* idx, float* dist, void* ws, size_t ws_bytes, ofx_stream stream) {
     return ofx_launch_l2_topk(Q, P, nq, np, D, k, index_base, idx, dist, ws, ws_bytes, (hipStream_t)stream);
+}
+extern "C" int ofx_l2_topk_grouped(ofx_handle*, const float* Q, const float* P, int nq, int np, int D, int k, const int* panels, int n_panels,
+                                   int max_group_rows, const int64_t* gt, int64_t* idx, float* dist, int* gt_pos, void* ws, size_t ws_bytes, ofx_stream stream) {
+    return ofx_launch_l2_topk_grouped(Q, P, nq, np, D, k, panels, n_panels, max_group_rows, gt, idx, dist, gt_pos, ws, ws_bytes, (hipStream_t)stream);
 }
 extern "C" int ofx_topk_merge(const int64_t* idx_in, const float* dist_in, int parts, int nq, int k, int64_t* idx, float* dist, ofx_stream stream) {
     return ofx_launch_topk_merge(idx_in, dist_in, parts, nq, k, idx, dist, (hipStream_t)stream);

@@ -8,6 +8,8 @@
 //                (reference src/trains/trainers/complementary_item_retrieval_trainer.py:240-249)
 //                = row norms + fp32-MFMA (v_mfma_f32_32x32x2_f32, an exact fmaf chain) distance
 //                tiles + per-query radix select of the k-th value + index-ordered collection.
+//  l2_topk_grouped : the same per category pool (the reference's validation loop, :192-249, and demo/app.py:184-190): every query against
+//                the pool of its group only, all groups in one launch sequence, + the position of the ground-truth row (recall@k).
 //  topk_merge  : merge of per-shard candidate lists after the RCCL all-gather (pool row-sharding).
 #include <algorithm>
 
@@ -75,20 +77,15 @@ __device__ __forceinline__ void dist_glds16(const char* g, OFX_LDS char* l) {
     __builtin_amdgcn_global_load_lds((const OFX_GLB void*)g, (OFX_LDS void*)l, 16, 0, 0);
 }
 
+// The tile walk both distance kernels share: walker bx of gx strides over the 128-row pool tiles of rows [p_begin, np) for the query panel
+// [q0, min(q0 + 128, nq)); row numbers are clamped into [0, nq) and [0, np) for the loads and masked in the epilogue.  dist_mfma_kernel
+// passes the whole problem's bounds, dist_grouped_kernel one panel's (nq = the panel's q_hi, p_begin / np = its pool's p_lo / p_hi): the
+// arithmetic of a (q, p) pair is the same instruction sequence either way.
 template <bool FILTER>
-__global__ __launch_bounds__(256, 2) void dist_mfma_kernel(const float* Q, const float* P, const float* qn, const float* pn, float* dist, int nq, int np, int D, int ld,
-                                                          int p_begin, const float* tau, int tau_ld, int* cnt, unsigned long long* cand, int cap, const int* only_flagged, int tiles_q) {
-    extern __shared__ __attribute__((aligned(16))) char dsm[];
-    OFX_LDS char* lds = (OFX_LDS char*)dsm;
+__device__ __forceinline__ void dist_tile_walk(OFX_LDS char* lds, const float* Q, const float* P, const float* qn, const float* pn, float* dist, int q0, int nq, int np, int D,
+                                               int ld, int p_begin, const float* tau, int tau_ld, int* cnt, unsigned long long* cand, int cap, int bx, int gx) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wave >> 1, wn = wave & 1;
-    // 1-D grid, query panel = block id mod tiles_q: with 8 panels (1000 queries) every XCD (blocks b, b + 8, ... share one) serves ONE panel, whose
-    // 512 KiB of queries stay in that XCD's L2 while the pool tiles stream through
-    const int q0 = ((int)blockIdx.x % tiles_q) * DT, bx = (int)blockIdx.x / tiles_q, gx = (int)gridDim.x / tiles_q;
-    if (only_flagged) {                                  // fallback launch: only query panels that hold a flagged query do anything
-        const int f = (tid < DT && q0 + tid < nq) ? only_flagged[q0 + tid] : 0;
-        if (!__syncthreads_or(f)) return;
-    }
     const int tiles_p = (np - p_begin + DT - 1) / DT;
     // LDS-DMA addressing: wave w moves rows (w * 4 + i) * 8 + (lane >> 3), i = 0..3, of each operand; physical 16-byte slot lane & 7 of a
     // row holds logical chunk (lane & 7) ^ ((row >> 1) & 7)
@@ -188,6 +185,39 @@ __global__ __launch_bounds__(256, 2) void dist_mfma_kernel(const float* Q, const
     }
 }
 
+template <bool FILTER>
+__global__ __launch_bounds__(256, 2) void dist_mfma_kernel(const float* Q, const float* P, const float* qn, const float* pn, float* dist, int nq, int np, int D, int ld,
+                                                          int p_begin, const float* tau, int tau_ld, int* cnt, unsigned long long* cand, int cap, const int* only_flagged, int tiles_q) {
+    extern __shared__ __attribute__((aligned(16))) char dsm[];
+    const int tid = threadIdx.x;
+    // 1-D grid, query panel = block id mod tiles_q: with 8 panels (1000 queries) every XCD (blocks b, b + 8, ... share one) serves ONE panel, whose
+    // 512 KiB of queries stay in that XCD's L2 while the pool tiles stream through
+    const int q0 = ((int)blockIdx.x % tiles_q) * DT, bx = (int)blockIdx.x / tiles_q, gx = (int)gridDim.x / tiles_q;
+    if (only_flagged) {                                  // fallback launch: only query panels that hold a flagged query do anything
+        const int f = (tid < DT && q0 + tid < nq) ? only_flagged[q0 + tid] : 0;
+        if (!__syncthreads_or(f)) return;
+    }
+    dist_tile_walk<FILTER>((OFX_LDS char*)dsm, Q, P, qn, pn, dist, q0, nq, np, D, ld, p_begin, tau, tau_ld, cnt, cand, cap, bx, gx);
+}
+
+// Category pools in one launch: block b serves panel b % n_panels = (q_lo, q_hi, p_lo, p_hi) of the device table - query rows [q_lo, q_hi), at
+// most 128, against pool rows [p_lo, p_hi) and nothing else - as walker b / n_panels of gridDim.x / n_panels over that pool's tiles.  The
+// distances go to dm[q, p - p_lo] (ld >= max_rows), and walker 0 records (p_lo, rows) per query for the select behind it.  The table is the
+// caller's; its values are clamped so that whatever it holds, no load or store leaves Q, P or dm.
+__global__ __launch_bounds__(256, 2) void dist_grouped_kernel(const float* Q, const float* P, const float* qn, const float* pn, float* dm, int nq, int np, int D, int ld,
+                                                             const int4* panels, int n_panels, int max_rows, int2* qpool) {
+    extern __shared__ __attribute__((aligned(16))) char dsm[];
+    const int bx = (int)blockIdx.x / n_panels, gx = (int)gridDim.x / n_panels;
+    const int4 pa = panels[(int)blockIdx.x % n_panels];
+    int q_lo = __builtin_amdgcn_readfirstlane(pa.x), q_hi = __builtin_amdgcn_readfirstlane(pa.y);
+    int p_lo = __builtin_amdgcn_readfirstlane(pa.z), p_hi = __builtin_amdgcn_readfirstlane(pa.w);
+    q_lo = max(q_lo, 0); q_hi = min(min(q_hi, nq), q_lo + DT);
+    p_lo = min(max(p_lo, 0), np); p_hi = min(min(p_hi, np), p_lo + max_rows);
+    if (q_hi <= q_lo) return;
+    if (bx == 0 && (int)threadIdx.x < q_hi - q_lo) qpool[q_lo + threadIdx.x] = make_int2(p_lo, max(p_hi - p_lo, 0));
+    dist_tile_walk<false>((OFX_LDS char*)dsm, Q, P, qn, pn, dm, q_lo, q_hi, p_hi, D, ld, p_lo, nullptr, 0, nullptr, nullptr, 0, bx, gx);
+}
+
 // block-wide exclusive scan of one int per thread (256 threads); returns exclusive prefix, *total = sum
 __device__ __forceinline__ int block_excl_scan(int v, int* sh /*[5]*/, int* total) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -226,18 +256,19 @@ __device__ __forceinline__ void bitonic_sort(unsigned long long* keys, int n /*p
     __syncthreads();
 }
 
-// one block per query row: exact k smallest of row[0..np) (non-negative floats, or NaN: ordered by bit pattern, i.e. last), ties -> smaller index
-__global__ __launch_bounds__(256) void topk_select_kernel(const float* dist, int ld, int np, int k, int64_t index_base,
-                                                         int64_t* idx_out, float* dist_out, const int* only_flagged = nullptr) {
-    if (only_flagged && !only_flagged[blockIdx.x]) return;          // fallback launch: only the flagged queries
+// one block per query row: exact k smallest of row[0..np) (non-negative floats, or NaN: ordered by bit pattern, i.e. last), ties -> smaller index,
+// into idx_out / dist_out[0..k).  np < k (grouped pools only): the np rows in order, then idx -1 / dist +inf.  gt_pos, when asked for: the
+// position j with idx_out[j] == gt, found among the sorted keys the block still holds; k when there is none or gt < 0.
+__device__ __forceinline__ void topk_select_row(const unsigned* row, int np, int k, int64_t index_base, int64_t* idx_out, float* dist_out, int64_t gt, int* gt_pos) {
     __shared__ int hist[2048];
     __shared__ int sh[8];
     __shared__ unsigned sel_prefix;
     __shared__ int sel_k;
+    __shared__ int gt_at;
     __shared__ unsigned long long keys[KMAX];
     const int tid = threadIdx.x;
-    const unsigned* row = (const unsigned*)(dist + (size_t)blockIdx.x * ld);
-    if (tid == 0) { sel_prefix = 0; sel_k = k; }
+    const int ksel = min(k, np);            // block-uniform
+    if (tid == 0) { sel_prefix = 0; sel_k = ksel; gt_at = k; }
     // three radix passes: bits [31:21], [20:10], [9:0]
     const int shift[3] = {21, 10, 0}, nbins[3] = {2048, 2048, 1024};
     unsigned mask_hi = 0;
@@ -275,7 +306,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(const float* dist, int
     }
     const unsigned T = sel_prefix;          // bits of the k-th smallest value
     const int need_eq = sel_k;              // how many == T to take (smallest indices)
-    const int c_less = k - need_eq;
+    const int c_less = ksel - need_eq;
     for (int i = tid; i < KMAX; i += 256) keys[i] = ~0ull;
     __syncthreads();
     int run_less = 0, run_eq = 0;
@@ -305,9 +336,31 @@ __global__ __launch_bounds__(256) void topk_select_kernel(const float* dist, int
     bitonic_sort(keys, KMAX);
     for (int i = tid; i < k; i += 256) {
         const unsigned long long key = keys[i];
-        idx_out[(size_t)blockIdx.x * k + i] = (int64_t)(key & 0xffffffffu) + index_base;
-        dist_out[(size_t)blockIdx.x * k + i] = __uint_as_float((unsigned)(key >> 32));
+        const int64_t r = i < ksel ? (int64_t)(key & 0xffffffffu) + index_base : -1;
+        idx_out[i] = r;
+        dist_out[i] = i < ksel ? __uint_as_float((unsigned)(key >> 32)) : INFINITY;
+        if (gt_pos && gt >= 0 && r == gt) gt_at = i;        // rows are distinct: at most one writer
     }
+    if (gt_pos) {
+        __syncthreads();
+        if (tid == 0) *gt_pos = gt_at;
+    }
+}
+
+__global__ __launch_bounds__(256) void topk_select_kernel(const float* dist, int ld, int np, int k, int64_t index_base,
+                                                         int64_t* idx_out, float* dist_out, const int* only_flagged = nullptr) {
+    if (only_flagged && !only_flagged[blockIdx.x]) return;          // fallback launch: only the flagged queries
+    topk_select_row((const unsigned*)(dist + (size_t)blockIdx.x * ld), np, k, index_base, idx_out + (size_t)blockIdx.x * k, dist_out + (size_t)blockIdx.x * k, -1, nullptr);
+}
+
+// grouped pools: query q selects among the qpool[q].y distances dist_grouped_kernel left in its row; rows of P = local row + qpool[q].x
+__global__ __launch_bounds__(256) void topk_select_grouped_kernel(const float* dm, int ld, int max_rows, int k, const int2* qpool, const int64_t* gt,
+                                                                 int64_t* idx_out, float* dist_out, int* gt_pos) {
+    const int q = blockIdx.x;
+    const int2 pool = qpool[q];
+    const int n = __builtin_amdgcn_readfirstlane(min(max(pool.y, 0), max_rows));       // a query no panel covered (a broken table) holds anything here
+    topk_select_row((const unsigned*)(dm + (size_t)q * ld), n, k, (int64_t)pool.x, idx_out + (size_t)q * k, dist_out + (size_t)q * k, gt ? gt[q] : -1,
+                    gt_pos ? gt_pos + q : nullptr);
 }
 
 // Last step of the filtered path, one block per query: the sample's k best (local rows < S) + the candidates that passed the filter
@@ -461,6 +514,44 @@ int ofx_launch_l2_topk(const float* Q, const float* P, int nq, int np, int D, in
     hipLaunchKernelGGL(dist_mfma_kernel<false>, dim3(dist_grid(tiles_q, (np + DT - 1) / DT)), dim3(256), DIST_LDS, s, Q, P, qn, pn, dm, nq, np, D, ld, 0,
                        (const float*)nullptr, 0, (int*)nullptr, (unsigned long long*)nullptr, 0, (const int*)flags, tiles_q);
     hipLaunchKernelGGL(topk_select_kernel, dim3(nq), dim3(256), 0, s, dm, ld, np, k, index_base, idx, dist, (const int*)flags);
+    OFX_LAUNCH_CHECK();
+    return OFX_OK;
+}
+
+// Workspace of the grouped call: norms of Q and P, the distance rows [nq, ld] (each query's own pool only), (p_lo, rows) per query.
+extern "C" size_t ofx_l2_topk_grouped_ws(int nq, int np, int max_group_rows) {
+    if (nq < 0 || np < 0 || max_group_rows < 0) return 0;
+    const size_t ld = ((size_t)max_group_rows + 3) / 4 * 4;
+    return al256((size_t)nq * 4) + al256((size_t)np * 4) + al256((size_t)nq * ld * 4) + al256((size_t)nq * 8);
+}
+
+int ofx_launch_l2_topk_grouped(const float* Q, const float* P, int nq, int np, int D, int k, const int* panels, int n_panels, int max_group_rows,
+                               const int64_t* gt, int64_t* idx, float* dist, int* gt_pos, void* ws, size_t ws_bytes, hipStream_t s) {
+    OFX_REQUIRE(Q && P && panels && idx && dist && ws, OFX_EINVAL, "l2_topk_grouped: NULL argument");
+    OFX_REQUIRE((gt != nullptr) == (gt_pos != nullptr), OFX_EINVAL, "l2_topk_grouped: gt and gt_pos go together");
+    OFX_REQUIRE(nq > 0 && np > 0 && D > 0 && D % 32 == 0, OFX_ESHAPE, "l2_topk_grouped: nq=%d np=%d D=%d (D must be a multiple of 32)", nq, np, D);
+    OFX_REQUIRE(k >= 1 && k <= KMAX, OFX_ESHAPE, "l2_topk_grouped: k=%d must be in [1, %d]", k, KMAX);
+    OFX_REQUIRE(n_panels >= 1 && max_group_rows >= 1, OFX_ESHAPE, "l2_topk_grouped: n_panels=%d max_group_rows=%d must be positive", n_panels, max_group_rows);
+    const size_t need = ofx_l2_topk_grouped_ws(nq, np, max_group_rows);
+    OFX_REQUIRE(ws_bytes >= need, OFX_EWORKSPACE, "l2_topk_grouped: workspace %zu < %zu bytes", ws_bytes, need);
+    OFX_REQUIRE(((uintptr_t)Q % 16 == 0) && ((uintptr_t)P % 16 == 0) && ((uintptr_t)panels % 16 == 0), OFX_EINVAL,
+                "l2_topk_grouped: Q, P and panels must be 16-byte aligned");
+    static DeviceOnce attr;
+    TRY(attr.run([]() -> int {
+        OFX_HIP(hipFuncSetAttribute((const void*)dist_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DIST_LDS));
+        return OFX_OK;
+    }));
+    const int ld = (max_group_rows + 3) / 4 * 4;
+    char* w = (char*)ws;
+    float* qn = (float*)w; w += al256((size_t)nq * 4);
+    float* pn = (float*)w; w += al256((size_t)np * 4);
+    float* dm = (float*)w; w += al256((size_t)nq * ld * 4);
+    int2* qpool = (int2*)w;
+    hipLaunchKernelGGL(sqnorm_kernel, dim3(std::min((nq + 3) / 4, 4096)), dim3(256), 0, s, Q, qn, nq, D);
+    hipLaunchKernelGGL(sqnorm_kernel, dim3(std::min((np + 3) / 4, 4096)), dim3(256), 0, s, P, pn, np, D);
+    hipLaunchKernelGGL(dist_grouped_kernel, dim3(dist_grid(n_panels, (max_group_rows + DT - 1) / DT)), dim3(256), DIST_LDS, s, Q, P, qn, pn, dm, nq, np, D, ld,
+                       (const int4*)panels, n_panels, max_group_rows, qpool);
+    hipLaunchKernelGGL(topk_select_grouped_kernel, dim3(nq), dim3(256), 0, s, dm, ld, max_group_rows, k, (const int2*)qpool, gt, idx, dist, gt_pos);
     OFX_LAUNCH_CHECK();
     return OFX_OK;
 }

@@ -383,6 +383,98 @@ class Engine:
                                          _ptr(ws), ws.numel(), _stream(self.device)), "ofx_l2_topk")
         return idx, dist
 
+    def l2_topk_grouped(self, Q: torch.Tensor, group_of_query, P: torch.Tensor, pool_offsets, k: int, gt=None, max_ws_bytes: int = 1 << 30):
+        """Category-pool retrieval (complementary_item_retrieval_trainer.py:192-249, demo/app.py:184-190): query i searches only pool
+        rows [pool_offsets[g], pool_offsets[g + 1]) of P, g = group_of_query[i].  One ofx_l2_topk_grouped call (4 launches) for all
+        groups, or one per chunk of queries when the distance buffer would exceed max_ws_bytes.
+
+        Q [nq, D] in the caller's order; group_of_query: nq host ints (sequence or CPU tensor); P [np, D]: all pools concatenated;
+        pool_offsets: G + 1 host ints; gt: optional nq rows of P (the ground truth inside the query's own pool; < 0 = none).
+        -> (idx int64 [nq, k] rows of P, dist fp32 [nq, k], gt_pos int32 [nq] | None), in the caller's order.  Per query the result has
+        the bits of l2_topk(Q[i:i+1], P[lo:hi], k, index_base=lo); a pool of fewer than k rows ends in idx -1 / dist +inf.  gt_pos is
+        the position of gt in idx, k when it is not among them, and -1 for a query without ground truth (parallel.grouped_recall
+        leaves those out of the ratio).  ValueError before any launch: a group id outside [0, G), a query whose pool is empty, offsets
+        that do not start at 0, decrease or end elsewhere than at np, a gt outside its query's pool, a max_ws_bytes that one query
+        does not fit."""
+        Q = _f32c(Q, self.device); P = _f32c(P, self.device)
+        nq, D = Q.shape
+        npool = P.shape[0]
+        grp = torch.as_tensor(group_of_query, device="cpu").to(torch.int64).reshape(-1)
+        off = torch.as_tensor(pool_offsets, device="cpu").to(torch.int64).reshape(-1)
+        G = off.numel() - 1
+        if G < 1 or int(off[0]) != 0 or int(off[-1]) != npool or bool((off[1:] < off[:-1]).any()):
+            raise ValueError("pool_offsets must start at 0, be non-decreasing and end at len(P)")
+        if grp.numel() != nq:
+            raise ValueError(f"group_of_query has {grp.numel()} entries for {nq} queries")
+        if nq and (int(grp.min()) < 0 or int(grp.max()) >= G):
+            raise ValueError(f"group_of_query must lie in [0, {G})")
+        q_lo, q_hi = off[grp], off[grp + 1]
+        if bool((q_hi == q_lo).any()):
+            raise ValueError("a query's pool is empty")
+        gt_h = None
+        if gt is not None:
+            gt_h = torch.as_tensor(gt).to(device="cpu", dtype=torch.int64).reshape(-1)
+            if gt_h.numel() != nq:
+                raise ValueError(f"gt has {gt_h.numel()} entries for {nq} queries")
+            if bool(((gt_h >= 0) & ((gt_h < q_lo) | (gt_h >= q_hi))).any()):
+                raise ValueError("a gt row lies outside its query's pool")
+        idx = torch.empty(nq, k, dtype=torch.int64, device=self.device)
+        dist = torch.empty(nq, k, dtype=torch.float32, device=self.device)
+        gt_pos = torch.empty(nq, dtype=torch.int32, device=self.device) if gt_h is not None else None
+        if nq == 0:
+            return idx, dist, gt_pos
+        max_rows = int((q_hi - q_lo).max())
+        need = lambda n: int(self.lib.ofx_l2_topk_grouped_ws(n, npool, max_rows))
+        if need(1) > max_ws_bytes:
+            raise ValueError(f"max_ws_bytes={max_ws_bytes}: one query against {max_rows} rows needs {need(1)} bytes")
+        lo, hi = 1, nq                                   # most queries per call whose workspace fits
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            lo, hi = (mid, hi) if need(mid) <= max_ws_bytes else (lo, mid - 1)
+        n_chunks = -(-nq // lo)
+        chunk = -(-nq // n_chunks)
+        # queries sorted by group (stable: the caller's order inside a group)
+        order = torch.argsort(grp, stable=True)
+        table, chunk_panels = _group_panels(grp[order], off, chunk)
+        table = table.to(self.device)
+        order_d = order.to(self.device)
+        Qs = Q.index_select(0, order_d)
+        gt_s = gt_h[order].to(self.device) if gt_h is not None else None
+        idx_s, dist_s = torch.empty_like(idx), torch.empty_like(dist)
+        pos_s = torch.empty_like(gt_pos) if gt_pos is not None else None
+        ws = self.workspace(need(chunk))
+        with torch.cuda.device(self.device):
+            for c0, c1, first, n_panels in chunk_panels:
+                L.check(self.lib.ofx_l2_topk_grouped(self.h, _ptr(Qs[c0:c1]), _ptr(P), c1 - c0, npool, D, k, _ptr(table[first:]), n_panels, max_rows,
+                                                     _ptr(gt_s[c0:c1]) if gt_s is not None else None, _ptr(idx_s[c0:c1]), _ptr(dist_s[c0:c1]),
+                                                     _ptr(pos_s[c0:c1]) if pos_s is not None else None, _ptr(ws), ws.numel(), _stream(self.device)),
+                        "ofx_l2_topk_grouped")
+        idx[order_d] = idx_s
+        dist[order_d] = dist_s
+        if gt_pos is not None:
+            gt_pos[order_d] = pos_s
+            if bool((gt_h < 0).any()):
+                gt_pos.masked_fill_(gt_h.to(self.device) < 0, -1)
+        return idx, dist, gt_pos
+
+
+def _group_panels(sorted_groups: torch.Tensor, offsets: torch.Tensor, chunk: int):
+    """The panel table of ofx_l2_topk_grouped for queries sorted by group, cut into calls of `chunk` queries (host int64 tensors in).
+    A panel is a run of queries of ONE group inside ONE call, at most 128 long: (q_lo, q_hi) relative to its call's first query, and
+    the group's pool rows (p_lo, p_hi).  -> (int32 [n_panels, 4], [(first query, end query, first panel, number of panels) per call])."""
+    nq, G = sorted_groups.numel(), offsets.numel() - 1
+    cnt = torch.bincount(sorted_groups, minlength=G)
+    start = torch.cumsum(cnt, 0) - cnt
+    cuts = [torch.arange(s, s + n, 128) for s, n in zip(start.tolist(), cnt.tolist()) if n]
+    calls = torch.arange(0, nq, chunk)
+    lo = torch.unique(torch.cat(cuts + [calls]))                  # sorted: every panel's first query
+    hi = torch.cat([lo[1:], torch.tensor([nq])])
+    g = sorted_groups[lo]
+    base = lo // chunk * chunk
+    table = torch.stack([lo - base, hi - base, offsets[g], offsets[g + 1]], 1).to(torch.int32)
+    first = torch.searchsorted(lo, calls).tolist() + [lo.numel()]
+    return table, [(c0, min(c0 + chunk, nq), first[i], first[i + 1] - first[i]) for i, c0 in enumerate(calls.tolist())]
+
 
 def fitb_argmin(y_hat: torch.Tensor, cand: torch.Tensor, return_dist: bool = False):
     """torch.cdist(y[B,1,D], cand[B,C,D]).squeeze(1).argmin(-1) on the GPU, fp32, first minimum."""

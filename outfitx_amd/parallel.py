@@ -10,10 +10,12 @@ backend 'nccl' (= RCCL over xGMI on ROCm) or 'gloo' (CPU tests).
   the fully connected xGMI mesh — and a local merge with a deterministic tie-break (smaller global
   index).  This step has no reference call site: the reference scores CIR on one GPU
   (complementary_item_retrieval_trainer.py:240-249); results are identical to the unsharded call.
+* CIR validation (recall@k inside the target's category pool, :192-249): the QUERIES are sharded by rank, the pools replicated; every rank
+  runs `Engine.l2_topk_grouped` on its queries and `grouped_recall` sums the integer hit counts in ONE all-reduce.
 """
 from __future__ import annotations
 
-from typing import Callable, Optional, Tuple
+from typing import Callable, Dict, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
@@ -73,3 +75,23 @@ def cir_topk(engine, queries: torch.Tensor, pool_shard: torch.Tensor, k: int, sh
     from .engine import topk_merge
     return sharded_topk(queries, pool_shard, k, shard_base,
                         lambda Q, P, kk, base: engine.l2_topk(Q, P, kk, index_base=base), topk_merge, group)
+
+
+def grouped_recall(gt_pos: torch.Tensor, k: int, top_k_list: Sequence[int], group=None) -> Dict[str, float]:
+    """Recall@K of a grouped retrieval for every K of top_k_list at once (compute_recall_metrics, cir_trainer:244-249).
+    gt_pos [n]: per query of THIS rank the position of its ground-truth row among its k nearest (Engine.l2_topk_grouped), k = not among
+    them, < 0 = the query has no ground truth and counts nowhere.  Every K must be <= k: a position beyond k is not known.
+    Integer hit counts per K and the number of valid queries are summed over the ranks in ONE all_reduce of an int64 vector (queries
+    sharded by rank; counts are summed, never ratios averaged, so uneven shards weigh right), then divided.  No valid query anywhere: 0.0."""
+    ks = [int(K) for K in top_k_list]
+    if any(K < 1 or K > k for K in ks):
+        raise ValueError(f"top_k_list {ks} must lie in [1, k = {k}]")
+    pos = gt_pos.reshape(-1)
+    valid = pos >= 0
+    counts = torch.stack([(valid & (pos < K)).sum() for K in ks] + [valid.sum()]).to(torch.int64)
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        if counts.is_cuda and dist.get_backend(group) == "gloo":
+            counts = counts.cpu()                        # gloo has no device all-reduce
+        dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=group)
+    c = counts.tolist()
+    return {f"Recall@{K}": (h / c[-1] if c[-1] else 0.0) for K, h in zip(ks, c)}

@@ -351,8 +351,10 @@ class CIRTrainer(FlatGradTrainer):
     """model(task=CIR, outfit_embedding=..., outfit_mask=..., target_item_text_embedding=...) -> [B, d_embed] target-item embeddings;
     batches are the reference's collate dicts (complementary_item_retrieval_trainer.py:73-87):
     {'input_dict': {...CIR task tensors...}, 'pos_item_embedding' [B,D], 'neg_items_embedding' [B,K,D], 'neg_items_mask' [B,K] bool}.
-    Replaces ComplementaryItemRetrievalTrainer.train_epoch (:66-116); negative sampling, the easy -> hard switch, checkpoints and the
-    recall@k validation loop stay with the caller (parallel.cir_topk covers the last)."""
+    Replaces ComplementaryItemRetrievalTrainer.train_epoch (:66-116) and, as `valid_epoch`, its validation loop with the recall@k inside
+    the target's category pool (:122-249; validation batches additionally carry 'pos_item_group' [B] and 'pos_item_row' [B], the
+    positive's category and its row inside that category's pool).  Negative sampling, the easy -> hard switch, checkpoints and logging
+    stay with the caller."""
 
     _sink_skip = (0, 2, 3)        # outfit_token and the CP head are not on the CIR path
 
@@ -402,3 +404,56 @@ class CIRTrainer(FlatGradTrainer):
             dist.all_reduce(total, op=dist.ReduceOp.SUM, group=self.group)
             total = total / self._world()
         return {"loss": float(total)}
+
+    def valid_epoch(self, batches: Iterable[dict], pools, top_k_list: Sequence[int] = (1, 5, 10, 15, 30, 50), with_recall: bool = True,
+                    topk_fn: Optional[Callable] = None) -> Dict[str, float]:
+        """valid_epoch (:122-191, without checkpointing and logging) + compute_recall_metrics (:192-249) on this rank's batches:
+        eval mode, no gradients; per batch the forward and the loss; at the end ONE grouped retrieval of all collected y_hat, each against
+        the pool of its positive's category, and parallel.grouped_recall over the ranks.
+        pools = (P [n_rows, D], pool_offsets [G + 1] host ints): all category pools concatenated, replicated on every rank.
+        topk_fn(Q, group_of_query, P, pool_offsets, k, gt=...) -> (idx, dist, gt_pos): Engine.l2_topk_grouped of the model's engine by
+        default (HIP only); k = max(top_k_list) as in the reference.  with_recall=False: the loss only (the reference computes recall
+        every fifth epoch).  -> {'loss': as train_epoch, 'Recall@K': ...}; the model's training flag is left as it was."""
+        was_training = self.model.training
+        self.model.eval()
+        dev = self.grads.flat.device
+        total = torch.zeros((), dtype=torch.float32, device=dev)
+        ys: List[torch.Tensor] = []; groups: List[torch.Tensor] = []; rows: List[torch.Tensor] = []
+        n = 0
+        try:
+            with torch.no_grad():
+                for batch in batches:
+                    inp = {k: (v if k == "task" else v.to(dev, non_blocking=True)) for k, v in batch["input_dict"].items()}
+                    y_hat = self.model(**inp)
+                    total += self.loss_fn(batch_y=batch["pos_item_embedding"].to(dev, non_blocking=True), batch_y_hat=y_hat,
+                                          batch_negative_samples=batch["neg_items_embedding"].to(dev, non_blocking=True),
+                                          batch_negative_mask=batch["neg_items_mask"].to(dev, non_blocking=True)).detach()
+                    n += 1
+                    if with_recall:
+                        ys.append(y_hat.detach())
+                        groups.append(torch.as_tensor(batch["pos_item_group"], device="cpu").to(torch.int64).reshape(-1))
+                        rows.append(torch.as_tensor(batch["pos_item_row"], device="cpu").to(torch.int64).reshape(-1))
+                total = total / max(n, 1)
+                if self._world() > 1:
+                    dist.all_reduce(total, op=dist.ReduceOp.SUM, group=self.group)
+                    total = total / self._world()
+                metrics = {"loss": float(total)}
+                if with_recall:
+                    from .parallel import grouped_recall
+                    P, offsets = pools
+                    k = max(int(K) for K in top_k_list)
+                    if topk_fn is None:
+                        if not hasattr(self.model, "_engine"):
+                            from ._lib import OfxError
+                            raise OfxError("valid_epoch: the grouped retrieval runs on a HIP model's engine only; pass topk_fn otherwise")
+                        topk_fn = self.model._engine().l2_topk_grouped
+                    if ys:
+                        grp = torch.cat(groups)
+                        gt = torch.as_tensor(offsets, device="cpu").to(torch.int64)[grp] + torch.cat(rows)
+                        gt_pos = topk_fn(torch.cat(ys), grp, P, offsets, k, gt=gt)[2]
+                    else:
+                        gt_pos = torch.empty(0, dtype=torch.int32, device=dev)           # a rank without batches still joins the all-reduce
+                    metrics.update(grouped_recall(gt_pos, k, top_k_list, self.group))
+        finally:
+            self.model.train(was_training)
+        return metrics
