@@ -6,7 +6,7 @@ PyTorch is plumbing here (device memory, streams); all arithmetic happens in lib
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -25,6 +25,19 @@ def _f32c(t: torch.Tensor, device) -> torch.Tensor:
     if t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
         t = t.to(device=device, dtype=torch.float32).contiguous()
     return t
+
+
+class SetInput(NamedTuple):
+    """A staged set input (Engine.stage_set).  `args` are the seven set-input arguments in ofx_cir_train_fwd's order - x, pad_mask,
+    table, ld, n_table, item_index, cu_items -: the dense form fills the first two, the indexed form the other five."""
+    B: int
+    L: int
+    staged: tuple            # the device tensors behind the pointers in `args` that this call may have made
+    args: tuple
+
+    @property
+    def indexed(self) -> bool:
+        return self.args[0] is None
 
 
 class Engine:
@@ -86,118 +99,62 @@ class Engine:
         return int(self.lib.ofx_workspace_bytes(self.h, op, n, length))
 
     # ---------------------------------------------------------------- outfit transformer
-    def set_encoder(self, x: torch.Tensor, mask: torch.Tensor, prefix: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x [B,L,D] float, mask [B,L] bool (True = pad) -> encoder output at the prefix token [B,D] fp32."""
-        B, Lq, D = x.shape
-        x = _f32c(x, self.device)
-        m = mask.to(device=self.device)
-        m = (m if m.dtype == torch.bool else m != 0).contiguous().view(torch.uint8)
-        stride = 0
-        if prefix is not None:
-            prefix = _f32c(prefix, self.device)
-            stride = 0 if prefix.dim() == 1 else D
-        out = torch.empty(B, D, dtype=torch.float32, device=self.device)
-        nb = self.ws_bytes(L.OP_SET_ENCODER, B, Lq)
-        ws = self.workspace(nb)
-        with torch.cuda.device(self.device):
-            L.check(self.lib.ofx_set_encoder_fwd(self.h, _ptr(x), _ptr(m), _ptr(prefix), stride, B, Lq, _ptr(out),
-                                                 _ptr(ws), ws.numel(), _stream(self.device)), "ofx_set_encoder_fwd")
-        return out
-
-    def _index_args(self, table: torch.Tensor, item_index: torch.Tensor, cu_seqlens: torch.Tensor):
-        """Validate / stage the indexed (varlen) set input.  Host-side index tensors are checked here (range, monotone
-        offsets, items per outfit); device-side ones are trusted (the kernel clamps indices)."""
-        if table.device != self.device or table.dtype != torch.float32 or table.dim() != 2 or table.stride(1) != 1:
-            raise L.OfxError("embedding table must be a [n, D] fp32 tensor on the engine's device with unit column stride")
-        if table.shape[1] != self.desc.d_model:
-            raise L.OfxError(f"embedding table has {table.shape[1]} columns, the model needs {self.desc.d_model}")
-        B = cu_seqlens.numel() - 1
-        if cu_seqlens.device.type == "cpu":
-            cu = cu_seqlens.to(torch.int64)
-            n = cu[1:] - cu[:-1]
-            if B < 1 or int(cu[0]) != 0 or bool((n < 0).any()) or int(cu[-1]) != item_index.numel():
-                raise ValueError("cu_seqlens must start at 0, be non-decreasing and end at len(item_index)")
-            max_items = int(n.max())
-        else:
-            max_items = None
-        if item_index.device.type == "cpu" and item_index.numel():
-            lo, hi = int(item_index.min()), int(item_index.max())
-            if lo < 0 or hi >= table.shape[0]:
-                raise IndexError(f"item_index out of range [0, {table.shape[0]}): min {lo}, max {hi}")
-        idx = item_index.to(device=self.device, dtype=torch.int32, non_blocking=True).contiguous()
-        cud = cu_seqlens.to(device=self.device, dtype=torch.int32, non_blocking=True).contiguous()
-        return idx, cud, B, max_items
-
-    def set_encoder_indexed(self, table: torch.Tensor, item_index: torch.Tensor, cu_seqlens: torch.Tensor, max_len: int,
-                            prefix: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Outfits as row indices into a device-resident embedding table -> encoder output at the prefix token [B,D]."""
-        idx, cud, B, max_items = self._index_args(table, item_index, cu_seqlens)
-        if max_items is not None and max_items > max_len:
-            raise ValueError(f"an outfit holds {max_items} items, max_len is {max_len} (truncate in the processor)")
-        D = self.desc.d_model
-        stride = 0
-        if prefix is not None:
-            prefix = _f32c(prefix, self.device)
-            stride = 0 if prefix.dim() == 1 else D
-        out = torch.empty(B, D, dtype=torch.float32, device=self.device)
-        ws = self.workspace(self.ws_bytes(L.OP_SET_ENCODER, B, max_len))
-        with torch.cuda.device(self.device):
-            L.check(self.lib.ofx_set_encoder_fwd_indexed(self.h, _ptr(table), table.stride(0), table.shape[0], _ptr(idx), _ptr(cud), _ptr(prefix), stride,
-                                                         B, max_len, _ptr(out), _ptr(ws), ws.numel(), _stream(self.device)), "ofx_set_encoder_fwd_indexed")
-        self._keep_idx = (idx, cud)
-        return out
-
-    def cp_train_fwd_indexed(self, table, item_index, cu_seqlens, max_len: int, dropout_p: float = 0.0, seed: int = 0):
-        idx, cud, B, max_items = self._index_args(table, item_index, cu_seqlens)
-        if max_items is not None and max_items > max_len:
-            raise ValueError(f"an outfit holds {max_items} items, max_len is {max_len} (truncate in the processor)")
-        tape = torch.empty(int(self.lib.ofx_cp_train_tape_bytes(self.h, B, max_len)), dtype=torch.uint8, device=self.device)
-        ws = self.workspace(int(self.lib.ofx_cp_train_ws_bytes(self.h, B, max_len)))
-        logits = torch.empty(B, 1, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            L.check(self.lib.ofx_cp_train_fwd_indexed(self.h, _ptr(table), table.stride(0), table.shape[0], _ptr(idx), _ptr(cud), B, max_len, _ptr(logits),
-                                                      _ptr(tape), tape.numel(), _ptr(ws), ws.numel(), float(dropout_p), int(seed) & 0xFFFFFFFF,
-                                                      _stream(self.device)), "ofx_cp_train_fwd_indexed")
-        self._keep_idx = (idx, cud)
-        return logits, tape
-
-    def cir_train_fwd(self, setin, target_text: torch.Tensor, dropout_p: float = 0.0, seed: int = 0):
-        """Tape-saving CIR forward.  setin: (x [B,L,D], mask [B,L]) or (table, item_index, cu_seqlens, max_len).
-        -> (y [B,D] fp32, tape, (B, L))"""
-        txt = _f32c(target_text, self.device)
-        null = None
+    def stage_set(self, setin) -> "SetInput":
+        """The one place that validates and stages a set input: (x [B,L,D] float, mask [B,L], True / non-zero = pad) or the indexed
+        (varlen) form (table [n,D], item_index, cu_seqlens, max_len).  Host-side index tensors are checked here (range, monotone
+        offsets, items per outfit); device-side ones are trusted (the kernel clamps indices).  The staged tensors stay referenced
+        until the next call: the kernels (and the non-blocking copies) read them asynchronously on the current stream."""
         if len(setin) == 4:
             table, item_index, cu_seqlens, Lq = setin
-            idx, cud, B, max_items = self._index_args(table, item_index, cu_seqlens)
+            if table.device != self.device or table.dtype != torch.float32 or table.dim() != 2 or table.stride(1) != 1:
+                raise L.OfxError("embedding table must be a [n, D] fp32 tensor on the engine's device with unit column stride")
+            if table.shape[1] != self.desc.d_model:
+                raise L.OfxError(f"embedding table has {table.shape[1]} columns, the model needs {self.desc.d_model}")
+            B = cu_seqlens.numel() - 1
+            max_items = None
+            if cu_seqlens.device.type == "cpu":
+                cu = cu_seqlens.to(torch.int64)
+                n = cu[1:] - cu[:-1]
+                if B < 1 or int(cu[0]) != 0 or bool((n < 0).any()) or int(cu[-1]) != item_index.numel():
+                    raise ValueError("cu_seqlens must start at 0, be non-decreasing and end at len(item_index)")
+                max_items = int(n.max())
+            if item_index.device.type == "cpu" and item_index.numel():
+                lo, hi = int(item_index.min()), int(item_index.max())
+                if lo < 0 or hi >= table.shape[0]:
+                    raise IndexError(f"item_index out of range [0, {table.shape[0]}): min {lo}, max {hi}")
+            idx = item_index.to(device=self.device, dtype=torch.int32, non_blocking=True).contiguous()
+            cud = cu_seqlens.to(device=self.device, dtype=torch.int32, non_blocking=True).contiguous()
             if max_items is not None and max_items > Lq:
                 raise ValueError(f"an outfit holds {max_items} items, max_len is {Lq} (truncate in the processor)")
-            args = (null, null, _ptr(table), table.stride(0), table.shape[0], _ptr(idx), _ptr(cud))
-            self._keep_idx = (idx, cud)
+            s = SetInput(B, Lq, (idx, cud), (None, None, _ptr(table), table.stride(0), table.shape[0], _ptr(idx), _ptr(cud)))
         else:
             x, mask = setin
             B, Lq, _ = x.shape
             x = _f32c(x, self.device)
             m = mask.to(device=self.device)
             m = (m if m.dtype == torch.bool else m != 0).contiguous().view(torch.uint8)
-            args = (_ptr(x), _ptr(m), null, 0, 0, null, null)
-            self._keep_idx = (x, m)
-        tape = torch.empty(int(self.lib.ofx_cp_train_tape_bytes(self.h, B, Lq)), dtype=torch.uint8, device=self.device)
-        ws = self.workspace(int(self.lib.ofx_cp_train_ws_bytes(self.h, B, Lq)))
-        y = torch.empty(B, self.desc.d_model, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            L.check(self.lib.ofx_cir_train_fwd(self.h, *args, _ptr(txt), B, Lq, _ptr(y), _ptr(tape), tape.numel(), _ptr(ws), ws.numel(),
-                                               float(dropout_p), int(seed) & 0xFFFFFFFF, _stream(self.device)), "ofx_cir_train_fwd")
-        return y, tape, (B, Lq)
+            s = SetInput(B, Lq, (x, m), (_ptr(x), _ptr(m), None, 0, 0, None, None))
+        self._keep_set = s.staged
+        return s
 
-    def cir_train_bwd(self, tape: torch.Tensor, dy: torch.Tensor, B: int, Lq: int, dropout_p: float = 0.0, seed: int = 0) -> torch.Tensor:
-        total, _ = self.grad_layout()
-        g = torch.empty(total, dtype=torch.float32, device=self.device)
-        d = _f32c(dy, self.device)
-        ws = self.workspace(int(self.lib.ofx_cp_train_ws_bytes(self.h, B, Lq)))
+    def _prefix(self, prefix: Optional[torch.Tensor]):
+        """Prefix token(s) -> (staged fp32 tensor or None, row stride): one [D] row for every outfit (stride 0) or one row per outfit."""
+        if prefix is None:
+            return None, 0
+        prefix = _f32c(prefix, self.device)
+        return prefix, 0 if prefix.dim() == 1 else self.desc.d_model
+
+    def set_encoder(self, setin, prefix: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """setin (either form of stage_set) -> encoder output at the prefix token [B,D] fp32."""
+        s = self.stage_set(setin)
+        prefix, stride = self._prefix(prefix)
+        out = torch.empty(s.B, self.desc.d_model, dtype=torch.float32, device=self.device)
+        ws = self.workspace(self.ws_bytes(L.OP_SET_ENCODER, s.B, s.L))
+        name, lead = ("ofx_set_encoder_fwd_indexed", s.args[2:]) if s.indexed else ("ofx_set_encoder_fwd", s.args[:2])
         with torch.cuda.device(self.device):
-            L.check(self.lib.ofx_cir_train_bwd(self.h, _ptr(tape), tape.numel(), _ptr(d), B, Lq, _ptr(g), total, _ptr(ws), ws.numel(),
-                                               float(dropout_p), int(seed) & 0xFFFFFFFF, _stream(self.device)), "ofx_cir_train_bwd")
-        return g
+            L.check(getattr(self.lib, name)(self.h, *lead, _ptr(prefix), stride, s.B, s.L, _ptr(out), _ptr(ws), ws.numel(),
+                                            _stream(self.device)), name)
+        return out
 
     def cp_head(self, row0: torch.Tensor) -> torch.Tensor:
         B = row0.shape[0]
@@ -222,36 +179,53 @@ class Engine:
             L.check(self.lib.ofx_cir_prefix(self.h, _ptr(t), B, _ptr(out), _stream(self.device)), "ofx_cir_prefix")
         return out
 
-    # ---------------------------------------------------------------- training step (CP path, next row N1)
+    # ---------------------------------------------------------------- training step (CP and CIR paths, next row N1)
     def grad_layout(self):
         n = 5 + 12 * self.desc.n_layers
         offs = (C.c_size_t * n)()
         total = int(self.lib.ofx_cp_train_grad_floats(self.h, offs, n))
         return total, list(offs)
 
-    def cp_train_fwd(self, x: torch.Tensor, mask: torch.Tensor, dropout_p: float = 0.0, seed: int = 0):
-        """Tape-saving CP forward: x [B,L,D], mask [B,L] (True = pad) -> (logits [B,1] fp32, tape uint8 tensor)."""
-        B, Lq, D = x.shape
-        x = _f32c(x, self.device)
-        m = mask.to(device=self.device)
-        m = (m if m.dtype == torch.bool else m != 0).contiguous().view(torch.uint8)
-        tape = torch.empty(int(self.lib.ofx_cp_train_tape_bytes(self.h, B, Lq)), dtype=torch.uint8, device=self.device)
-        ws = self.workspace(int(self.lib.ofx_cp_train_ws_bytes(self.h, B, Lq)))
-        logits = torch.empty(B, 1, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            L.check(self.lib.ofx_cp_train_fwd(self.h, _ptr(x), _ptr(m), B, Lq, _ptr(logits), _ptr(tape), tape.numel(),
-                                              _ptr(ws), ws.numel(), float(dropout_p), int(seed) & 0xFFFFFFFF, _stream(self.device)), "ofx_cp_train_fwd")
-        return logits, tape
+    def _train_ws(self, B: int, Lq: int) -> torch.Tensor:
+        return self.workspace(int(self.lib.ofx_cp_train_ws_bytes(self.h, B, Lq)))
 
-    def cp_train_bwd(self, tape: torch.Tensor, dlogits: torch.Tensor, B: int, Lq: int, dropout_p: float = 0.0, seed: int = 0) -> torch.Tensor:
-        """d loss / d logits [B,1] -> flat fp32 gradient buffer (layout: grad_layout())."""
-        total, _ = self.grad_layout()
-        g = torch.empty(total, dtype=torch.float32, device=self.device)
-        dl = _f32c(dlogits, self.device)
-        ws = self.workspace(int(self.lib.ofx_cp_train_ws_bytes(self.h, B, Lq)))
+    def train_fwd(self, head: str, setin, target_text: Optional[torch.Tensor] = None, dropout_p: float = 0.0, seed: int = 0):
+        """Tape-saving forward of the CP ('cp': -> logits [B,1]) or the CIR / FITB ('cir': target_text [B,512] -> y [B,D]) path over
+        either form of set input (stage_set).  -> (out fp32, tape uint8 tensor - a fresh one per call, owned by the caller -, (B, L))"""
+        width = {"cp": 1, "cir": self.desc.d_model}[head]
+        txt = _f32c(target_text, self.device) if head == "cir" else None
+        s = self.stage_set(setin)
+        tape = torch.empty(int(self.lib.ofx_cp_train_tape_bytes(self.h, s.B, s.L)), dtype=torch.uint8, device=self.device)
+        ws = self._train_ws(s.B, s.L)
+        out = torch.empty(s.B, width, dtype=torch.float32, device=self.device)
+        if head == "cir":
+            name, lead = "ofx_cir_train_fwd", s.args + (_ptr(txt),)
+        else:
+            name, lead = ("ofx_cp_train_fwd_indexed", s.args[2:]) if s.indexed else ("ofx_cp_train_fwd", s.args[:2])
         with torch.cuda.device(self.device):
-            L.check(self.lib.ofx_cp_train_bwd(self.h, _ptr(tape), tape.numel(), _ptr(dl), B, Lq, _ptr(g), total,
-                                              _ptr(ws), ws.numel(), float(dropout_p), int(seed) & 0xFFFFFFFF, _stream(self.device)), "ofx_cp_train_bwd")
+            L.check(getattr(self.lib, name)(self.h, *lead, s.B, s.L, _ptr(out), _ptr(tape), tape.numel(), _ptr(ws), ws.numel(),
+                                            float(dropout_p), int(seed) & 0xFFFFFFFF, _stream(self.device)), name)
+        return out, tape, (s.B, s.L)
+
+    def train_bwd(self, head: str, tape: torch.Tensor, dhead: torch.Tensor, B: int, Lq: int, dropout_p: float = 0.0, seed: int = 0,
+                  dests=None) -> Optional[torch.Tensor]:
+        """Backward of the 'cp' / 'cir' path from d loss / d head output ([B,1] / [B,D]).  dests None: -> a flat fp32 gradient buffer
+        (layout: grad_layout()).  dests given (one fp32 contiguous tensor of the parameter's shape per packed tensor, None for tensors
+        off the path): every gradient is ADDED straight into them - p.grad += g without the 75 accumulate kernels of autograd - and
+        nothing is returned."""
+        if dests is None:
+            total, _ = self.grad_layout()
+            g = torch.empty(total, dtype=torch.float32, device=self.device)
+            name, sink = f"ofx_{head}_train_bwd", (_ptr(g), total)
+        else:
+            g = None
+            ptrs = (C.c_void_p * len(dests))(*[None if t is None else t.data_ptr() for t in dests])
+            name, sink = f"ofx_{head}_train_bwd_into", (ptrs, len(dests), 1)         # 1: accumulate
+        d = _f32c(dhead, self.device)
+        ws = self._train_ws(B, Lq)
+        with torch.cuda.device(self.device):
+            L.check(getattr(self.lib, name)(self.h, _ptr(tape), tape.numel(), _ptr(d), B, Lq, *sink, _ptr(ws), ws.numel(),
+                                            float(dropout_p), int(seed) & 0xFFFFFFFF, _stream(self.device)), name)
         return g
 
     def arm_layer_events(self, events) -> None:
@@ -259,19 +233,6 @@ class Engine:
         the NEXT backward call records events[l] when layer l's gradients are final (ofx_train_arm_layer_events)."""
         arr = (C.c_void_p * len(events))(*[int(e.cuda_event) for e in events])
         L.check(self.lib.ofx_train_arm_layer_events(self.h, arr, len(events)), "ofx_train_arm_layer_events")
-
-    def train_bwd_into(self, head: str, tape: torch.Tensor, dhead: torch.Tensor, B: int, Lq: int, dests, accumulate: bool,
-                       dropout_p: float = 0.0, seed: int = 0) -> None:
-        """Backward of the CP ('cp') or CIR ('cir') path writing every gradient straight into `dests` (one fp32 contiguous
-        tensor of the parameter's shape per packed tensor, None for tensors off the path) - p.grad += g without the 75
-        accumulate kernels of autograd."""
-        ptrs = (C.c_void_p * len(dests))(*[None if t is None else t.data_ptr() for t in dests])
-        d = _f32c(dhead, self.device)
-        ws = self.workspace(int(self.lib.ofx_cp_train_ws_bytes(self.h, B, Lq)))
-        fn = self.lib.ofx_cp_train_bwd_into if head == "cp" else self.lib.ofx_cir_train_bwd_into
-        with torch.cuda.device(self.device):
-            L.check(fn(self.h, _ptr(tape), tape.numel(), _ptr(d), B, Lq, ptrs, len(dests), int(accumulate), _ptr(ws), ws.numel(),
-                       float(dropout_p), int(seed) & 0xFFFFFFFF, _stream(self.device)), f"ofx_{head}_train_bwd_into")
 
     # ---------------------------------------------------------------- towers
     def vit(self, pixels: torch.Tensor, out: torch.Tensor, col: int, normalize: bool) -> None:

@@ -58,42 +58,41 @@ except ImportError:                                   # older torch: CPTrainer /
     pass
 
 
-class _CPTrainFn(torch.autograd.Function):
-    """CP path with a hand-written backward (libofx_hip.so: ofx_cp_train_fwd / ofx_cp_train_bwd).  Gradients flow to
-    the outfit transformer, outfit_token and cp_ffn; the embeddings are data (cp_trainer feeds precomputed ones)."""
+# Indices into OutfitX._outfit_tensors() that a head's backward never touches: the CP path leaves target_item_image_emb and cir_ffn
+# alone, the CIR / FITB path outfit_token and the CP head.  They get no gradient, and gradient-sink mode asks nothing of their .grad.
+HEAD_OFF_PATH = {"cp": (1, 4), "cir": (0, 2, 3)}
+
+
+class _TrainFn(torch.autograd.Function):
+    """Training path of one head with the hand-written backward (Engine.train_fwd / train_bwd over ofx_{cp,cir}_train_fwd /
+    ofx_{cp,cir}_train_bwd[_into]).  'cp': gradients flow to the outfit transformer, outfit_token and cp_ffn; 'cir' (CIR / FITB): to the
+    transformer, target_item_image_emb and cir_ffn.  The embeddings are data (the trainers feed precomputed ones).  sink: gradient-sink
+    mode (OutfitX.grad_sink) as it stood when the forward ran."""
+
+    N_LEAD = 7                # forward's arguments in front of *params: backward returns None for each
 
     @staticmethod
-    def forward(ctx, eng, x, mask, F, drop, *params):
-        if isinstance(x, tuple):                  # indexed (varlen) input: (table, item_index, cu_seqlens, max_len)
-            table, idx, cu, max_len = x
-            logits, tape = eng.cp_train_fwd_indexed(table, idx, cu, max_len, *drop)
-            bl = (cu.numel() - 1, max_len)
-        else:
-            logits, tape = eng.cp_train_fwd(x, mask, *drop)
-            bl = (x.shape[0], x.shape[1])
-        ctx.eng, ctx.tape, ctx.bl, ctx.F, ctx.drop = eng, tape, bl, F, drop
+    def forward(ctx, eng, head, setin, txt, F, drop, sink, *params):
+        out, ctx.tape, ctx.bl = eng.train_fwd(head, setin, txt, *drop)
+        ctx.eng, ctx.head, ctx.F, ctx.drop = eng, head, F, drop
         ctx.shapes = [tuple(p.shape) for p in params]
-        ctx.params = params if getattr(eng, "grad_sink", False) else None
-        return logits
+        ctx.params = params if sink else None
+        return out
 
     @staticmethod
-    def backward(ctx, dlogits):
-        eng = ctx.eng
-        B, Lq = ctx.bl
-        dests = _sink_dests(ctx.params, (1, 4)) if ctx.params is not None else None
-        if dests is not None:
-            eng.train_bwd_into("cp", ctx.tape, dlogits.contiguous(), B, Lq, dests, True, *ctx.drop)
-            ctx.tape = None
-            return (None,) * (5 + len(ctx.shapes))
-        g = eng.cp_train_bwd(ctx.tape, dlogits.contiguous(), B, Lq, *ctx.drop)
+    def backward(ctx, dhead):
+        eng, skip = ctx.eng, HEAD_OFF_PATH[ctx.head]
+        dests = _sink_dests(ctx.params, skip) if ctx.params is not None else None
+        g = eng.train_bwd(ctx.head, ctx.tape, dhead.contiguous(), *ctx.bl, *ctx.drop, dests=dests)
         ctx.tape = None
+        if dests is not None:                     # the kernels have added into every p.grad already
+            return (None,) * (_TrainFn.N_LEAD + len(ctx.shapes))
         _, offs = eng.grad_layout()
-        out = _grad_views(g, offs, ctx.shapes, eng.desc.d_model, ctx.F, skip=(1, 4))   # target_item_image_emb, cir_ffn: not on the CP path
-        return (None, None, None, None, None, *out)
+        return (None,) * _TrainFn.N_LEAD + tuple(_grad_views(g, offs, ctx.shapes, eng.desc.d_model, ctx.F, skip))
 
 
 def _sink_dests(params, skip):
-    """Gradient-sink mode (OutfitX.grad_sink, set by trainer.CPTrainer): every parameter on the path already owns a dense fp32
+    """Gradient-sink mode (OutfitX.grad_sink, set by trainer.FlatGradTrainer): every parameter on the path already owns a dense fp32
     .grad on its own device -> the backward kernels add into those buffers directly."""
     dests = []
     for i, p in enumerate(params):
@@ -127,32 +126,6 @@ def _grad_views(g, offs, shapes, D, F, skip):
                 n *= v
             out.append(g[offs[i]:offs[i] + n].view(shp))
     return out
-
-
-class _CIRTrainFn(torch.autograd.Function):
-    """CIR / FITB path with the hand-written backward (ofx_cir_train_fwd / ofx_cir_train_bwd): gradients reach the
-    transformer, target_item_image_emb and cir_ffn (the CP head and outfit_token are not on this path)."""
-
-    @staticmethod
-    def forward(ctx, eng, setin, txt, F, drop, *params):
-        y, tape, bl = eng.cir_train_fwd(setin, txt, *drop)
-        ctx.eng, ctx.tape, ctx.bl, ctx.F, ctx.drop = eng, tape, bl, F, drop
-        ctx.shapes = [tuple(p.shape) for p in params]
-        ctx.params = params if getattr(eng, "grad_sink", False) else None
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        eng = ctx.eng
-        dests = _sink_dests(ctx.params, (0, 2, 3)) if ctx.params is not None else None
-        if dests is not None:
-            eng.train_bwd_into("cir", ctx.tape, dy.contiguous(), *ctx.bl, dests, True, *ctx.drop)
-            ctx.tape = None
-            return (None,) * (5 + len(ctx.shapes))
-        g = eng.cir_train_bwd(ctx.tape, dy.contiguous(), *ctx.bl, *ctx.drop)
-        ctx.tape = None
-        _, offs = eng.grad_layout()
-        return (None, None, None, None, None, *_grad_views(g, offs, ctx.shapes, eng.desc.d_model, ctx.F, skip=(0, 2, 3)))
 
 
 class OutfitX(nn.Module):
@@ -265,9 +238,9 @@ class OutfitX(nn.Module):
         """north-star alias of ItemEncoder.forward: [B,L] items -> [B,L,d_embed]."""
         return self.item_encoder(images, texts)
 
-    def _run_encoder(self, outfit_embedding, outfit_mask, prefix=None, precision: Optional[str] = None):
+    def _run_encoder(self, setin, prefix=None, precision: Optional[str] = None):
         eng = self._engine(precision)
-        return eng, eng.set_encoder(outfit_embedding, outfit_mask, prefix)
+        return eng, eng.set_encoder(setin, prefix)
 
     def _tower_fed(self) -> Optional[str]:
         """Precision of the set transformer for embeddings the towers produced in this call (see __init__)."""
@@ -280,11 +253,20 @@ class OutfitX(nn.Module):
         index lists (`item_index`, `cu_seqlens` from processor.OutfitXIndexed*Processor) instead of padded tensors."""
         self.embedding_table = table.to(device=self.device, dtype=torch.float32).contiguous()
 
-    def _indexed(self, item_index, cu_seqlens, embedding_table, max_len):
+    def _grad_mode(self) -> bool:
+        return self.training and torch.is_grad_enabled()
+
+    def _set_input(self, outfit_embedding, outfit_mask, item_index=None, cu_seqlens=None, embedding_table=None, max_len=None):
+        """A forward's set arguments -> the `setin` tuple of Engine.stage_set: (outfit_embedding, outfit_mask), or - when item_index is
+        given - (table, item_index, cu_seqlens, max_len); max_len defaults to the longest outfit the kernels of this mode take."""
+        if item_index is None:
+            return outfit_embedding, outfit_mask
         table = embedding_table if embedding_table is not None else getattr(self, "embedding_table", None)
         if table is None:
             raise ValueError("indexed input needs an embedding table: pass embedding_table= or call set_embedding_table()")
-        return table, item_index, cu_seqlens, int(max_len if max_len is not None else min(self.cfg.max_length, 63 if not (self.training and torch.is_grad_enabled()) else 31))
+        if max_len is None:
+            max_len = min(self.cfg.max_length, 31 if self._grad_mode() else 63)
+        return table, item_index, cu_seqlens, int(max_len)
 
     def _cp_forward(self, outfit_embedding: Optional[torch.Tensor] = None, outfit_mask: Optional[torch.Tensor] = None,
                     encoder_input_dict: Optional[dict] = None, *, item_index: Optional[torch.Tensor] = None,
@@ -292,14 +274,8 @@ class OutfitX(nn.Module):
                     max_len: Optional[int] = None) -> torch.Tensor:
         """outfit_x.py:120-144 -> raw compatibility logits [B,1].  Beyond the reference's arguments: the indexed form
         (item_index, cu_seqlens[, embedding_table, max_len]) — same result as the padded tensors built from those rows."""
-        if item_index is not None:
-            spec = self._indexed(item_index, cu_seqlens, embedding_table, max_len)
-            if self.training and torch.is_grad_enabled():
-                return self._cp_train_forward(spec, None)
-            eng = self._engine()
-            return eng.cp_head(eng.set_encoder_indexed(*spec))
         prec = None
-        if encoder_input_dict is not None:
+        if item_index is None and encoder_input_dict is not None:
             if outfit_embedding is None and not self.training and getattr(self, "graph_replay", False):
                 from .graphs import ForwardReplay
                 if ForwardReplay.eligible(self, outfit_mask, encoder_input_dict):
@@ -309,9 +285,10 @@ class OutfitX(nn.Module):
                                             lambda: self._cp_eval(outfit_mask, encoder_input_dict["images"], None, encoder_input_dict["texts"]))
             outfit_embedding = self.item_encoder(**encoder_input_dict)
             prec = self._tower_fed()
-        if self.training and torch.is_grad_enabled():
-            return self._cp_train_forward(outfit_embedding, outfit_mask)
-        eng, row0 = self._run_encoder(outfit_embedding, outfit_mask, precision=prec)
+        setin = self._set_input(outfit_embedding, outfit_mask, item_index, cu_seqlens, embedding_table, max_len)
+        if self._grad_mode():
+            return self._train_forward("cp", setin)
+        eng, row0 = self._run_encoder(setin, precision=prec)
         return eng.cp_head(row0)
 
     def _cp_eval(self, outfit_mask, images, prepared_texts, texts=None) -> torch.Tensor:
@@ -319,61 +296,47 @@ class OutfitX(nn.Module):
         tokens already staged on the device)."""
         with torch.no_grad():
             emb = self.item_encoder(images, texts, prepared_texts=prepared_texts)
-            eng, row0 = self._run_encoder(emb, outfit_mask, precision=self._tower_fed())
+            eng, row0 = self._run_encoder(self._set_input(emb, outfit_mask), precision=self._tower_fed())
             return eng.cp_head(row0)
 
-    def sink_ready(self, skip=(1, 4)) -> bool:
-        """True when the next CP backward will add straight into the parameters' own .grad buffers (gradient-sink mode with a dense
-        fp32 .grad on every tensor of the path): only then are a layer's gradients final where the backward records its event -
-        with the autograd fallback they land in a private buffer and AccumulateGrad adds them later (trainer.CPTrainer checks this
-        before arming the overlapped reduction)."""
-        return bool(getattr(self, "grad_sink", False)) and _sink_dests(self._outfit_tensors(), skip) is not None
+    def sink_ready(self, head: str = "cp") -> bool:
+        """True when the next backward of `head` ('cp' | 'cir') will add straight into the parameters' own .grad buffers (gradient-sink
+        mode with a dense fp32 .grad on every tensor of the path): only then are a layer's gradients final where the backward records
+        its event - with the autograd fallback they land in a private buffer and AccumulateGrad adds them later (trainer.FlatGradTrainer
+        checks this before arming the overlapped reduction)."""
+        return bool(getattr(self, "grad_sink", False)) and _sink_dests(self._outfit_tensors(), HEAD_OFF_PATH[head]) is not None
 
     def arm_bwd_layer_events(self, events) -> None:
         """Data-parallel overlap (trainer.CPTrainer): the next backward of the training step records events[l] when layer l's
         gradients are final."""
         self._engine(self.train_precision).arm_layer_events(events)
 
-    def _cp_train_forward(self, outfit_embedding, outfit_mask):
-        """CP trainer step (compatibility_prediction_trainer.py:57-81): forward with a tape, backward in libofx_hip.so."""
+    def _train_forward(self, head: str, setin, target_text: Optional[torch.Tensor] = None):
+        """Trainer step of either head (compatibility_prediction_trainer.py:57-81, complementary_item_retrieval_trainer.py:73-92):
+        forward with a tape, backward in libofx_hip.so."""
         t = self.cfg.transformer
         if self.train_precision not in ("bf16", "f16"):
             raise ValueError("train_precision must be 'bf16' or 'f16'")
-        if isinstance(outfit_embedding, torch.Tensor) and outfit_embedding.requires_grad:
-            raise NotImplementedError("gradients w.r.t. the item embeddings (encoder fine-tuning) are not built")
+        x = setin[0] if len(setin) == 2 else None          # the indexed form's table is data
+        if any(isinstance(v, torch.Tensor) and v.requires_grad for v in (x, target_text)):
+            what = "item" if head == "cp" else "item / text"
+            raise NotImplementedError(f"gradients w.r.t. the {what} embeddings (encoder fine-tuning) are not built")
         eng = self._engine(self.train_precision)
-        eng.grad_sink = bool(getattr(self, "grad_sink", False))
         # dropout masks are hash(seed, site, element); the seed is drawn from torch's global generator, so
         # torch.manual_seed() makes a run reproducible (same distribution as torch's dropout, not the same stream)
         p = float(t.dropout)
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p > 0.0 else 0
         self.last_dropout = (p, seed)
-        return _CPTrainFn.apply(eng, outfit_embedding, outfit_mask, t.d_ffn, (p, seed), *self._outfit_tensors())
+        return _TrainFn.apply(eng, head, setin, target_text, t.d_ffn, (p, seed), bool(getattr(self, "grad_sink", False)),
+                              *self._outfit_tensors())
 
     def _cir_forward(self, outfit_embedding: Optional[torch.Tensor] = None, outfit_mask: Optional[torch.Tensor] = None,
                      target_item_text_embedding: Optional[torch.Tensor] = None, *, item_index: Optional[torch.Tensor] = None,
                      cu_seqlens: Optional[torch.Tensor] = None, embedding_table: Optional[torch.Tensor] = None,
                      max_len: Optional[int] = None) -> torch.Tensor:
         """outfit_x.py:147-172 -> target-item embedding [B, d_embed] (indexed form as in _cp_forward)."""
-        if self.training and torch.is_grad_enabled():
-            t = self.cfg.transformer
-            if self.train_precision not in ("bf16", "f16"):
-                raise ValueError("train_precision must be 'bf16' or 'f16'")
-            if (isinstance(outfit_embedding, torch.Tensor) and outfit_embedding.requires_grad) or target_item_text_embedding.requires_grad:
-                raise NotImplementedError("gradients w.r.t. the item / text embeddings (encoder fine-tuning) are not built")
-            setin = (self._indexed(item_index, cu_seqlens, embedding_table, max_len) if item_index is not None
-                     else (outfit_embedding, outfit_mask))
-            p = float(t.dropout)
-            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p > 0.0 else 0
-            self.last_dropout = (p, seed)
-            eng = self._engine(self.train_precision)
-            eng.grad_sink = bool(getattr(self, "grad_sink", False))
-            return _CIRTrainFn.apply(eng, setin, target_item_text_embedding, t.d_ffn, (p, seed), *self._outfit_tensors())
+        setin = self._set_input(outfit_embedding, outfit_mask, item_index, cu_seqlens, embedding_table, max_len)
+        if self._grad_mode():
+            return self._train_forward("cir", setin, target_item_text_embedding)
         eng = self._engine()
-        prefix = eng.cir_prefix(target_item_text_embedding)
-        if item_index is not None:
-            table, idx, cu, ml = self._indexed(item_index, cu_seqlens, embedding_table, max_len)
-            row0 = eng.set_encoder_indexed(table, idx, cu, ml, prefix)
-        else:
-            row0 = eng.set_encoder(outfit_embedding, outfit_mask, prefix)
-        return eng.cir_head(row0)
+        return eng.cir_head(eng.set_encoder(setin, eng.cir_prefix(target_item_text_embedding)))

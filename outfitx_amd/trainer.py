@@ -183,8 +183,7 @@ class FlatGradTrainer:
     alone); both stay on the device.  The OneCycleLR schedule advances whether or not the step was skipped: the schedule counts
     accumulation windows, and finding out would cost a host synchronisation per step."""
 
-    # OutfitX._outfit_tensors() entries that are NOT on the task's path (sink_ready ignores them): CP skips target_item_image_emb, cir_ffn
-    _sink_skip = (1, 4)
+    head = "cp"                   # the model head this trainer's backward runs through (outfit_x.HEAD_OFF_PATH): what sink_ready() is asked about
 
     def __init__(self, model: torch.nn.Module, steps_per_epoch: int, cfg, loss_fn: Callable,
                  params: Optional[Iterable[torch.nn.Parameter]] = None, group=None):
@@ -210,7 +209,7 @@ class FlatGradTrainer:
         self.last_step_skipped: Optional[torch.Tensor] = None       # hip_optimizer only: 0-d int32 on the device
         # outfitx_amd.OutfitX: let the backward kernels add straight into the arena views (no per-tensor accumulate kernels);
         # valid because nothing here relies on autograd hooks (DDP would)
-        if hasattr(model, "_cp_train_forward"):
+        if hasattr(model, "sink_ready"):
             model.grad_sink = True
         # per-layer gradient slices for the overlapped reduction (None: the model has no encoder-layer structure -> one all-reduce)
         self.layer_slices = self.rest_slices = None
@@ -231,6 +230,19 @@ class FlatGradTrainer:
     def _world(self) -> int:
         return dist.get_world_size(self.group) if dist.is_available() and dist.is_initialized() else 1
 
+    def _inputs(self, batch: dict) -> dict:
+        """batch['input_dict'] with every tensor on the arena's device (the task class passes through)."""
+        dev = self.grads.flat.device
+        return {k: (v if k == "task" else v.to(dev, non_blocking=True)) for k, v in batch["input_dict"].items()}
+
+    def _rank_mean(self, total: torch.Tensor, n: int) -> float:
+        """Summed micro-batch loss / number of batches, averaged over the ranks."""
+        total = total / max(n, 1)
+        if self._world() > 1:
+            dist.all_reduce(total, op=dist.ReduceOp.SUM, group=self.group)
+            total = total / self._world()
+        return float(total)
+
     def _arm_overlap(self) -> bool:
         """Before the backward of an accumulation window's LAST micro-batch: arm the per-layer completion events (HIP model only)."""
         if not (self.overlap_reduce and self.layer_slices and self._world() > 1 and hasattr(self.model, "arm_bwd_layer_events")
@@ -238,7 +250,7 @@ class FlatGradTrainer:
             return False
         # the events mean "final in the arena" only on the gradient-sink path; any tensor whose .grad is not the arena view (detached,
         # non-contiguous, not fp32) sends the backward through autograd's accumulation, which runs AFTER the events: plain reduction then
-        if hasattr(self.model, "sink_ready") and not self.model.sink_ready(self._sink_skip):
+        if hasattr(self.model, "sink_ready") and not self.model.sink_ready(self.head):
             return False
         if self._layer_events is None:
             self._layer_events = [torch.cuda.Event() for _ in self.layer_slices]
@@ -327,10 +339,8 @@ class CPTrainer(FlatGradTrainer):
     def micro_step(self, batch: dict, step: int):
         """One micro-batch: forward, loss / accumulation_steps, backward; optimizer step on the accumulation boundary.
         Returns (detached loss, detached logits)."""
-        dev = self.grads.flat.device
-        inp = {k: (v if k == "task" else v.to(dev, non_blocking=True)) for k, v in batch["input_dict"].items()}
-        labels = batch["label"].to(dev, non_blocking=True)
-        y_hat = self.model(**inp).squeeze(dim=-1)
+        labels = batch["label"].to(self.grads.flat.device, non_blocking=True)
+        y_hat = self.model(**self._inputs(batch)).squeeze(dim=-1)
         loss = self.loss_fn(y_hat=y_hat, y_true=labels)
         self._backward_and_step(loss, step)
         return loss.detach(), y_hat.detach(), labels
@@ -356,7 +366,7 @@ class CIRTrainer(FlatGradTrainer):
     positive's category and its row inside that category's pool).  Negative sampling, the easy -> hard switch, checkpoints and logging
     stay with the caller."""
 
-    _sink_skip = (0, 2, 3)        # outfit_token and the CP head are not on the CIR path
+    head = "cir"
 
     def __init__(self, model: torch.nn.Module, steps_per_epoch: int, cfg: Optional[CIRTrainConfig] = None,
                  loss_fn: Optional[Callable] = None, params: Optional[Iterable[torch.nn.Parameter]] = None, group=None):
@@ -378,15 +388,17 @@ class CIRTrainer(FlatGradTrainer):
         off_ids = {id(t) for t in off}
         return [p for p in model.parameters() if p.requires_grad and id(p) not in off_ids]
 
+    def _loss(self, batch: dict, y_hat: torch.Tensor) -> torch.Tensor:
+        dev = self.grads.flat.device
+        return self.loss_fn(batch_y=batch["pos_item_embedding"].to(dev, non_blocking=True), batch_y_hat=y_hat,
+                            batch_negative_samples=batch["neg_items_embedding"].to(dev, non_blocking=True),
+                            batch_negative_mask=batch["neg_items_mask"].to(dev, non_blocking=True))
+
     def micro_step(self, batch: dict, step: int):
         """One micro-batch (:73-99): forward, loss / accumulation_steps, backward; optimizer step on the accumulation boundary.
         Returns (detached loss, detached y_hat)."""
-        dev = self.grads.flat.device
-        inp = {k: (v if k == "task" else v.to(dev, non_blocking=True)) for k, v in batch["input_dict"].items()}
-        y_hat = self.model(**inp)
-        loss = self.loss_fn(batch_y=batch["pos_item_embedding"].to(dev, non_blocking=True), batch_y_hat=y_hat,
-                            batch_negative_samples=batch["neg_items_embedding"].to(dev, non_blocking=True),
-                            batch_negative_mask=batch["neg_items_mask"].to(dev, non_blocking=True))
+        y_hat = self.model(**self._inputs(batch))
+        loss = self._loss(batch, y_hat)
         self._backward_and_step(loss, step)
         return loss.detach(), y_hat.detach()
 
@@ -399,11 +411,7 @@ class CIRTrainer(FlatGradTrainer):
         for step, batch in enumerate(batches):
             total += self.micro_step(batch, step)[0]
             n += 1
-        total = total / max(n, 1)
-        if self._world() > 1:
-            dist.all_reduce(total, op=dist.ReduceOp.SUM, group=self.group)
-            total = total / self._world()
-        return {"loss": float(total)}
+        return {"loss": self._rank_mean(total, n)}
 
     def valid_epoch(self, batches: Iterable[dict], pools, top_k_list: Sequence[int] = (1, 5, 10, 15, 30, 50), with_recall: bool = True,
                     topk_fn: Optional[Callable] = None) -> Dict[str, float]:
@@ -423,21 +431,14 @@ class CIRTrainer(FlatGradTrainer):
         try:
             with torch.no_grad():
                 for batch in batches:
-                    inp = {k: (v if k == "task" else v.to(dev, non_blocking=True)) for k, v in batch["input_dict"].items()}
-                    y_hat = self.model(**inp)
-                    total += self.loss_fn(batch_y=batch["pos_item_embedding"].to(dev, non_blocking=True), batch_y_hat=y_hat,
-                                          batch_negative_samples=batch["neg_items_embedding"].to(dev, non_blocking=True),
-                                          batch_negative_mask=batch["neg_items_mask"].to(dev, non_blocking=True)).detach()
+                    y_hat = self.model(**self._inputs(batch))
+                    total += self._loss(batch, y_hat).detach()
                     n += 1
                     if with_recall:
                         ys.append(y_hat.detach())
                         groups.append(torch.as_tensor(batch["pos_item_group"], device="cpu").to(torch.int64).reshape(-1))
                         rows.append(torch.as_tensor(batch["pos_item_row"], device="cpu").to(torch.int64).reshape(-1))
-                total = total / max(n, 1)
-                if self._world() > 1:
-                    dist.all_reduce(total, op=dist.ReduceOp.SUM, group=self.group)
-                    total = total / self._world()
-                metrics = {"loss": float(total)}
+                metrics = {"loss": self._rank_mean(total, n)}
                 if with_recall:
                     from .parallel import grouped_recall
                     P, offsets = pools

@@ -384,7 +384,7 @@ def test_cir_trainer_equals_the_reference_loop_written_out_by_hand(prec, ltol):
     on_path = [p for p in CIRTrainer._default_params(m) if any(p is q for q in trainable(m).values())]
     assert len(on_path) == len(trainable(m)) - 3                       # outfit_token, cp_ffn.1.weight, cp_ffn.1.bias are left out
     tr = CIRTrainer(m, steps_per_epoch=4, cfg=CIRTrainConfig(learning_rate=LR, accumulation_steps=ACC, n_epochs=1), params=on_path)
-    assert tr.cfg.margin == 2.0 and tr.layer_slices is not None and len(tr.layer_slices) == 6 and m.sink_ready((0, 2, 3))
+    assert tr.cfg.margin == 2.0 and tr.layer_slices is not None and len(tr.layer_slices) == 6 and m.sink_ready("cir")
     losses = [float(tr.micro_step(b, i)[0]) for i, b in enumerate(batches)]
     got = {k: v.detach().clone() for k, v in trainable(m).items()}
     # ---- the reference's loop by hand

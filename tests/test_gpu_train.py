@@ -326,9 +326,11 @@ def test_dropout_training_step_matches_torch_autograd_with_the_same_masks(n, Lp,
     assert set(ours) == {k for k, v in P.items() if v.grad is not None}
 
 
-def test_indexed_training_step_equals_the_padded_one():
-    """N3 x N1: a training step fed by (item_index, cu_seqlens) into the resident table == the padded-tensor step."""
-    from src.models.datatypes import OutfitCompatibilityPredictionTask as CP
+@pytest.mark.parametrize("head", ["cp", "cir"])
+def test_indexed_training_step_equals_the_padded_one(head):
+    """N3 x N1: a training step fed by (item_index, cu_seqlens) into the resident table == the padded-tensor step, output and every
+    gradient bit for bit, through the CP head and through the CIR head (which also takes a target_item_text_embedding)."""
+    from src.models.datatypes import (OutfitCompatibilityPredictionTask as CP, OutfitComplementaryItemRetrievalTask as CIR)
     n_items = [5, 16, 1, 8, 3, 0]
     g = np.random.default_rng(8)
     table = synth.item_embeddings(8, "table", 300)
@@ -339,13 +341,18 @@ def test_indexed_training_step_equals_the_padded_one():
         emb[b, :len(r)] = table[r]; mask[b, :len(r)] = False
     m = make_model("bf16")
     m.set_embedding_table(torch.from_numpy(table))
-    up = torch.linspace(-1.0, 2.0, len(n_items)).cuda()
-    (m(task=CP, outfit_embedding=cu(emb), outfit_mask=cu(mask)).squeeze(-1) * up).sum().backward()
+    kw = {"task": CP} if head == "cp" else {"task": CIR, "target_item_text_embedding": cu(synth.unit_rows(8, "target_text", len(n_items), 512))}
+    up = torch.linspace(-1.0, 2.0, len(n_items)).cuda()[:, None]
+    y_dense = m(outfit_embedding=cu(emb), outfit_mask=cu(mask), **kw)
+    (y_dense * up).sum().backward()
     dense = {k: v.grad.clone() for k, v in trainable(m).items() if v.grad is not None}
+    assert dense
     m.zero_grad(set_to_none=True)
-    y = m(task=CP, item_index=torch.from_numpy(np.concatenate(idx).astype(np.int32)), cu_seqlens=cu_items)
-    (y.squeeze(-1) * up).sum().backward()
+    y = m(item_index=torch.from_numpy(np.concatenate(idx).astype(np.int32)), cu_seqlens=cu_items, **kw)
+    (y * up).sum().backward()
+    assert torch.equal(y, y_dense)
     for k, v in trainable(m).items():
+        assert (v.grad is not None) == (k in dense), k
         if k in dense:
             assert torch.equal(v.grad, dense[k]), k
 

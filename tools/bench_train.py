@@ -226,7 +226,7 @@ def main():
 
     def fwd_only():
         eng = m._engine(a.precision)
-        eng.cp_train_fwd(emb, mask)
+        eng.train_fwd("cp", (emb, mask))
 
     what = "2..8 items (uniform)" if a.polyvore else f"{a.items} items"
     res = {"workload": f"CP trainer step, {a.batch} outfits x {what} (padded {a.pad}), precomputed embeddings",
