@@ -274,6 +274,21 @@ int ofx_focal_loss_ex(const float* logits, const float* labels, int B, float alp
 size_t ofx_set_rank_loss_ws_bytes(int B, int K, int D);
 int ofx_set_rank_loss(const float* y, const float* y_hat, const float* neg, const uint8_t* neg_mask, int B, int K, int D, float margin,
                       float upstream, float* loss, float* dy_hat, float* d_pos, float* d_neg, void* ws, size_t ws_bytes, ofx_stream stream);
+/* The same loss with the positives and the negatives named by row of a device-resident embedding table (the index form of a CIR batch:
+ * no [B, K, D] tensor exists anywhere):  exactly ofx_set_rank_loss with y[b] = table[pos_index[b]] and neg[b, k] = table[neg_index[b, k]] -
+ * the same kernel body reading its rows through the indices, the same summation order, hence the same bits as the dense call on the
+ * gathered rows, in *loss, dy_hat, d_pos and d_neg alike.
+ *   table [n_table, ld] fp32, ld >= D, ld % 4 == 0, 16-byte aligned (a row's first D floats are used); pos_index int32 [B]; neg_index int32
+ *   [B, K], contiguous (may be NULL when K = 0).  neg_index[b, k] < 0 means padded - it replaces the mask byte: the row is never loaded and
+ *   d_neg reads +inf there.
+ *   The index arrays live on the device, so the host cannot check their values: the kernel clamps pos_index into [0, n_table) and a
+ *   non-negative neg_index to <= n_table - 1.  A wrong index gives a wrong result, never an access outside the table.
+ * NULL or misaligned table / y_hat / dy_hat / ws, NULL pos_index, NULL neg_index with K > 0: OFX_EINVAL; the dense call's shape rules, ld,
+ * 1 <= n_table <= INT_MAX: OFX_ESHAPE; short workspace (ofx_set_rank_loss_ws_bytes(B, K, D), unchanged): OFX_EWORKSPACE - a rejected call
+ * launches nothing.  Two launches (the first counts neg_index >= 0), no floating-point atomics, bit-reproducible, same LDS residency rule. */
+int ofx_set_rank_loss_indexed(const float* table, int ld, long long n_table, const int* pos_index, const int* neg_index, const float* y_hat,
+                              int B, int K, int D, float margin, float upstream, float* loss, float* dy_hat, float* d_pos, float* d_neg,
+                              void* ws, size_t ws_bytes, ofx_stream stream);
 
 /* ------------------------------------------------------------------ optimizer step ---------- */
 /* The accumulation boundary of the trainers (compatibility_prediction_trainer.py:70-80 = complementary_item_retrieval_trainer.py:89-99):

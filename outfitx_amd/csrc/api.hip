@@ -156,6 +156,8 @@ int ofx_launch_focal_loss(const float* logits, const float* labels, int B, float
 size_t ofx_set_rank_loss_ws(int B, int K);
 int ofx_launch_set_rank_loss(const float* y, const float* y_hat, const float* neg, const uint8_t* mask, int B, int K, int D, float margin, float upstream,
                              float* loss, float* dy_hat, float* d_pos, float* d_neg, void* ws, hipStream_t s);
+int ofx_launch_set_rank_loss_indexed(const float* table, int ld, int n_table, const int* pos_index, const int* neg_index, const float* y_hat, int B, int K,
+                                     int D, float margin, float upstream, float* loss, float* dy_hat, float* d_pos, float* d_neg, void* ws, hipStream_t s);
 size_t ofx_adamw_step_ws(long long n_arena);
 int ofx_launch_adamw_step(const ofx_opt_segment* segments, int n_segments, float* grad, float* exp_avg, float* exp_avg_sq, long long n_arena,
                           float* step, double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm, double grad_scale,
@@ -1327,6 +1329,23 @@ extern "C" int ofx_set_rank_loss(const float* y, const float* y_hat, const float
                 "set_rank_loss: y, y_hat, neg, dy_hat and ws must be 16-byte aligned");
     OFX_REQUIRE(ws_bytes >= ofx_set_rank_loss_ws(B, K), OFX_EWORKSPACE, "set_rank_loss: workspace %zu < %zu bytes", ws_bytes, ofx_set_rank_loss_ws(B, K));
     return ofx_launch_set_rank_loss(y, y_hat, neg, neg_mask, B, K, D, margin, upstream, loss, dy_hat, d_pos, d_neg, ws, (hipStream_t)stream);
+}
+
+extern "C" int ofx_set_rank_loss_indexed(const float* table, int ld, long long n_table, const int* pos_index, const int* neg_index, const float* y_hat,
+                                         int B, int K, int D, float margin, float upstream, float* loss, float* dy_hat, float* d_pos, float* d_neg,
+                                         void* ws, size_t ws_bytes, ofx_stream stream) {
+    OFX_REQUIRE(rank_loss_shape_ok(B, K, D), OFX_ESHAPE,
+                "set_rank_loss_indexed: B = %d, K = %d, D = %d; needs B >= 1, K >= 0, D %% 4 == 0, 4 <= D <= 4096", B, K, D);
+    OFX_REQUIRE(ld >= D && ld % 4 == 0 && n_table >= 1 && n_table <= INT_MAX, OFX_ESHAPE,
+                "set_rank_loss_indexed: ld = %d, n_table = %lld; needs ld >= D = %d, ld %% 4 == 0, 1 <= n_table <= INT_MAX", ld, n_table, D);
+    OFX_REQUIRE(table && pos_index && y_hat && loss && ws && (neg_index || K == 0), OFX_EINVAL, "set_rank_loss_indexed: NULL argument");
+    OFX_REQUIRE((((uintptr_t)table | (uintptr_t)y_hat | (uintptr_t)dy_hat | (uintptr_t)ws) & 15) == 0 &&
+                    (((uintptr_t)pos_index | (uintptr_t)neg_index) & 3) == 0,
+                OFX_EINVAL, "set_rank_loss_indexed: table, y_hat, dy_hat and ws must be 16-byte aligned, the index arrays 4-byte aligned");
+    OFX_REQUIRE(ws_bytes >= ofx_set_rank_loss_ws(B, K), OFX_EWORKSPACE, "set_rank_loss_indexed: workspace %zu < %zu bytes", ws_bytes,
+                ofx_set_rank_loss_ws(B, K));
+    return ofx_launch_set_rank_loss_indexed(table, ld, (int)n_table, pos_index, neg_index, y_hat, B, K, D, margin, upstream, loss, dy_hat, d_pos, d_neg, ws,
+                                            (hipStream_t)stream);
 }
 
 static bool adamw_shape_ok(long long n_arena) { return n_arena > 0 && n_arena % 64 == 0; }

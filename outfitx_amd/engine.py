@@ -513,6 +513,41 @@ def set_rank_loss(y: torch.Tensor, y_hat: torch.Tensor, neg: torch.Tensor, neg_m
     return loss, dy
 
 
+def set_rank_loss_indexed(table: torch.Tensor, pos_index: torch.Tensor, neg_index: torch.Tensor, y_hat: torch.Tensor, margin: float,
+                          upstream: float = 1.0, need_grad: bool = True, n_table: Optional[int] = None):
+    """set_rank_loss with y[b] = table[pos_index[b]] and neg[b, k] = table[neg_index[b, k]] read straight from the table
+    (ofx_set_rank_loss_indexed): no [B, D] / [B, K, D] tensor is gathered.  table [n, ld] fp32 with unit column stride (a column slice of
+    a wider table is taken as it is, ld = its row stride; ld % 4 == 0); pos_index [B], neg_index [B, K] integer, a negative neg_index =
+    padded; y_hat [B, D], D <= ld: a row's first D floats are used.  n_table (default: all rows) is the row count the kernel clamps the
+    indices to.  Same bits as set_rank_loss on the gathered rows.  -> (0-d loss, dy_hat [B, D] or None)."""
+    lib = L.load()
+    dev = y_hat.device
+    if dev.type != "cuda":
+        raise L.OfxError("set_rank_loss_indexed needs HIP tensors; losses.SetWiseRankingLoss.forward_indexed gathers on the CPU")
+    if (table.dim() != 2 or y_hat.dim() != 2 or pos_index.dim() != 1 or neg_index.dim() != 2 or pos_index.shape[0] != y_hat.shape[0]
+            or neg_index.shape[0] != y_hat.shape[0] or table.shape[1] < y_hat.shape[1]):
+        raise ValueError(f"set_rank_loss_indexed: table {tuple(table.shape)}, pos_index {tuple(pos_index.shape)}, neg_index "
+                         f"{tuple(neg_index.shape)}, y_hat {tuple(y_hat.shape)} are not [n,>=D], [B], [B,K], [B,D]")
+    B, D = y_hat.shape
+    K = neg_index.shape[1]
+    tb = table.detach()
+    if tb.device != dev or tb.dtype != torch.float32 or tb.stride(1) != 1 or tb.stride(0) < tb.shape[1] or tb.stride(0) % 4:
+        tb = _f32c(tb, dev)                            # not the layout the kernel reads in place: a private copy
+    ld = tb.stride(0)
+    hc = _f32c(y_hat.detach(), dev)
+    pi = pos_index.to(device=dev, dtype=torch.int32).contiguous()
+    ni = neg_index.to(device=dev, dtype=torch.int32).contiguous()
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    dy = torch.empty_like(hc) if need_grad else None
+    n_ws = lib.ofx_set_rank_loss_ws_bytes(B, K, D)
+    ws = torch.empty(max(n_ws, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.ofx_set_rank_loss_indexed(_ptr(tb), ld, tb.shape[0] if n_table is None else int(n_table), _ptr(pi), _ptr(ni) if K else None,
+                                              _ptr(hc), B, K, D, float(margin), float(upstream), _ptr(loss), _ptr(dy), None, None, _ptr(ws),
+                                              ws.numel(), _stream(dev)), "ofx_set_rank_loss_indexed")
+    return loss, dy
+
+
 ADAMW_WG_FLOATS = 4096      # arena floats one workgroup of ofx_adamw_step covers per stride step (optim.hip OPT_WG_FLOATS); grid = min(ceil(n / this), 2048)
 
 

@@ -6,13 +6,14 @@ No CPU path: HIP tensors only.
 
 SetWiseRankingLoss — drop-in for `src.losses.SetWiseRankingLoss` (src/losses/set_wise_ranking_loss.py:5-39), the CIR trainer's loss:
 on HIP tensors the value and d loss / d y_hat come from one pass over the negatives (ofx_set_rank_loss); everywhere else (CPU
-tensors, other dtypes, gradients wanted into the positives or the negatives) it is the torch expression."""
+tensors, other dtypes, gradients wanted into the positives or the negatives) it is the torch expression.  `forward_indexed` is the same loss
+with the positives and the negatives named by row of a device-resident embedding table (ofx_set_rank_loss_indexed)."""
 from __future__ import annotations
 
 import torch
 from torch import nn
 
-from .engine import focal_loss, set_rank_loss
+from .engine import focal_loss, set_rank_loss, set_rank_loss_indexed
 
 
 class _FocalFn(torch.autograd.Function):
@@ -45,6 +46,19 @@ class _SetRankFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y_hat, y, neg, neg_mask, margin):
         loss, dy = set_rank_loss(y, y_hat, neg, neg_mask, margin, 1.0, need_grad=y_hat.requires_grad)
+        ctx.save_for_backward(dy)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dy,) = ctx.saved_tensors
+        return dy * g, None, None, None, None
+
+
+class _SetRankIndexedFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y_hat, table, pos_index, neg_index, margin):
+        loss, dy = set_rank_loss_indexed(table, pos_index, neg_index, y_hat, margin, 1.0, need_grad=y_hat.requires_grad)
         ctx.save_for_backward(dy)
         return loss
 
@@ -91,3 +105,21 @@ class SetWiseRankingLoss(nn.Module):
         hinge_all = torch.relu(d_pos[:, None] - d_neg + self.margin) * valid
         hardest = d_neg.masked_fill(batch_negative_mask, float("inf")).amin(dim=1)
         return hinge_all.sum() / n_valid + torch.relu(d_pos - hardest + self.margin).mean()
+
+    def forward_indexed(self, batch_y_hat, table, pos_index, neg_index):
+        """forward(table[pos_index], batch_y_hat, table[neg_index], neg_index < 0) without the gathered tensors: table [n, >= D] holds
+        the item embeddings (OutfitX.embedding_table), pos_index [B] and neg_index [B, K] name rows of it, a negative neg_index is a padded
+        slot (processor.OutfitXIndexedProcessor's CIR collate).  HIP tensors, fp32 y_hat and table, int32 indices: ONE fused call that
+        reads the rows straight from the table - same bits as forward() on the gathered rows.  Anything else (CPU, other dtypes): the
+        rows are gathered and forward() runs on them."""
+        ts = (batch_y_hat, table, pos_index, neg_index)
+        if (all(isinstance(t, torch.Tensor) and t.device.type == "cuda" for t in ts) and batch_y_hat.dtype == torch.float32
+                and table.dtype == torch.float32 and pos_index.dtype == torch.int32 and neg_index.dtype == torch.int32
+                and not table.requires_grad and batch_y_hat.dim() == 2 and table.dim() == 2 and table.stride(1) == 1
+                and table.stride(0) % 4 == 0 and table.shape[0] >= 1
+                and pos_index.shape == batch_y_hat.shape[:1] and neg_index.dim() == 2 and neg_index.shape[0] == batch_y_hat.shape[0]
+                and batch_y_hat.shape[0] >= 1 and batch_y_hat.shape[1] % 4 == 0 and 4 <= batch_y_hat.shape[1] <= min(4096, table.shape[1])):
+            return _SetRankIndexedFn.apply(batch_y_hat, table, pos_index, neg_index, float(self.margin))
+        D = batch_y_hat.shape[-1]
+        rows = table[:, :D]
+        return self.forward(rows[pos_index.long()], batch_y_hat, rows[neg_index.clamp(min=0).long()], neg_index < 0)

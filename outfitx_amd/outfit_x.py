@@ -256,14 +256,19 @@ class OutfitX(nn.Module):
     def _grad_mode(self) -> bool:
         return self.training and torch.is_grad_enabled()
 
+    def _table(self, embedding_table=None) -> torch.Tensor:
+        """The embedding table an indexed argument refers to: the call's own, else the one set_embedding_table() keeps."""
+        table = embedding_table if embedding_table is not None else getattr(self, "embedding_table", None)
+        if table is None:
+            raise ValueError("indexed input needs an embedding table: pass embedding_table= or call set_embedding_table()")
+        return table
+
     def _set_input(self, outfit_embedding, outfit_mask, item_index=None, cu_seqlens=None, embedding_table=None, max_len=None):
         """A forward's set arguments -> the `setin` tuple of Engine.stage_set: (outfit_embedding, outfit_mask), or - when item_index is
         given - (table, item_index, cu_seqlens, max_len); max_len defaults to the longest outfit the kernels of this mode take."""
         if item_index is None:
             return outfit_embedding, outfit_mask
-        table = embedding_table if embedding_table is not None else getattr(self, "embedding_table", None)
-        if table is None:
-            raise ValueError("indexed input needs an embedding table: pass embedding_table= or call set_embedding_table()")
+        table = self._table(embedding_table)
         if max_len is None:
             max_len = min(self.cfg.max_length, 31 if self._grad_mode() else 63)
         return table, item_index, cu_seqlens, int(max_len)
@@ -333,8 +338,16 @@ class OutfitX(nn.Module):
     def _cir_forward(self, outfit_embedding: Optional[torch.Tensor] = None, outfit_mask: Optional[torch.Tensor] = None,
                      target_item_text_embedding: Optional[torch.Tensor] = None, *, item_index: Optional[torch.Tensor] = None,
                      cu_seqlens: Optional[torch.Tensor] = None, embedding_table: Optional[torch.Tensor] = None,
-                     max_len: Optional[int] = None) -> torch.Tensor:
-        """outfit_x.py:147-172 -> target-item embedding [B, d_embed] (indexed form as in _cp_forward)."""
+                     max_len: Optional[int] = None, target_item_index: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """outfit_x.py:147-172 -> target-item embedding [B, d_embed] (indexed form as in _cp_forward).  target_item_index (int [B]) names
+        the targets by table row instead of target_item_text_embedding: a row's second half is the item's text embedding
+        (polyvore_item_dataset.py:75), gathered on the device; it goes with the dense or the indexed set alike."""
+        if target_item_index is not None:
+            if target_item_text_embedding is not None:
+                raise ValueError("pass target_item_text_embedding or target_item_index, not both")
+            table = self._table(embedding_table)
+            half = table.shape[1] // 2
+            target_item_text_embedding = table.detach()[:, half:].index_select(0, target_item_index.to(table.device).long())
         setin = self._set_input(outfit_embedding, outfit_mask, item_index, cu_seqlens, embedding_table, max_len)
         if self._grad_mode():
             return self._train_forward("cir", setin, target_item_text_embedding)

@@ -114,15 +114,41 @@ class OutfitXIndexedProcessor:
     to cfg.max_length items exactly like `_get_max_length` does with truncation=True; the encoder result is identical
     to the padded form (padding never reaches the arithmetic: pad-free sets).  Picklable, CPU-only.
 
+    CIR (`run_mode` 'train' | 'valid' | 'test', required for this task and ignored for CP / FITB): a sample is
+    `(query, negative_item_ids)` - the negatives are item IDS where the reference dataset's `__getitem__` returns their embeddings
+    (a dataset that samples negatives has the ids in hand before it looks the embeddings up).  Everything the batch names is a table
+    row: `input_dict = {task, item_index, cu_seqlens, target_item_index}` (the target's text embedding is the second half of its row,
+    polyvore_item_dataset.py:75; `OutfitX` gathers it on the device), plus `pos_item_index` int32 [B] and `neg_items_index` int32 [B, K]
+    for 'train' / 'valid', plus `pos_item_id` for 'valid' / 'test'.  K and the padding are those of
+    `OutfitXComplementaryItemRetrievalTaskProcessor` on the same samples (`_get_max_length`, truncation included); a padded slot holds
+    -1 where that processor's `neg_items_mask` is True.  The trainer's loss reads the rows from the table
+    (`SetWiseRankingLoss.forward_indexed`): a batch is a few hundred KB of int32 instead of hundreds of MB of fp32.
+
     id_to_row: item_id -> row of the table (embedding_store.EmbeddingTable.index)."""
 
-    def __init__(self, task: Type, cfg: Optional[OutfitXConfig] = None, id_to_row=None):
+    def __init__(self, task: Type, cfg: Optional[OutfitXConfig] = None, id_to_row=None,
+                 run_mode: Optional[Literal["train", "valid", "test"]] = None):
         self.task, self.cfg = task, cfg if cfg is not None else OutfitXConfig()
         self.id_to_row = id_to_row
+        if task is OutfitComplementaryItemRetrievalTask and run_mode not in ("train", "valid", "test"):
+            raise ValueError(f"the indexed CIR collate needs run_mode 'train' | 'valid' | 'test', got {run_mode!r}")
+        self.run_mode = run_mode
+
+    def _row(self, item_id) -> int:
+        return int(item_id) if self.id_to_row is None else int(self.id_to_row[item_id])
 
     def _rows(self, items) -> List[int]:
         ids = [it.item_id for it in items][: self.cfg.max_length]
-        return [int(i) for i in ids] if self.id_to_row is None else [int(self.id_to_row[i]) for i in ids]
+        return [self._row(i) for i in ids]
+
+    def _neg_index(self, negs) -> torch.Tensor:
+        """Ragged lists of negative item ids -> int32 [B, K] rows, -1 on the padded slots; K by OutfitXBaseProcessor._get_max_length."""
+        K = OutfitXBaseProcessor._get_max_length(self, negs)
+        out = np.full((len(negs), K), -1, np.int32)
+        for i, ids in enumerate(negs):
+            n = min(len(ids), K)
+            out[i, :n] = [self._row(j) for j in ids[:n]]
+        return torch.from_numpy(out)
 
     def _index(self, outfits):
         rows = [self._rows(o) for o in outfits]
@@ -145,6 +171,18 @@ class OutfitXIndexedProcessor:
                                    "target_item_text_embedding": txt},
                     "candidate_item_embedding": torch.stack([torch.as_tensor(c) for c in cands]),
                     "answer_index": torch.tensor(answers, dtype=torch.long)}
+        if self.task is OutfitComplementaryItemRetrievalTask:
+            queries, negs = zip(*batch)
+            idx, cu = self._index([q.outfit for q in queries])
+            target = torch.from_numpy(np.fromiter((self._row(q.target_item.item_id) for q in queries), np.int32, count=len(queries)))
+            out = {"input_dict": {"task": OutfitComplementaryItemRetrievalTask, "item_index": idx, "cu_seqlens": cu,
+                                  "target_item_index": target}}
+            if self.run_mode != "train":
+                out["pos_item_id"] = [q.target_item.item_id for q in queries]
+            if self.run_mode != "test":
+                out["pos_item_index"] = target.clone()
+                out["neg_items_index"] = self._neg_index([list(n) for n in negs])
+            return out
         raise ValueError(f"no indexed collate for task {self.task!r}")
 
 

@@ -364,17 +364,28 @@ class CIRTrainer(FlatGradTrainer):
     Replaces ComplementaryItemRetrievalTrainer.train_epoch (:66-116) and, as `valid_epoch`, its validation loop with the recall@k inside
     the target's category pool (:122-249; validation batches additionally carry 'pos_item_group' [B] and 'pos_item_row' [B], the
     positive's category and its row inside that category's pool).  Negative sampling, the easy -> hard switch, checkpoints and logging
-    stay with the caller."""
+    stay with the caller.
+
+    Index-form batches (processor.OutfitXIndexedProcessor with the CIR task) carry table rows instead of embeddings:
+    {'input_dict': {'task', 'item_index', 'cu_seqlens', 'target_item_index'}, 'pos_item_index' [B] int32, 'neg_items_index' [B,K] int32,
+    negative = padded}.  A batch that has 'pos_item_index' takes the loss's `forward_indexed`, which reads the positives and the negatives
+    straight from the embedding table - `embedding_table=` here, else `model.embedding_table` (OutfitX.set_embedding_table) - so a step is
+    fed by a few hundred KB of int32 and no [B,K,D] tensor exists on host or device; same bits as the dense batch gathered from those rows.
+    Both forms can be mixed freely; the caller still samples the negatives, now handing over their ids."""
 
     head = "cir"
 
     def __init__(self, model: torch.nn.Module, steps_per_epoch: int, cfg: Optional[CIRTrainConfig] = None,
-                 loss_fn: Optional[Callable] = None, params: Optional[Iterable[torch.nn.Parameter]] = None, group=None):
+                 loss_fn: Optional[Callable] = None, params: Optional[Iterable[torch.nn.Parameter]] = None, group=None,
+                 embedding_table: Optional[torch.Tensor] = None):
         cfg = cfg or CIRTrainConfig()
+        self.embedding_table = None
         if loss_fn is None:
             from .losses import SetWiseRankingLoss
             loss_fn = SetWiseRankingLoss(margin=cfg.margin)
         super().__init__(model, steps_per_epoch, cfg, loss_fn, params, group)
+        if embedding_table is not None:
+            self.embedding_table = embedding_table.to(self.grads.flat.device)
 
     @staticmethod
     def _default_params(model: torch.nn.Module) -> List[torch.nn.Parameter]:
@@ -390,6 +401,12 @@ class CIRTrainer(FlatGradTrainer):
 
     def _loss(self, batch: dict, y_hat: torch.Tensor) -> torch.Tensor:
         dev = self.grads.flat.device
+        if "pos_item_index" in batch:
+            table = self.embedding_table if self.embedding_table is not None else getattr(self.model, "embedding_table", None)
+            if table is None:
+                raise ValueError("index-form CIR batches need an embedding table: pass embedding_table= or call model.set_embedding_table()")
+            return self.loss_fn.forward_indexed(batch_y_hat=y_hat, table=table, pos_index=batch["pos_item_index"].to(dev, non_blocking=True),
+                                                neg_index=batch["neg_items_index"].to(dev, non_blocking=True))
         return self.loss_fn(batch_y=batch["pos_item_embedding"].to(dev, non_blocking=True), batch_y_hat=y_hat,
                             batch_negative_samples=batch["neg_items_embedding"].to(dev, non_blocking=True),
                             batch_negative_mask=batch["neg_items_mask"].to(dev, non_blocking=True))

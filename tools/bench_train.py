@@ -17,6 +17,14 @@ timings.  `loss_kernel_GBps` is (B K D 4 + 3 B D 4) bytes - neg read once, y / y
 
     python tools/bench_train.py --task cir [--cir-batches 256,3072] [--negatives 10] [--loss-reps 30]
 
+It then times the INDEX form of the same batches (positives, negatives, target text and outfit rows named by row of a device-resident
+table of --table rows; outfitx_amd/csrc/rank_loss.hip TableRows) against the dense batches GATHERED FROM THE SAME ROWS, alternating in one
+process: the loss forward + backward through the class (`ms_loss_fwd_bwd_indexed_*` / `_dense_*`) and as raw engine calls
+(`ms_loss_call_indexed_*` / `_dense_*`, with the dense call's own spread over its timings: `_dense_min/_p25/_p75/_max`), the CIRTrainer
+step on device-resident batches (`ms_step_indexed_*` / `ms_step_dense_*`) and on batches handed over from pinned host memory on every step,
+as a DataLoader does (`ms_step_hostfed_*`), and the bytes per batch of both forms, computed here (`batch_bytes_*`).  Those keys are also
+written to --indexed-out (profiles/cir_indexed_bench.json).
+
 The CP run also times the accumulation BOUNDARY alone at the CP arena's real size (51.3 M floats) in its two forms, alternating in
 one process, medians over --boundary-reps device-event timings after a warm-up: `ms_boundary_torch` (vector_norm -> mul_ -> fused AdamW
 over the per-tensor views -> zero_, plus the div_ by the world size when there is more than one rank) and `ms_boundary_hip`
@@ -56,6 +64,11 @@ def timed(fn, steps, warmup):
 def median_ms(fns, reps, warmup, prep=None):
     """Device-event time of each callable, the callables ALTERNATING inside every repetition -> list of medians (ms).  prep (optional)
     runs before every timed call, outside the timed span."""
+    return [float(np.median(t)) for t in sample_ms(fns, reps, warmup, prep)]
+
+
+def sample_ms(fns, reps, warmup, prep=None):
+    """The timings behind median_ms: one list of `reps` device-event times (ms) per callable."""
     for _ in range(warmup):
         for fn in fns:
             if prep:
@@ -71,7 +84,7 @@ def median_ms(fns, reps, warmup, prep=None):
             a.record(); fn(); b.record()
             b.synchronize()
             ts[i].append(a.elapsed_time(b))
-    return [float(np.median(t)) for t in ts]
+    return ts
 
 
 def boundary_bench(params, world, reps, res):
@@ -125,6 +138,73 @@ def eager_set_rank_loss(batch_y, batch_y_hat, batch_negative_samples, batch_nega
     return hinge_all.sum() / n_valid + torch.relu(d_pos - hardest + margin).mean()
 
 
+def cir_indexed_bench(a, m, params, B, K, res):
+    """Index-form batches against the dense batches gathered from the same table rows (module docstring)."""
+    from outfitx_amd.engine import set_rank_loss, set_rank_loss_indexed
+    from outfitx_amd.trainer import CIRTrainConfig, CIRTrainer
+    from src.losses import SetWiseRankingLoss
+    from src.models.datatypes import OutfitComplementaryItemRetrievalTask as CIR
+    D, L = 1024, a.pad
+    g = np.random.default_rng(99)
+    table = torch.from_numpy(synth.item_embeddings(99, "table", a.table) * 3.0)
+    n_items = np.full(B, a.items)
+    idx = torch.from_numpy(g.integers(0, a.table, int(n_items.sum())).astype(np.int32))
+    cu = torch.from_numpy(np.concatenate([[0], np.cumsum(n_items)]).astype(np.int32))
+    pos = torch.from_numpy(g.integers(0, a.table, B).astype(np.int32))
+    neg = g.integers(0, a.table, (B, K)).astype(np.int32)
+    neg[g.random((B, K)) < 0.1] = -1
+    neg = torch.from_numpy(neg)
+    emb = torch.zeros(B, L, D); mask = torch.ones(B, L, dtype=torch.bool)
+    emb[:, :a.items] = table[idx.long()].view(B, a.items, D); mask[:, :a.items] = False
+    host = {"indexed": {"input_dict": {"task": CIR, "item_index": idx, "cu_seqlens": cu, "target_item_index": pos.clone()},
+                        "pos_item_index": pos, "neg_items_index": neg},
+            "dense": {"input_dict": {"task": CIR, "outfit_embedding": emb, "outfit_mask": mask,
+                                     "target_item_text_embedding": table[pos.long(), D // 2:].contiguous()},
+                      "pos_item_embedding": table[pos.long()], "neg_items_embedding": table[neg.clamp(min=0).long()], "neg_items_mask": neg < 0}}
+    move = lambda b, f: {k: ({n: (v if n == "task" else f(v)) for n, v in t.items()} if k == "input_dict" else f(t)) for k, t in b.items()}
+    nbytes = lambda b: sum(v.numel() * v.element_size() for t in b.values() for v in (t.values() if isinstance(t, dict) else [t]) if isinstance(v, torch.Tensor))
+    for form in host:
+        res[f"batch_bytes_{form}_b{B}"] = int(nbytes(host[form]))
+    pinned = {f: move(b, lambda v: v.pin_memory()) for f, b in host.items()}
+    dev = {f: move(b, lambda v: v.cuda()) for f, b in host.items()}
+    m.set_embedding_table(table)
+    tab = m.embedding_table
+    # ---- the loss alone: class forward + backward, and the raw two-launch calls
+    y_hat0 = torch.from_numpy(synth.item_embeddings(99, "y_hat", B) * 3.0).cuda()
+    di, dd = dev["indexed"], dev["dense"]
+    fn = SetWiseRankingLoss(margin=2.0)
+
+    def loss_indexed():
+        yh = y_hat0.detach().requires_grad_(True)
+        fn.forward_indexed(yh, tab, di["pos_item_index"], di["neg_items_index"]).backward()
+        return yh.grad
+
+    def loss_dense():
+        yh = y_hat0.detach().requires_grad_(True)
+        fn(batch_y=dd["pos_item_embedding"], batch_y_hat=yh, batch_negative_samples=dd["neg_items_embedding"], batch_negative_mask=dd["neg_items_mask"]).backward()
+        return yh.grad
+
+    res[f"loss_grad_indexed_equals_dense_b{B}"] = bool(torch.equal(loss_indexed(), loss_dense()))
+    call_i = lambda: set_rank_loss_indexed(tab, di["pos_item_index"], di["neg_items_index"], y_hat0, 2.0)
+    call_d = lambda: set_rank_loss(dd["pos_item_embedding"], y_hat0, dd["neg_items_embedding"], dd["neg_items_mask"], 2.0)
+    ts = sample_ms([loss_indexed, loss_dense, call_i, call_d], a.loss_reps, 5)
+    for name, t in zip(("loss_fwd_bwd_indexed", "loss_fwd_bwd_dense", "loss_call_indexed", "loss_call_dense"), ts):
+        res[f"ms_{name}_b{B}"] = float(np.median(t))
+        for tag, q in (("min", 0), ("p25", 25), ("p75", 75), ("max", 100)):
+            res[f"ms_{name}_{tag}_b{B}"] = float(np.percentile(t, q))
+    res[f"loss_call_indexed_over_dense_b{B}"] = res[f"ms_loss_call_indexed_b{B}"] / res[f"ms_loss_call_dense_b{B}"]
+    # ---- the trainer step: device-resident batches, then batches that cross from pinned host memory on every step
+    for where, forms in (("", dev), ("hostfed_", pinned)):
+        for form in ("indexed", "dense"):
+            tr = CIRTrainer(m, steps_per_epoch=10 ** 9, cfg=CIRTrainConfig(accumulation_steps=1), params=params)
+            k = [0]
+            def step():
+                tr.micro_step(forms[form], k[0]); k[0] += 1
+            res[f"ms_step_{where}{form}_b{B}"] = timed(step, a.steps, a.warmup)
+            del tr
+    del m.embedding_table
+
+
 def cir_main(a, m, params):
     from outfitx_amd.engine import set_rank_loss
     from outfitx_amd.trainer import CIRTrainConfig, CIRTrainer
@@ -171,7 +251,16 @@ def cir_main(a, m, params):
         res[f"ms_loss_fwd_bwd_fused_b{B}"], res[f"ms_loss_fwd_bwd_eager_b{B}"], res[f"ms_loss_kernel_call_b{B}"] = t_f, t_e, t_k
         res[f"loss_eager_over_fused_b{B}"] = t_e / t_f
         res[f"loss_kernel_GBps_b{B}"] = nbytes / (t_k * 1e-3) / 1e9
+    ires = {"workload": f"index-form CIR batches against the dense batches gathered from the same rows of a {a.table}-row table, "
+                        f"{a.items} items per outfit (padded {a.pad}), {K} negatives per query, 10 % padded", "precision": a.precision,
+            "loss_reps": a.loss_reps, "steps": a.steps}
+    for B in [int(v) for v in a.cir_batches.split(",")]:
+        cir_indexed_bench(a, m, params, B, K, ires)
+    res.update({k: v for k, v in ires.items() if k not in res})
     print(json.dumps(res))
+    if a.indexed_out:
+        with open(a.indexed_out, "w") as f:
+            f.write(json.dumps(ires) + "\n")
 
 
 def main():
@@ -180,6 +269,8 @@ def main():
     ap.add_argument("--cir-batches", default="256,3072")
     ap.add_argument("--negatives", type=int, default=10)
     ap.add_argument("--loss-reps", type=int, default=30)
+    ap.add_argument("--table", type=int, default=100_000, help="rows of the device-resident embedding table (CIR task, index form)")
+    ap.add_argument("--indexed-out", default="", help="also write the index-form keys to this file (CIR task)")
     ap.add_argument("--boundary-reps", type=int, default=30)
     ap.add_argument("--boundary-out", default="", help="also write the JSON line to this file (CP task)")
     ap.add_argument("--batch", type=int, default=256)
