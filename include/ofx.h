@@ -409,6 +409,52 @@ int ofx_gemm_tn(const void* A, int lda, const void* B, int ldb, float* C, int ld
 size_t ofx_gemm_splitk_ws(int M, int N, int K);
 int ofx_gemm_splitk(const void* A, const void* W, void* C, const float* bias, const float* resid, int M, int N, int K,
                     int lda, int ldc, int ldr, int act, int out_kind, int op_dtype, void* slab, size_t slab_bytes, ofx_stream stream);
+/* The non-attention kernels of the training backward, one call each.  A dropout site is (dropout_p, seed, site) exactly as the step
+ * builds it: mask element (row, col) is what ofx_dropout_mask returns for the same arguments, dropout_p = 0 is no dropout.  NULL required
+ * pointers, misaligned pointers and dropout_p outside [0, 1) are OFX_EINVAL, an unsupported shape OFX_ESHAPE, a short workspace
+ * OFX_EWORKSPACE; a refused call launches nothing.  `m_dev`, where taken, is an optional device-side live row count: the kernels use
+ * min(*m_dev, M) rows and neither read nor write rows from there on, except as said under ofx_gemm_train.
+ *
+ *   ofx_gemm_train: ofx_gemm_splitk with the training epilogue: C = drop(act(A W^T + bias)) + resid, and for OFX_ACT_MISH_GRAD
+ *     C = drop(A W^T + bias) * mish'(resid) (resid, required then, is the saved pre-activation).  aux_out: optional fp32 [M, N] copy of
+ *     A W^T + bias before activation and dropout (row stride N).  Mask element = (output row, output column).  Live rows are written in
+ *     full and nothing at or past row M is touched; rows [*m_dev, M) of C and aux_out are not written by any kernel of the dispatcher
+ *     (128- and 64-row tiles, 256x256, 256x128, ping-pong, split-K reduce: tiles past the live rows leave at once, the operand loads
+ *     clamp onto the last live row, the epilogues and the reduce stop at the live count), and those rows of A and resid are not read:
+ *     they may hold anything.  tests/test_gpu_bwd_ops.py holds every kernel to this.
+ *   ofx_gemm_tn_into: ofx_gemm_tn storing only C[:m_valid, :n_valid] (0 = all; n_valid a multiple of 4; ldc >= n_valid may be < N),
+ *     accumulate: C += the product instead of C = (one fp32 addition per element, after the split-K sum).  Nothing else of C is written.
+ *   ofx_transpose_cast: dst [C, ldd >= R] operand type = round-to-nearest-even cast of src [R, C] fp32 transposed; columns R .. ldd - 1 of
+ *     dst are not written.  row_dst: optional row-major copy [R, ld_row >= C] of the same cast, columns C .. ld_row - 1 not written.
+ *   ofx_layernorm_bwd: rows r < min(*m_dev, M) of fp32 [M, D] dy and x, stats [M, 2] = (mean, rstd) of x's rows, gamma [D]:
+ *         g = dy gamma, xh = (x - mean) rstd, dx[r] = rstd (g - mean(g) - xh mean(g xh)) + addend,
+ *     addend = add[r] (add_map NULL), add[add_map[r]] (add_map[r] >= 0) or nothing (add NULL or add_map[r] < 0).  dx fp32 [M, D];
+ *     dx_op [M, D] operand type = cast(dx . mask of the site) - dx itself stays undropped.  Column sums over the live rows, each optional:
+ *     dgamma = sum dy xh, dbeta = sum dy, dcols = sum dx . mask (the fp32 values before the cast); accumulate: += instead of =.
+ *     D in {512, 768, 1024}; ws: ofx_layernorm_bwd_ws(D) bytes (0 for another D).  Rows at or past the live count are not written.
+ *   ofx_colsum: out_k[c % seg] (+)= sum over r < min(*m_dev, M) of row_scale[r] * x[gather ? gather[r] : r][c], k = c / seg, for the
+ *     columns c < C with c % seg < valid (valid = 0: seg); NULL out_k: that segment is skipped.  x: fp32 (x_kind 0) or the operand
+ *     type (x_kind 1), row stride ld >= C.  C and ld multiples of 4, C <= 3 seg, M >= 1.  ws: ofx_colsum_ws(C) bytes.  A live count of 0
+ *     stores zeros (accumulate: leaves the outputs as they are).
+ *   ofx_head_bwd: block b writes row r = cu ? cu[b] : b of dX (fp32 [rows, D]) and dXb (operand type): CP mode (dlogits given, w [D]):
+ *     dX[r] = dlogits[b] * w * mask_head(b, c); CIR mode (dlogits NULL, w [B, D] ready row gradients, db must be NULL): dX[r] = w[b] *
+ *     mask_head(b, c) - w may alias dX when cu is NULL.  dXb[r] = cast(dX[r] * mask_below(r, c)).  db (CP mode, optional): db[0] (+)=
+ *     sum_b dlogits[b].  A negative site = no dropout there.  Other rows of dX and dXb are not written.  D a multiple of 4. */
+int ofx_gemm_train(const void* A, const void* W, void* C, const float* bias, const float* resid, float* aux_out, int M, const int* m_dev,
+                   int N, int K, int lda, int ldc, int ldr, int act, int out_kind, float dropout_p, unsigned seed, int site, int op_dtype,
+                   void* slab, size_t slab_bytes, ofx_stream stream);
+int ofx_gemm_tn_into(const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, int K, const int* k_dev,
+                     int m_valid, int n_valid, int accumulate, void* slab, size_t slab_bytes, int op_dtype, ofx_stream stream);
+int ofx_transpose_cast(const float* src, void* dst, int R, int C, int ldd, void* row_dst, int ld_row, int op_dtype, ofx_stream stream);
+size_t ofx_layernorm_bwd_ws(int D);
+int ofx_layernorm_bwd(const float* dy, const float* x, const float* stats, const float* gamma, const float* add, const int* add_map,
+                      float* dx, void* dx_op, float* dgamma, float* dbeta, float* dcols, int M, const int* m_dev, int D, float dropout_p,
+                      unsigned seed, int site, int accumulate, int op_dtype, void* ws, size_t ws_bytes, ofx_stream stream);
+size_t ofx_colsum_ws(int C);
+int ofx_colsum(const void* x, int x_kind, int ld, const int* gather, const float* row_scale, float* out0, float* out1, float* out2, int seg,
+               int C, int valid, int M, const int* m_dev, int accumulate, int op_dtype, void* ws, size_t ws_bytes, ofx_stream stream);
+int ofx_head_bwd(const float* dlogits, const float* w, const int* cu, float* dX, void* dXb, float* db, int B, int D, float dropout_p,
+                 unsigned seed, int head_site, int below_site, int accumulate, int op_dtype, ofx_stream stream);
 int ofx_layernorm(const float* x, const int* row_idx, const float* gamma, const float* beta, void* y, int rows,
                   int D, int ldy, int out_kind, int op_dtype, float eps, ofx_stream stream);
 int ofx_attention(const void* qkv, void* out, const int64_t* key_mask, int nseq, int seq_len, int n_head, int ld,

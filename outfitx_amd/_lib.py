@@ -182,6 +182,14 @@ SIGNATURES = {
     "ofx_gemm_tn": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _i, _vp]),
     "ofx_gemm_splitk_ws": (_sz, [_i, _i, _i]),
     "ofx_gemm_splitk": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "ofx_gemm_train": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, C.c_uint, _i, _i, _vp, _sz, _vp]),
+    "ofx_gemm_tn_into": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _sz, _i, _vp]),
+    "ofx_transpose_cast": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp]),
+    "ofx_layernorm_bwd_ws": (_sz, [_i]),
+    "ofx_layernorm_bwd": (_i, [_vp] * 11 + [_i, _vp, _i, _f, C.c_uint, _i, _i, _i, _vp, _sz, _vp]),
+    "ofx_colsum_ws": (_sz, [_i]),
+    "ofx_colsum": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _sz, _vp]),
+    "ofx_head_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, C.c_uint, _i, _i, _i, _i, _vp]),
     "ofx_layernorm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "ofx_attention": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "ofx_fused_qkv_attention": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),

@@ -1434,6 +1434,73 @@ extern "C" int ofx_gemm_tn(const void* A, int lda, const void* B, int ldb, float
                            void* slab, size_t slab_bytes, int op_dtype, ofx_stream stream) {
     return ofx_launch_gemm_tn(A, lda, B, ldb, C, ldc, M, N, K, k_dev, slab, slab_bytes, op_dtype, (hipStream_t)stream);
 }
+// the non-attention kernels of the training backward, one call each, dropout sites built as the step builds them
+static bool op_dtype_ok(int op_dtype) { return op_dtype == OFX_BF16 || op_dtype == OFX_F16; }
+static bool drop_p_ok(float p) { return p >= 0.f && p < 1.f; }
+static bool aligned_to(size_t mask, std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs) if ((uintptr_t)p & mask) return false;
+    return true;
+}
+extern "C" int ofx_gemm_train(const void* A, const void* W, void* C, const float* bias, const float* resid, float* aux_out, int M, const int* m_dev,
+                              int N, int K, int lda, int ldc, int ldr, int act, int out_kind, float dropout_p, unsigned seed, int site, int op_dtype,
+                              void* slab, size_t slab_bytes, ofx_stream stream) {
+    OFX_REQUIRE(A && W && C && drop_p_ok(dropout_p) && (act != OFX_ACT_MISH_GRAD || resid), OFX_EINVAL, "gemm_train: bad argument");
+    OFX_REQUIRE(aligned_to(15, {bias, resid, aux_out, slab}) && aligned_to(3, {m_dev}), OFX_EINVAL,
+                "gemm_train: bias, resid, aux_out and slab must be 16-byte aligned");
+    GemmArgs g = op_gemm(A, W, C, bias, resid, M, N, K, lda, ldc, ldr, act, out_kind); g.slab = slab; g.slab_bytes = slab_bytes;
+    g.aux_out = aux_out; g.m_dev = m_dev; g.drop = make_drop(dropout_p, seed, (unsigned)site);
+    return ofx_launch_gemm(g, op_dtype, (hipStream_t)stream);
+}
+extern "C" int ofx_gemm_tn_into(const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, int K, const int* k_dev,
+                                int m_valid, int n_valid, int accumulate, void* slab, size_t slab_bytes, int op_dtype, ofx_stream stream) {
+    OFX_REQUIRE(A && B && C && m_valid >= 0 && n_valid >= 0, OFX_EINVAL, "gemm_tn_into: bad argument");
+    OFX_REQUIRE(aligned_to(15, {slab}) && aligned_to(3, {k_dev}), OFX_EINVAL, "gemm_tn_into: slab must be 16-byte aligned");
+    return ofx_launch_gemm_tn(A, lda, B, ldb, C, ldc, M, N, K, k_dev, slab, slab_bytes, op_dtype, (hipStream_t)stream, m_valid, n_valid, accumulate ? 1 : 0);
+}
+extern "C" int ofx_transpose_cast(const float* src, void* dst, int R, int C, int ldd, void* row_dst, int ld_row, int op_dtype, ofx_stream stream) {
+    OFX_REQUIRE(src && dst && op_dtype_ok(op_dtype), OFX_EINVAL, "transpose_cast: bad argument");
+    OFX_REQUIRE(aligned_to(3, {src}) && aligned_to(1, {dst, row_dst}), OFX_EINVAL, "transpose_cast: misaligned pointer");
+    OFX_REQUIRE(R > 0 && C > 0, OFX_ESHAPE, "transpose_cast: R=%d C=%d", R, C);
+    return ofx_launch_transpose_cast(src, dst, R, C, ldd, op_dtype, (hipStream_t)stream, row_dst, ld_row);
+}
+static bool ln_bwd_d_ok(int D) { return D == 512 || D == 768 || D == 1024; }
+extern "C" size_t ofx_layernorm_bwd_ws(int D) { return ln_bwd_d_ok(D) ? ofx_ln_bwd_part_floats(D) * sizeof(float) : 0; }
+extern "C" int ofx_layernorm_bwd(const float* dy, const float* x, const float* stats, const float* gamma, const float* add, const int* add_map,
+                                 float* dx, void* dx_op, float* dgamma, float* dbeta, float* dcols, int M, const int* m_dev, int D, float dropout_p,
+                                 unsigned seed, int site, int accumulate, int op_dtype, void* ws, size_t ws_bytes, ofx_stream stream) {
+    OFX_REQUIRE(dy && x && stats && gamma && dx && dx_op && ws && (add || !add_map) && drop_p_ok(dropout_p) && op_dtype_ok(op_dtype), OFX_EINVAL,
+                "layernorm_bwd: bad argument");
+    OFX_REQUIRE(M > 0 && ln_bwd_d_ok(D), OFX_ESHAPE, "layernorm_bwd: M = %d, D = %d; needs M >= 1, D in {512, 768, 1024}", M, D);
+    OFX_REQUIRE(aligned_to(15, {dy, x, gamma, add, dx, ws}) && aligned_to(7, {dx_op}) && aligned_to(3, {stats, add_map, dgamma, dbeta, dcols, m_dev}), OFX_EINVAL,
+                "layernorm_bwd: dy, x, gamma, add, dx and ws must be 16-byte aligned, dx_op 8-byte aligned");
+    OFX_REQUIRE(ws_bytes >= ofx_layernorm_bwd_ws(D), OFX_EWORKSPACE, "layernorm_bwd: workspace %zu < %zu bytes", ws_bytes, ofx_layernorm_bwd_ws(D));
+    return ofx_launch_ln_bwd(dy, x, stats, gamma, add, add_map, dx, dx_op, dgamma, dbeta, dcols, (float*)ws, D, m_dev, M, op_dtype,
+                             make_drop(dropout_p, seed, (unsigned)site), (hipStream_t)stream, accumulate ? 1 : 0);
+}
+static bool colsum_c_ok(int C) { return C > 0 && C % 4 == 0; }
+extern "C" size_t ofx_colsum_ws(int C) { return colsum_c_ok(C) ? ofx_colsum_part_floats(C) * sizeof(float) : 0; }
+extern "C" int ofx_colsum(const void* x, int x_kind, int ld, const int* gather, const float* row_scale, float* out0, float* out1, float* out2, int seg,
+                          int C, int valid, int M, const int* m_dev, int accumulate, int op_dtype, void* ws, size_t ws_bytes, ofx_stream stream) {
+    OFX_REQUIRE(x && ws && (out0 || out1 || out2) && (x_kind == 0 || (x_kind == 1 && op_dtype_ok(op_dtype))), OFX_EINVAL, "colsum: bad argument");
+    OFX_REQUIRE(colsum_c_ok(C) && M > 0 && ld >= C && ld % 4 == 0 && seg > 0 && C <= 3 * (long long)seg && valid >= 0 && valid <= seg, OFX_ESHAPE,
+                "colsum: C = %d, ld = %d, seg = %d, valid = %d, M = %d; needs C %% 4 == 0, ld >= C, ld %% 4 == 0, C <= 3 seg, valid <= seg, M >= 1", C, ld,
+                seg, valid, M);
+    OFX_REQUIRE(aligned_to(x_kind == 0 ? 15 : 7, {x}) && aligned_to(15, {ws}) && aligned_to(3, {gather, row_scale, out0, out1, out2, m_dev}), OFX_EINVAL,
+                "colsum: x must be aligned to four of its elements, ws to 16 bytes");
+    OFX_REQUIRE(ws_bytes >= ofx_colsum_ws(C), OFX_EWORKSPACE, "colsum: workspace %zu < %zu bytes", ws_bytes, ofx_colsum_ws(C));
+    return ofx_launch_colsum(x, x_kind, ld, gather, row_scale, out0, out1, out2, seg, (float*)ws, C, m_dev, M, op_dtype, (hipStream_t)stream, valid,
+                             accumulate ? 1 : 0);
+}
+extern "C" int ofx_head_bwd(const float* dlogits, const float* w, const int* cu, float* dX, void* dXb, float* db, int B, int D, float dropout_p,
+                            unsigned seed, int head_site, int below_site, int accumulate, int op_dtype, ofx_stream stream) {
+    OFX_REQUIRE(w && dX && dXb && (dlogits || !db) && drop_p_ok(dropout_p) && op_dtype_ok(op_dtype), OFX_EINVAL, "head_bwd: bad argument");
+    OFX_REQUIRE(B > 0 && D > 0 && D % 4 == 0, OFX_ESHAPE, "head_bwd: B = %d, D = %d; needs B >= 1, D a positive multiple of 4", B, D);
+    OFX_REQUIRE(aligned_to(15, {w, dX}) && aligned_to(7, {dXb}) && aligned_to(3, {dlogits, cu, db}), OFX_EINVAL,
+                "head_bwd: w and dX must be 16-byte aligned, dXb 8-byte aligned");
+    const DropArgs none;
+    return ofx_launch_cp_head_bwd(dlogits, w, cu, dX, dXb, db, B, D, op_dtype, head_site < 0 ? none : make_drop(dropout_p, seed, (unsigned)head_site),
+                                  below_site < 0 ? none : make_drop(dropout_p, seed, (unsigned)below_site), (hipStream_t)stream, accumulate ? 1 : 0);
+}
 extern "C" int ofx_layernorm(const float* x, const int* row_idx, const float* gamma, const float* beta, void* y, int rows,
                              int D, int ldy, int out_kind, int op_dtype, float eps, ofx_stream stream) {
     LnArgs a{x, row_idx, gamma, beta, y, rows, D, ldy, out_kind, eps};
