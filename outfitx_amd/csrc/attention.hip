@@ -221,7 +221,6 @@ __global__ __launch_bounds__(64) void set_attention_kernel(SetK a) {
     }
     // operand-type outputs: the fp32 rows go through the (now free) q staging rows and leave as 16-byte stores - 8 lanes per 64-column
     // slice, 8 rows per instruction, one instruction per copy (hi | lo | hi) instead of one 2-byte store per lane, row and copy
-    typedef typename OpT<T>::v8 v8;
     for (int i = 0; i < nq; ++i) {
         const float* row = sc + i * (SMAX + 4);
         float acc = 0.f;
@@ -235,15 +234,7 @@ __global__ __launch_bounds__(64) void set_attention_kernel(SetK a) {
         const int i = i0 + r8;
         if (i < nq) {
             const f32x4 x0 = *(const f32x4*)(qs + i * STR + c8), x1 = *(const f32x4*)(qs + i * STR + c8 + 4);
-            v8 hi, lo;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                hi[e] = (T)x0[e]; hi[4 + e] = (T)x1[e];
-                lo[e] = (T)(x0[e] - (float)hi[e]); lo[4 + e] = (T)(x1[e] - (float)hi[4 + e]);
-            }
-            T* p = (T*)a.out + (size_t)(r0 + i) * a.ldo + h * 64 + c8;
-            *(v8*)p = hi;
-            if (a.out_kind == 2) { *(v8*)(p + D) = lo; *(v8*)(p + 2 * D) = hi; }
+            store8<T>(a.out, (size_t)(r0 + i) * a.ldo + h * 64 + c8, x0, x1, a.out_kind, D);
         }
     }
 }

@@ -3,8 +3,12 @@
 // gemm_x3.hip: three-product 256x128; gemm_tn.hip: weight-gradient TN kernel) and of fused_qkv_attn.hip, which borrows the tile
 // constants and the block remap: the kernel kinds, kernel arguments, the tile walk (gemm_walk.h), the two-wave-group main loop
 // (gemm_pingpong.h: slot protocol, BK = 32 lane constants, persistent walk, dual-weight step), the live-row clamp, the LDS-DMA
-// helpers and the fused epilogues.  Everything here has internal linkage (anonymous namespace / templates); the files are split
-// only so that they compile in parallel.
+// helpers and the fused epilogue.  There is ONE epilogue value chain (epi_value, epi_residual) and one rounding / [hi | lo | hi] store
+// (store4 / store8, ofx_common.h); the kernels reach it by several routes - epilogue2's fp32 and operand-type branches, epilogue_direct
+// (accumulator layout), splitk_reduce_kernel - which differ only in where the values come from and how they leave: loads and prefetch
+// depth, LDS staging and swizzle, 16- or 32-byte row segments, buffer stores.  The 128x128 / 64x128 kernel's `epilogue`, whose fold
+// role is a run-time choice, keeps the same chain written out (the reason stands above it).  Everything here has internal linkage
+// (anonymous namespace / templates); the files are split only so that they compile in parallel.
 #pragma once
 #include <type_traits>
 
@@ -86,7 +90,42 @@ __device__ __forceinline__ bool clamp_live_rows(const int* m_dev, int& M, int m0
     return false;
 }
 
-// One wave drains its 64x64 fp32 sub-tile from LDS as whole row segments: 16 lanes x 16 B per row.
+// THE epilogue arithmetic, written once; every route below (and the split-K second pass) feeds it values in registers and takes values
+// back.  What the routes own is where the values come from and how they leave: the loads and their prefetch depth, the LDS staging
+// and its swizzle, the store shapes.  In order:
+//   1. acc + bias, or as LayerNorm-fold consumer (fold) (acc - colsum mean) rstd + bias'
+//   2. the optional fp32 tape copy (KArgs::aux_out)
+//   3. the activation (OFX_ACT_MISH_GRAD: none here, see epi_residual)
+//   4. the hashed dropout multiplier
+// for the 4 consecutive columns gn .. gn + 3 of row gm.  act, fold and train (steps 2 and 4 present at all) are compile-time constants
+// at every call but the split-K pass's run-time act; a route without training features needs no gm / gn.
+__device__ __forceinline__ f32x4 epi_value(const KArgs& p, f32x4 v, int act, bool fold, float mu, float rs, f32x4 cs, f32x4 bias, bool train,
+                                           int gm = 0, int gn = 0) {
+    v = fold ? (v - cs * mu) * rs + bias : v + bias;
+    if (train && p.aux_out) *(f32x4*)(p.aux_out + (size_t)gm * p.N + gn) = v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = apply_act(v[e], act);
+    if (train && p.drop.thresh) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] *= drop_mul(p.drop, gm, gn + e);
+    }
+    return v;
+}
+//   5. + residual, or under OFX_ACT_MISH_GRAD x mish'(residual) (the residual operand then carries the forward pre-activation)
+__device__ __forceinline__ f32x4 epi_residual(f32x4 v, f32x4 r, int act) {
+    if (act != OFX_ACT_MISH_GRAD) return v + r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] *= act_mish_grad(r[e]);
+    return v;
+}
+//   6. the store: store4 / store8 (ofx_common.h), or a route's own fp32 / buffer store
+
+// One wave drains its 64x64 fp32 sub-tile from LDS as whole row segments: 16 lanes x 16 B per row.  The fold role is chosen at run
+// time here (consumer: p.row_stat; producer: p.xlo), and the training features are present whatever it is (ofx_launch_gemm excludes
+// the combination).  This route keeps the chain of epi_value / epi_residual WRITTEN OUT, same steps in the same order: with a run-time
+// fold role the helper's step 1 turns the branch around the statistics loads into selects over both forms (twice the v_cndmask, 11 %
+// more instructions in gemm_128x128_kernel), and the training step, whose GEMMs run this kernel, measured 0.9 % slower.  Change the two
+// together.
 template <typename T, int ACT>
 __device__ __forceinline__ void epilogue(const KArgs& p, OFX_LDS float* ep, int gm0, int gn0, int lane, int nrows = 64) {
     typedef typename OpT<T>::v4 v4;
@@ -106,11 +145,7 @@ __device__ __forceinline__ void epilogue(const KArgs& p, OFX_LDS float* ep, int 
             } else v += bias4;
             if (p.aux_out) *(f32x4*)(p.aux_out + (size_t)gm * p.N + gn) = v;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (ACT == OFX_ACT_QUICK_GELU) v[e] = act_quick_gelu(v[e]);
-                else if (ACT == OFX_ACT_GELU) v[e] = act_gelu(v[e]);
-                else if (ACT == OFX_ACT_MISH) v[e] = act_mish(v[e]);
-            }
+            for (int e = 0; e < 4; ++e) v[e] = apply_act(v[e], ACT);
             if (p.drop.thresh) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] *= drop_mul(p.drop, gm, gn + e);
@@ -128,27 +163,12 @@ __device__ __forceinline__ void epilogue(const KArgs& p, OFX_LDS float* ep, int 
                 const v4 h0 = *(const v4*)hp, l0 = *(const v4*)lp;
                 v4 hb, lb;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { v[e] += (float)h0[e] + (float)l0[e]; hb[e] = (T)v[e]; lb[e] = (T)(v[e] - (float)hb[e]); }
+                for (int e = 0; e < 4; ++e) { v[e] += (float)h0[e] + (float)l0[e]; hb[e] = (T)v[e]; lb[e] = lo_of<T>(v[e], hb[e]); }
                 *(v4*)hp = hb; *(v4*)lp = lb;
                 const float ssum = row16_sum_to_lane15((v[0] + v[1]) + (v[2] + v[3]));
                 const float ssq = row16_sum_to_lane15((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]));
                 if ((lane & 15) == 15) *(f32x2*)(p.stat_part + ((size_t)gm * (p.N >> 6) + (gn0 >> 6)) * 2) = f32x2{ssum, ssq};
-            } else if (p.out_kind == 0) {
-                *(f32x4*)(p.C + ((size_t)gm * p.ldc + gn) * 4) = v;
-            } else {
-                v4 hi;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) hi[e] = (T)v[e];
-                T* crow = (T*)p.C + (size_t)gm * p.ldc + gn;
-                *(v4*)crow = hi;
-                if (p.out_kind == 2) {
-                    v4 lo;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) lo[e] = (T)(v[e] - (float)hi[e]);
-                    *(v4*)(crow + p.N) = lo;
-                    *(v4*)(crow + 2 * p.N) = hi;
-                }
-            }
+            } else store4<T>(p.C, (size_t)gm * p.ldc + gn, v, p.out_kind, p.N);
         }
     }
 }
@@ -169,14 +189,6 @@ constexpr int EPI_CONST_BIAS = 128, EPI_CONST_CSUM = 256, EPI_CONST_BYTES_PER_WA
 // 16-B chunks), leaving as whole 128/256-byte row segments with 16-byte stores (the store tail is issue-bound:
 // guide T21).  fp32 output: 16 lanes x 4 columns per row, the fp32 residual of pass i+2 requested while pass i is
 // written out.  bf16/f16 output: 8 lanes x 8 columns per row -> one dwordx4 store per lane instead of two dwordx2.
-template <typename T, int ACT>
-__device__ __forceinline__ float act_apply(float v) {
-    if (ACT == OFX_ACT_QUICK_GELU) return act_quick_gelu(v);
-    if (ACT == OFX_ACT_GELU) return act_gelu(v);
-    if (ACT == OFX_ACT_MISH) return act_mish(v);
-    return v;
-}
-
 // FOLD (LayerNorm folding, compile-time so the common path keeps its registers): 0 none, 2 consumer (row statistics + column sums
 // applied to the accumulator), 3 producer whose residual stream is the operand-type pair (xb_out = hi, xlo = lo = x - hi), read and
 // rewritten in place with per-segment statistics - no fp32 copy of the stream.
@@ -229,21 +241,12 @@ __device__ __forceinline__ void epilogue2(const KArgs& p, OFX_LDS char* ep, f32x
                 const int gm = gm0 + i * 16 + row;
                 f32x4 v = *(OFX_LDS f32x4*)(ep + row * 256 + ((chunk ^ (row & 7)) << 4));
                 if (gm < p.M && gn < p.n_valid) {
-                    if (FOLD == 2) {
-                        const float mu = p.row_stat[2 * (size_t)gm * p.stat_ld], rs = p.row_stat[2 * (size_t)gm * p.stat_ld + 1];
-                        v = (v - *(const f32x4*)(p.col_sum + gn) * mu) * rs + bias4;
-                    } else v += bias4;
-                    if (FOLD == 0 && p.aux_out) *(f32x4*)(p.aux_out + (size_t)gm * p.N + gn) = v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = act_apply<T, ACT>(v[e]);
-                    if (FOLD == 0 && p.drop.thresh) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] *= drop_mul(p.drop, gm, gn + e);
-                    }
-                    if (ACT == OFX_ACT_MISH_GRAD) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] *= act_mish_grad((RAMP ? resr[RAMP ? i : 0][it] : res[i % (DEPTH + 1)][it])[e]);
-                    } else v += (RAMP ? resr[RAMP ? i : 0][it] : res[i % (DEPTH + 1)][it]);
+                    float mu = 0.f, rs = 1.f;
+                    f32x4 cs = {0.f, 0.f, 0.f, 0.f};
+                    if (FOLD == 2) { mu = p.row_stat[2 * (size_t)gm * p.stat_ld]; rs = p.row_stat[2 * (size_t)gm * p.stat_ld + 1]; cs = *(const f32x4*)(p.col_sum + gn); }
+                    v = epi_value(p, v, ACT, FOLD == 2, mu, rs, cs, bias4, FOLD == 0, gm, gn);
+                    // the prefetched register, zero without a residual, goes in unconditionally (-0.0 leaves as +0.0)
+                    v = epi_residual(v, RAMP ? resr[RAMP ? i : 0][it] : res[i % (DEPTH + 1)][it], ACT);
                     *(f32x4*)(p.C + ((size_t)gm * p.ldc + gn) * 4) = v;
                 }
             }
@@ -311,53 +314,30 @@ __device__ __forceinline__ void epilogue2(const KArgs& p, OFX_LDS char* ep, f32x
                 f32x4 v0 = *(OFX_LDS f32x4*)(ep + row * 256 + (((2 * c8) ^ (row & 7)) << 4));
                 f32x4 v1 = *(OFX_LDS f32x4*)(ep + row * 256 + (((2 * c8 + 1) ^ (row & 7)) << 4));
                 if (gm < p.M) {
+                    float mu = 0.f, rs = 1.f;
                     if (FOLD == 2) {
-                        float mu, rs;
                         if (st_lds) { const f32x2 ms = *(OFX_LDS f32x2*)(st + 2 * (i * 16 + row)); mu = ms[0]; rs = ms[1]; }
                         else { mu = p.row_stat[2 * (size_t)gm * p.stat_ld]; rs = p.row_stat[2 * (size_t)gm * p.stat_ld + 1]; }
-                        v0 = (v0 - cs0 * mu) * rs + b0; v1 = (v1 - cs1 * mu) * rs + b1;
-                    } else { v0 += b0; v1 += b1; }
-                    if (FOLD == 0 && p.aux_out) { *(f32x4*)(p.aux_out + (size_t)gm * p.N + gn) = v0; *(f32x4*)(p.aux_out + (size_t)gm * p.N + gn + 4) = v1; }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { v0[e] = act_apply<T, ACT>(v0[e]); v1[e] = act_apply<T, ACT>(v1[e]); }
-                    if (FOLD == 0 && p.drop.thresh) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) { v0[e] *= drop_mul(p.drop, gm, gn + e); v1[e] *= drop_mul(p.drop, gm, gn + 4 + e); }
                     }
+                    v0 = epi_value(p, v0, ACT, FOLD == 2, mu, rs, cs0, b0, FOLD == 0, gm, gn);
+                    v1 = epi_value(p, v1, ACT, FOLD == 2, mu, rs, cs1, b1, FOLD == 0, gm, gn + 4);
                     if (p.resid) {
                         const f32x4 r0 = *(const f32x4*)(p.resid + (size_t)gm * p.ldr + gn), r1 = *(const f32x4*)(p.resid + (size_t)gm * p.ldr + gn + 4);
-                        if (ACT == OFX_ACT_MISH_GRAD) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) { v0[e] *= act_mish_grad(r0[e]); v1[e] *= act_mish_grad(r1[e]); }
-                        } else { v0 += r0; v1 += r1; }
+                        v0 = epi_residual(v0, r0, ACT); v1 = epi_residual(v1, r1, ACT);
                     }
                     if (FOLD == 3) {
                         const v8 h = rh[FOLD == 3 ? i % (D3 + 1) : 0][it], l = rl[FOLD == 3 ? i % (D3 + 1) : 0][it];
 #pragma unroll
                         for (int e = 0; e < 4; ++e) { v0[e] += (float)h[e] + (float)l[e]; v1[e] += (float)h[4 + e] + (float)l[4 + e]; }
                     }
-                    v8 hi;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { hi[e] = (T)v0[e]; hi[4 + e] = (T)v1[e]; }
-                    T* crow = (T*)p.C + (size_t)gm * p.ldc + gn;
-                    *(v8*)crow = hi;
+                    // (this branch never sees out_kind 0 but as a producer, whose C is xb_out in the operand type, ldc == N)
+                    store8<T>(p.C, (size_t)gm * p.ldc + gn, v0, v1, FOLD == 3 ? 1 : p.out_kind, p.N, FOLD == 3 ? p.xlo : nullptr);
                     if (FOLD == 3) {
-                        v8 lo;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) { lo[e] = (T)(v0[e] - (float)hi[e]); lo[4 + e] = (T)(v1[e] - (float)hi[4 + e]); }
-                        *(v8*)((T*)p.xlo + (size_t)gm * p.N + gn) = lo;
                         // per-64-column (sum, sum of squares) of the fp32 values: the 8 lanes of this row
                         const float ssum = row8_sum(((v0[0] + v0[1]) + (v0[2] + v0[3])) + ((v1[0] + v1[1]) + (v1[2] + v1[3])));
                         const float ssq = row8_sum(((v0[0] * v0[0] + v0[1] * v0[1]) + (v0[2] * v0[2] + v0[3] * v0[3])) +
                                                    ((v1[0] * v1[0] + v1[1] * v1[1]) + (v1[2] * v1[2] + v1[3] * v1[3])));
                         if (c8 == ((2 * i + it) & 7)) { keep_s[FOLD == 3 ? (2 * i + it) >> 3 : 0] = ssum; keep_q[FOLD == 3 ? (2 * i + it) >> 3 : 0] = ssq; }
-                    }
-                    if (p.out_kind == 2) {
-                        v8 lo;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) { lo[e] = (T)(v0[e] - (float)hi[e]); lo[4 + e] = (T)(v1[e] - (float)hi[4 + e]); }
-                        *(v8*)(crow + p.N) = lo;
-                        *(v8*)(crow + 2 * p.N) = hi;
                     }
                 }
             }
@@ -410,11 +390,8 @@ __device__ __forceinline__ void epilogue_direct(const KArgs& p, f32x4 (&acc)[NP]
             if (FOLD == 2) { const f32x2 ms = *(OFX_LDS const f32x2*)(cst + 2 * (i * 16 + fr)); mu = ms[0]; rs = ms[1]; }
 #pragma unroll
             for (int jp = 0; jp < 2; ++jp) {
-                f32x4 va = acc[i][h * 4 + 2 * jp], vb = acc[i][h * 4 + 2 * jp + 1];
-                if (FOLD == 2) { va = (va - cs[2 * jp] * mu) * rs + bb[2 * jp]; vb = (vb - cs[2 * jp + 1] * mu) * rs + bb[2 * jp + 1]; }
-                else { va += bb[2 * jp]; vb += bb[2 * jp + 1]; }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { va[e] = act_apply<T, ACT>(va[e]); vb[e] = act_apply<T, ACT>(vb[e]); }
+                const f32x4 va = epi_value(p, acc[i][h * 4 + 2 * jp], ACT, FOLD == 2, mu, rs, cs[2 * jp], bb[2 * jp], false);
+                const f32x4 vb = epi_value(p, acc[i][h * 4 + 2 * jp + 1], ACT, FOLD == 2, mu, rs, cs[2 * jp + 1], bb[2 * jp + 1], false);
                 const unsigned a_lo = __builtin_bit_cast(unsigned, t2{(T)va[0], (T)va[1]}), a_hi = __builtin_bit_cast(unsigned, t2{(T)va[2], (T)va[3]});
                 const unsigned b_lo = __builtin_bit_cast(unsigned, t2{(T)vb[0], (T)vb[1]}), b_hi = __builtin_bit_cast(unsigned, t2{(T)vb[2], (T)vb[3]});
                 // first result = [A rows 0 | B rows 0 | A rows 2 | B rows 2] of the 16-lane rows, second = [A 1 | B 1 | A 3 | B 3]: a lane with fq even now holds A's
@@ -480,7 +457,6 @@ __device__ __forceinline__ void epilogue2_dispatch(const KArgs& p, OFX_LDS char*
 // Split-K second pass: out = epilogue( sum_s slab[s] ) in a fixed order (deterministic), 4 columns per thread.
 template <typename T>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(KArgs p) {
-    typedef typename OpT<T>::v4 v4;
     const int M = p.m_dev ? min(*p.m_dev, p.M) : p.M;
     const int n4 = p.N / 4;
     const size_t total = (size_t)M * n4, plane = (size_t)p.m_slab * p.N;
@@ -490,37 +466,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(KArgs p) {
         const float* sp = p.slab + (size_t)gm * p.N + gn;
         f32x4 v = *(const f32x4*)sp;
         for (int s = 1; s < p.splits; ++s) v += *(const f32x4*)(sp + s * plane);
-        if (p.bias) v += *(const f32x4*)(p.bias + gn);
-        if (p.aux_out) *(f32x4*)(p.aux_out + (size_t)gm * p.N + gn) = v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = apply_act(v[e], p.act);
-        if (p.drop.thresh) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] *= drop_mul(p.drop, gm, gn + e);
-        }
-        if (p.resid) {
-            const f32x4 rr = *(const f32x4*)(p.resid + (size_t)gm * p.ldr + gn);
-            if (p.act == OFX_ACT_MISH_GRAD) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] *= act_mish_grad(rr[e]);
-            } else v += rr;
-        }
-        if (p.out_kind == 0) {
-            *(f32x4*)(p.C + ((size_t)gm * p.ldc + gn) * 4) = v;
-        } else {
-            v4 hi;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) hi[e] = (T)v[e];
-            T* crow = (T*)p.C + (size_t)gm * p.ldc + gn;
-            *(v4*)crow = hi;
-            if (p.out_kind == 2) {
-                v4 lo;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) lo[e] = (T)(v[e] - (float)hi[e]);
-                *(v4*)(crow + p.N) = lo;
-                *(v4*)(crow + 2 * p.N) = hi;
-            }
-        }
+        f32x4 bias4 = {-0.f, -0.f, -0.f, -0.f};            // no bias: nothing is added (x + -0.0 is x, a -0.0 sum included)
+        if (p.bias) bias4 = *(const f32x4*)(p.bias + gn);
+        v = epi_value(p, v, p.act, false, 0.f, 1.f, bias4, bias4, true, gm, gn);
+        if (p.resid) v = epi_residual(v, *(const f32x4*)(p.resid + (size_t)gm * p.ldr + gn), p.act);
+        store4<T>(p.C, (size_t)gm * p.ldc + gn, v, p.out_kind, p.N);
     }
 }
 

@@ -7,27 +7,6 @@
 
 namespace {
 
-template <typename T>
-__device__ __forceinline__ void store4(void* y, size_t off, f32x4 v, int out_kind, int D) {
-    if (out_kind == 0) {
-        *(f32x4*)((float*)y + off) = v;
-    } else {
-        typedef typename OpT<T>::v4 v4;
-        v4 hi;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) hi[e] = (T)v[e];
-        T* p = (T*)y + off;
-        *(v4*)p = hi;
-        if (out_kind == 2) {
-            v4 lo;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) lo[e] = (T)(v[e] - (float)hi[e]);
-            *(v4*)(p + D) = lo;
-            *(v4*)(p + 2 * D) = hi;
-        }
-    }
-}
-
 // y[r] = LN(x[row_idx ? row_idx[r] : r]) * gamma + beta.  NCH = D/256 float4 chunks per lane.
 template <typename T, int NCH>
 __global__ __launch_bounds__(256) void layernorm_kernel(LnArgs a, const int* rows_dev) {
@@ -160,7 +139,7 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const float* src, T* dst
         typedef typename OpT<T>::v4 v4;
         v4 hi, lo;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { hi[e] = (T)v[e]; lo[e] = (T)(v[e] - (float)hi[e]); }
+        for (int e = 0; e < 4; ++e) { hi[e] = (T)v[e]; lo[e] = lo_of<T>(v[e], hi[e]); }
         T* p = dst + (size_t)r * ld + c;
         *(v4*)p = hi;
         if (mode == 1) { *(v4*)(p + K_dst) = lo; *(v4*)(p + 2 * K_dst) = hi; }

@@ -69,6 +69,45 @@ template <> struct OpT<f16_t> {
     }
 };
 
+// ---- the (hi, lo) split of an fp32 value: hi = (T)v, lo = the rounded remainder - written here and nowhere else
+template <typename T>
+__device__ __forceinline__ T lo_of(float v, T hi) { return (T)(v - (float)hi); }
+// ---- output stores: one lane's 4 NV consecutive fp32 values v[0 .. NV) to elements y[off ...].  out_kind 0: fp32; 1: rounded to the
+// operand type (hi); 2: [hi | lo | hi] at column blocks of width D (the A operand of a three-product GEMM).  ylo (out_kind 1): the
+// (hi, lo) pair form - lo goes to ylo[off ...] (the LayerNorm-fold residual stream, GemmArgs::xlo).  Every operand-type store is one
+// instruction of 8 NV bytes per lane.
+template <typename T, int NV>
+__device__ __forceinline__ void store_cols(void* y, size_t off, const f32x4 (&v)[NV], int out_kind, int D, void* ylo = nullptr) {
+    typedef T vt __attribute__((ext_vector_type(4 * NV)));
+    if (out_kind == 0) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) *(f32x4*)((float*)y + off + 4 * k) = v[k];
+        return;
+    }
+    vt hi;
+#pragma unroll
+    for (int e = 0; e < 4 * NV; ++e) hi[e] = (T)v[e >> 2][e & 3];
+    T* p = (T*)y + off;
+    *(vt*)p = hi;
+    if (out_kind == 2 || ylo) {
+        vt lo;
+#pragma unroll
+        for (int e = 0; e < 4 * NV; ++e) lo[e] = lo_of<T>(v[e >> 2][e & 3], hi[e]);
+        if (ylo) *(vt*)((T*)ylo + off) = lo;
+        else { *(vt*)(p + D) = lo; *(vt*)(p + 2 * D) = hi; }
+    }
+}
+template <typename T>
+__device__ __forceinline__ void store4(void* y, size_t off, f32x4 v, int out_kind, int D, void* ylo = nullptr) {
+    const f32x4 vs[1] = {v};
+    store_cols<T, 1>(y, off, vs, out_kind, D, ylo);
+}
+template <typename T>
+__device__ __forceinline__ void store8(void* y, size_t off, f32x4 v0, f32x4 v1, int out_kind, int D, void* ylo = nullptr) {
+    const f32x4 vs[2] = {v0, v1};
+    store_cols<T, 2>(y, off, vs, out_kind, D, ylo);
+}
+
 // ---- activations (fp32) ----
 // v_rcp_f32 (1 ulp) instead of an IEEE division: results feed a bf16/f16 operand or are compared at 1e-5
 __device__ __forceinline__ float act_quick_gelu(float u) { return u * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.4554669595930157f * u)); }   // exp(-1.702 u) = 2^(-1.702 log2(e) u): one multiply, one v_exp_f32
