@@ -290,6 +290,39 @@ int ofx_set_rank_loss_indexed(const float* table, int ld, long long n_table, con
                               int B, int K, int D, float margin, float upstream, float* loss, float* dy_hat, float* d_pos, float* d_neg,
                               void* ws, size_t ws_bytes, ofx_stream stream);
 
+/* ------------------------------------------------------------------ CIR training batches, built on the device --- */
+/* One index-form CIR training batch (what ofx_cir_train_fwd and ofx_set_rank_loss_indexed take) drawn where the embedding table lives:
+ * PolyvoreComplementaryItemRetrievalDataset.__getitem__ + __get_negative_sample (polyvore_complementary_item_retrieval_dataset.py:50-67,
+ * 94-109) and the processor's truncation for B queries at once - the same distributions, not Python's random stream.  Stateless (no handle).
+ * The training split and the negative pools, all DEVICE int32 arrays, uploaded once:
+ *   outfit_cu [n_outfits + 1], outfit_rows [n_outfit_rows]: outfit o = table rows outfit_rows[outfit_cu[o] .. outfit_cu[o + 1]), 2 .. 64 of them;
+ *   pos_cu [n_outfits + 1], pos_slots [n_pos_slots]: the positions inside outfit o that may become the positive (positive_idx_list);
+ *   pool_cu [n_pools + 1], pool_rows [n_pool_rows]: the table rows that share a sampling key (semantic_category 'easy', category_id 'hard' -
+ *     the easy -> hard switch is a second set of these four arrays), each pool in table order;
+ *   row_pool [n_table], row_slot [n_table]: a row's pool (negative = in none) and its position inside that pool;
+ *   outfit_ids [B]: the outfits of this batch (the same outfit may appear in several slots: every slot draws on its own).
+ * Per query b, o = outfit_ids[b], n items, P eligible positions; word(stream, i) = the 32-bit word of (seed, draw, stream, b, i) and
+ * below(u, n) = (u * n) >> 32 (ofx_draw_u32 and ofx_draw_below in outfitx_amd/csrc/ofx_common.h; the bias of below is under n / 2^32):
+ *   positive   p = pos_slots[pos_cu[o] + below(word(0, 0), P)];  target_item_index[b] = t = outfit_rows[outfit_cu[o] + p];
+ *   remainder  the other n - 1 items in file order j = 0 .. n - 2 get keys word(1, j); ordered by (key, j) ascending - a uniform shuffle -
+ *              the first min(n - 1, max_len) go to item_index[cu_seqlens[b] ...];  cu_seqlens [B + 1] = the running sum of those lengths;
+ *   negatives  pool g = row_pool[t] of m rows, the target at slot s_t = row_slot[t].  m - 1 >= K: Floyd's algorithm over [0, m - 1): for
+ *              s = 0 .. K - 1, j = m - 1 - K + s, v = below(word(2, s), j + 1), slot s takes v, or j when an earlier slot holds v - a uniform
+ *              K-subset from K words, no rejection loop; value v names pool slot v + (v >= s_t), i.e. never the target.  m - 1 < K: the other
+ *              m - 1 rows in pool order, then -1.  Rows of the query's own outfit are not excluded (the reference does not either).
+ * Outputs (DEVICE int32): item_index [B * max_len], compact - elements at or past cu_seqlens[B] are NOT written; cu_seqlens [B + 1];
+ * target_item_index [B]; neg_items_index [B, K], -1 = empty slot (NULL when K = 0).
+ * Two launches on `stream` (the scan of the lengths, then one wave per query), no workspace, allocation, copy or wait (capturable).  A pure
+ * function of its arguments: the same (seed, draw) repeats the batch to the bit; tests/cir_sampler_ref.py restates it in numpy.
+ * Checked: a NULL pointer, a pointer that is not 16-byte aligned, B < 1: OFX_EINVAL; K outside [0, 64], max_len outside [1, 31] (the training
+ * step's limit), n_outfits < 1, n_table < 1, another count negative, B * max(K, max_len) > INT_MAX: OFX_ESHAPE; a refused call launches
+ * nothing.  The host cannot see the arrays' contents: the kernels clamp every value they index with into its array (by the counts given
+ * here), so a wrong table gives wrong draws, never an access out of bounds. */
+int ofx_cir_sample_batch(const int* outfit_cu, const int* outfit_rows, int n_outfits, int n_outfit_rows, const int* pos_cu, const int* pos_slots,
+                         int n_pos_slots, const int* pool_cu, const int* pool_rows, int n_pools, int n_pool_rows, const int* row_pool,
+                         const int* row_slot, int n_table, const int* outfit_ids, int B, unsigned seed, unsigned draw, int K, int max_len,
+                         int* item_index, int* cu_seqlens, int* target_item_index, int* neg_items_index, ofx_stream stream);
+
 /* ------------------------------------------------------------------ optimizer step ---------- */
 /* The accumulation boundary of the trainers (compatibility_prediction_trainer.py:70-80 = complementary_item_retrieval_trainer.py:89-99):
  * torch.nn.utils.clip_grad_norm_(max_norm) -> torch.optim.AdamW step (amsgrad off, maximize off) -> zero the gradient, over ONE flat

@@ -164,6 +164,7 @@ SIGNATURES = {
     "ofx_set_rank_loss_ws_bytes": (_sz, [_i, _i, _i]),
     "ofx_set_rank_loss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ofx_set_rank_loss_indexed": (_i, [_vp, _i, C.c_longlong, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ofx_cir_sample_batch": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, C.c_uint, C.c_uint, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "ofx_adamw_step_ws_bytes": (_sz, [C.c_longlong]),
     "ofx_adamw_step": (_i, [_vp, _i, _vp, _vp, _vp, C.c_longlong, _vp] + [C.c_double] * 7 + [_vp, _vp, _vp, _sz, _vp]),
     "ofx_profile_enable": (None, [_i]),

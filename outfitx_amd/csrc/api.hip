@@ -1348,6 +1348,32 @@ extern "C" int ofx_set_rank_loss_indexed(const float* table, int ld, long long n
                                             (hipStream_t)stream);
 }
 
+extern "C" int ofx_cir_sample_batch(const int* outfit_cu, const int* outfit_rows, int n_outfits, int n_outfit_rows, const int* pos_cu, const int* pos_slots,
+                                    int n_pos_slots, const int* pool_cu, const int* pool_rows, int n_pools, int n_pool_rows, const int* row_pool,
+                                    const int* row_slot, int n_table, const int* outfit_ids, int B, unsigned seed, unsigned draw, int K, int max_len,
+                                    int* item_index, int* cu_seqlens, int* target_item_index, int* neg_items_index, ofx_stream stream) {
+    OFX_REQUIRE(B >= 1, OFX_EINVAL, "cir_sample_batch: B = %d; needs B >= 1", B);
+    OFX_REQUIRE(K >= 0 && K <= 64 && max_len >= 1 && max_len <= 31, OFX_ESHAPE, "cir_sample_batch: K = %d, max_len = %d; needs 0 <= K <= 64, 1 <= max_len <= 31",
+                K, max_len);
+    OFX_REQUIRE(n_outfits >= 1 && n_table >= 1 && n_outfit_rows >= 0 && n_pos_slots >= 0 && n_pools >= 0 && n_pool_rows >= 0, OFX_ESHAPE,
+                "cir_sample_batch: n_outfits = %d, n_table = %d (both >= 1), n_outfit_rows = %d, n_pos_slots = %d, n_pools = %d, n_pool_rows = %d (all >= 0)",
+                n_outfits, n_table, n_outfit_rows, n_pos_slots, n_pools, n_pool_rows);
+    OFX_REQUIRE((long long)B * std::max(K, max_len) <= INT_MAX, OFX_ESHAPE, "cir_sample_batch: B * max(K, max_len) = %lld exceeds INT_MAX",
+                (long long)B * std::max(K, max_len));
+    const void* ptrs[] = {outfit_cu, outfit_rows, pos_cu, pos_slots, pool_cu, pool_rows, row_pool, row_slot, outfit_ids, item_index, cu_seqlens, target_item_index};
+    uintptr_t bits = (uintptr_t)neg_items_index;
+    for (const void* p : ptrs) {
+        OFX_REQUIRE(p, OFX_EINVAL, "cir_sample_batch: NULL argument");
+        bits |= (uintptr_t)p;
+    }
+    OFX_REQUIRE(neg_items_index || K == 0, OFX_EINVAL, "cir_sample_batch: NULL neg_items_index with K = %d", K);
+    OFX_REQUIRE((bits & 15) == 0, OFX_EINVAL, "cir_sample_batch: every array must be 16-byte aligned");
+    CirSampleArgs a{outfit_cu, outfit_rows, pos_cu, pos_slots, pool_cu, pool_rows, row_pool, row_slot, outfit_ids,
+                    n_outfits, n_outfit_rows, n_pos_slots, n_pools, n_pool_rows, n_table, B, K, max_len, seed, draw,
+                    item_index, cu_seqlens, target_item_index, neg_items_index};
+    return ofx_launch_cir_sample_batch(a, (hipStream_t)stream);
+}
+
 static bool adamw_shape_ok(long long n_arena) { return n_arena > 0 && n_arena % 64 == 0; }
 extern "C" size_t ofx_adamw_step_ws_bytes(long long n_arena) { return adamw_shape_ok(n_arena) ? ofx_adamw_step_ws(n_arena) : 0; }
 extern "C" int ofx_adamw_step(const ofx_opt_segment* segments, int n_segments, float* grad, float* exp_avg, float* exp_avg_sq, long long n_arena,

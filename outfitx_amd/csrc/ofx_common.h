@@ -262,6 +262,19 @@ __host__ __device__ __forceinline__ float drop_mul(const DropArgs& d, unsigned r
     h = ofx_fmix32(h ^ (col * 0x9E3779B1u + 0x7F4A7C15u));
     return h >= d.thresh ? d.scale : 0.0f;
 }
+// ---- counter-based draws (cir_sample.hip): word i of stream `stream` of batch slot b of draw `draw` under `seed` - a pure function of its
+// arguments, so host code (and the numpy restatement in tests/cir_sampler_ref.py) repeats the kernel's draws to the bit.  Every step is a
+// bijection of the argument it takes in for a fixed prefix: two slots, or two counters of one slot, never share a word by construction.
+__host__ __device__ __forceinline__ unsigned ofx_draw_u32(unsigned seed, unsigned draw, unsigned stream, unsigned b, unsigned i) {
+    unsigned h = ofx_fmix32(seed + 0x6A09E667u);
+    h = ofx_fmix32(h ^ draw);
+    h = ofx_fmix32(h + stream * 0x9E3779B9u + 0x7F4A7C15u);
+    h = ofx_fmix32(h ^ (b * 0x632BE5ABu));
+    return ofx_fmix32(h + i * 0x9E3779B1u);
+}
+// a word -> an integer of [0, n), n >= 1: the high half of u * n.  Every value is hit floor(2^32 / n) or that + 1 times, so the
+// probabilities differ from 1 / n by less than 2^-32 each: a relative bias below n / 2^32 (1.2e-3 at n = 5,000,000, 2.3e-6 at n = 10,000).
+__host__ __device__ __forceinline__ unsigned ofx_draw_below(unsigned u, unsigned n) { return (unsigned)(((unsigned long long)u * n) >> 32); }
 inline DropArgs make_drop(float p, unsigned seed, unsigned site) {
     DropArgs d;
     if (p > 0.f) { d.seed = seed; d.site = site; d.thresh = (unsigned)((double)p * 4294967296.0); d.scale = 1.0f / (1.0f - p); }
@@ -363,6 +376,14 @@ int ofx_launch_fold_pack(const float* Wsrc, const float* gamma, const float* bet
                          int N, int K, int op_dtype, hipStream_t s, int split = 0);
 int ofx_launch_cir_prefix(const float* img_emb, const float* txt, float* out, int B, int D, hipStream_t s);
 int ofx_launch_cp_head(const float* row0, const float* w, const float* bias, float* logits, int B, int D, hipStream_t s);
+
+struct CirSampleArgs {       // ofx_cir_sample_batch (include/ofx.h), cir_sample.hip
+    const int *outfit_cu, *outfit_rows, *pos_cu, *pos_slots, *pool_cu, *pool_rows, *row_pool, *row_slot, *outfit_ids;
+    int n_outfits, n_outfit_rows, n_pos_slots, n_pools, n_pool_rows, n_table, B, K, max_len;
+    unsigned seed, draw;
+    int *item_index, *cu_seqlens, *target_item_index, *neg_items_index;
+};
+int ofx_launch_cir_sample_batch(const CirSampleArgs& a, hipStream_t s);
 
 struct AttnArgs {
     const void* qkv;          // [nseq*seq_len, ld] operand type: q at col 0, k at col k_off, v at col v_off; head h at +h*64

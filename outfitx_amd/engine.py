@@ -98,6 +98,45 @@ class Engine:
     def ws_bytes(self, op: int, n: int, length: int) -> int:
         return int(self.lib.ofx_workspace_bytes(self.h, op, n, length))
 
+    @staticmethod
+    def cir_sample_batch(split: Dict[str, torch.Tensor], pools: Dict[str, torch.Tensor], outfit_ids: torch.Tensor, seed: int, draw: int, K: int,
+                         max_len: int, n_pool_rows: Optional[int] = None):
+        """One CIR training batch drawn on the device (ofx_cir_sample_batch; semantics in include/ofx.h).  The entry is stateless: it
+        takes no handle, so a dataset calls this without an engine.  split: the int32 device tensors 'outfit_cu', 'outfit_rows', 'pos_cu',
+        'pos_slots'; pools: 'pool_cu', 'pool_rows', 'row_pool', 'row_slot' (sampler.CIRDeviceDataset and sampler.CIRNegativePools build
+        both); outfit_ids: int32 [B] on the same device (another dtype or device, or a view that is not 16-byte aligned, is copied
+        first).  n_pool_rows: the live length of pool_rows when the tensor is longer (an empty array is uploaded as one element).
+        -> (item_index [B * max_len] - compact, its tail past cu_seqlens[B] is uninitialised -, cu_seqlens [B + 1], target_item_index [B],
+        neg_items_index [B, K]), int32.  Two launches on the current stream; no copy to or from the host and no wait when outfit_ids is
+        already an aligned device tensor."""
+        lib = L.load()
+        dev = split["outfit_cu"].device
+        if dev.type != "cuda":
+            raise L.OfxError("cir_sample_batch needs HIP tensors; there is no CPU path")
+        ts = [split[k] for k in ("outfit_cu", "outfit_rows", "pos_cu", "pos_slots")] + [pools[k] for k in ("pool_cu", "pool_rows", "row_pool", "row_slot")]
+        for t in ts:
+            if t.device != dev or t.dtype != torch.int32 or not t.is_contiguous():
+                raise ValueError(f"cir_sample_batch: every table must be a contiguous int32 tensor on {dev}")
+        ocu, orows, pcu, pslots, gcu, grows, rpool, rslot = ts
+        if rpool.numel() != rslot.numel() or pcu.numel() != ocu.numel():
+            raise ValueError("cir_sample_batch: row_pool / row_slot or outfit_cu / pos_cu differ in length")
+        ids = outfit_ids if isinstance(outfit_ids, torch.Tensor) else torch.as_tensor(outfit_ids)
+        ids = ids.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+        if ids.data_ptr() % 16:
+            ids = ids.clone()                                   # a slice of a longer tensor: a fresh allocation is aligned
+        B, K, max_len = ids.numel(), int(K), int(max_len)
+        item_index = torch.empty(max(B * max_len, 1), dtype=torch.int32, device=dev)
+        cu = torch.empty(B + 1, dtype=torch.int32, device=dev)
+        target = torch.empty(B, dtype=torch.int32, device=dev)
+        neg = torch.empty(B, max(K, 0), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            L.check(lib.ofx_cir_sample_batch(_ptr(ocu), _ptr(orows), ocu.numel() - 1, orows.numel(), _ptr(pcu), _ptr(pslots), pslots.numel(), _ptr(gcu),
+                                             _ptr(grows), gcu.numel() - 1, grows.numel() if n_pool_rows is None else int(n_pool_rows), _ptr(rpool),
+                                             _ptr(rslot), rpool.numel(), _ptr(ids), B, int(seed) & 0xFFFFFFFF,
+                                             int(draw) & 0xFFFFFFFF, K, max_len, _ptr(item_index), _ptr(cu), _ptr(target), _ptr(neg) if K > 0 else None,
+                                             _stream(dev)), "ofx_cir_sample_batch")
+        return item_index, cu, target, neg
+
     # ---------------------------------------------------------------- outfit transformer
     def stage_set(self, setin) -> "SetInput":
         """The one place that validates and stages a set input: (x [B,L,D] float, mask [B,L], True / non-zero = pad) or the indexed

@@ -363,15 +363,20 @@ class CIRTrainer(FlatGradTrainer):
     {'input_dict': {...CIR task tensors...}, 'pos_item_embedding' [B,D], 'neg_items_embedding' [B,K,D], 'neg_items_mask' [B,K] bool}.
     Replaces ComplementaryItemRetrievalTrainer.train_epoch (:66-116) and, as `valid_epoch`, its validation loop with the recall@k inside
     the target's category pool (:122-249; validation batches additionally carry 'pos_item_group' [B] and 'pos_item_row' [B], the
-    positive's category and its row inside that category's pool).  Negative sampling, the easy -> hard switch, checkpoints and logging
-    stay with the caller.
+    positive's category and its row inside that category's pool).  Checkpoints and logging stay with the caller; so does negative sampling
+    for batches made on the host - `sampler.CIRDeviceDataset` draws whole training batches on the device instead (below).
 
     Index-form batches (processor.OutfitXIndexedProcessor with the CIR task) carry table rows instead of embeddings:
     {'input_dict': {'task', 'item_index', 'cu_seqlens', 'target_item_index'}, 'pos_item_index' [B] int32, 'neg_items_index' [B,K] int32,
     negative = padded}.  A batch that has 'pos_item_index' takes the loss's `forward_indexed`, which reads the positives and the negatives
     straight from the embedding table - `embedding_table=` here, else `model.embedding_table` (OutfitX.set_embedding_table) - so a step is
     fed by a few hundred KB of int32 and no [B,K,D] tensor exists on host or device; same bits as the dense batch gathered from those rows.
-    Both forms can be mixed freely; the caller still samples the negatives, now handing over their ids."""
+    Both forms can be mixed freely.  The index form's tensors may already live on the device: `train_epoch(ds.epoch(batch_size, epoch))`
+    with a `sampler.CIRDeviceDataset` gets every batch from one kernel call (positive, shuffled and truncated remainder, K negatives;
+    `ds.set_pools` is the easy -> hard switch) with no host tensor, H2D copy or synchronisation per step.  Nothing here changes for that:
+    `Engine.stage_set` trusts device-side index tensors, takes B from `cu_seqlens` and hands `item_index` over by address, so the
+    dataset's over-allocated `item_index` [B * max_length] (compact up to cu_seqlens[B]) is read exactly as far as a host-built one;
+    tests/test_gpu_cir_sampler.py holds losses and parameters to the bits of the same batches fed from host tensors."""
 
     head = "cir"
 

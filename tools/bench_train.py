@@ -25,6 +25,16 @@ step on device-resident batches (`ms_step_indexed_*` / `ms_step_dense_*`) and on
 as a DataLoader does (`ms_step_hostfed_*`), and the bytes per batch of both forms, computed here (`batch_bytes_*`).  Those keys are also
 written to --indexed-out (profiles/cir_indexed_bench.json).
 
+Last, the batches DRAWN ON THE DEVICE (outfitx_amd/sampler.py, ofx_cir_sample_batch): --device-batch queries (3072) from outfits of
+--items + 1 items over the --table rows in --pools negative pools.  `ms_batch_build_*` is the build of one batch alone (device events;
+`_wall`: host and device, calls back to back); `ms_step_resident_*` / `ms_step_hostfed_*` / `ms_step_devicefed_*` are the CIRTrainer step on
+one fixed device-resident index batch, on that batch handed over from pinned host memory on every step, and on a fresh batch drawn by
+`CIRDeviceDataset.batch` before every step - --device-rounds rounds, the three alternating inside every round, medians over the rounds
+with every round's value in `*_rounds_*`.  `devicefed_inside_resident_range_*` says whether the device-fed median lies between the
+smallest and the largest resident round of this session.  `ms_host_collate_indexed_committed` repeats the host collate of one such batch
+from profiles/cir_indexed_collate_bench.json (before the caller's own sampling).  --device-only runs this leg alone; --device-out writes its
+line (profiles/cir_device_batches_bench.json).
+
 The CP run also times the accumulation BOUNDARY alone at the CP arena's real size (51.3 M floats) in its two forms, alternating in
 one process, medians over --boundary-reps device-event timings after a warm-up: `ms_boundary_torch` (vector_norm -> mul_ -> fused AdamW
 over the per-tensor views -> zero_, plus the div_ by the world size when there is more than one rank) and `ms_boundary_hip`
@@ -205,6 +215,69 @@ def cir_indexed_bench(a, m, params, B, K, res):
     del m.embedding_table
 
 
+def cir_device_bench(a, m, params, B, K):
+    """Batches drawn on the device (outfitx_amd.sampler, ofx_cir_sample_batch) feeding CIRTrainer (module docstring) -> the result dict."""
+    from outfitx_amd.sampler import CIRDeviceDataset, CIRNegativePools
+    from outfitx_amd.trainer import CIRTrainConfig, CIRTrainer
+    g = np.random.default_rng(99)
+    n_outfits = max(4 * B, 16384)
+    outfits = g.integers(0, a.table, (n_outfits, a.items + 1)).tolist()          # one item becomes the positive, a.items remain
+    pools = CIRNegativePools(g.integers(0, a.pools, a.table))
+    ds = CIRDeviceDataset(outfits, pools, None, max_length=a.pad, negatives=K, seed=99)
+    m.set_embedding_table(torch.from_numpy(synth.item_embeddings(99, "table", a.table) * 3.0))
+    res = {"workload": f"CIR batches of {B} drawn on the device from {n_outfits} outfits of {a.items + 1} items, a {a.table}-row table in {a.pools} pools, "
+                       f"{K} negatives per query, feeding the CIRTrainer step", "precision": a.precision, "steps": a.steps, "rounds": a.device_rounds,
+           "loss_reps": a.loss_reps}
+    order = ds.order(0)
+    ids = order[:B]
+    k = [0]
+
+    def build():
+        k[0] += 1
+        return ds.batch(ids, k[0])
+
+    ts = sample_ms([build], a.loss_reps, 5)[0]                                  # device time of one batch build (two launches + four allocations)
+    res[f"ms_batch_build_b{B}"] = float(np.median(ts))
+    res[f"ms_batch_build_min_b{B}"], res[f"ms_batch_build_max_b{B}"] = float(np.min(ts)), float(np.max(ts))
+    res[f"ms_batch_build_wall_b{B}"] = timed(build, a.steps, a.warmup)           # host + device, back to back
+    one = ds.batch(ids, 0)
+    total = int(one["input_dict"]["cu_seqlens"][-1])
+    compact = lambda f: {"input_dict": {n: (v if n == "task" else f(v[:total] if n == "item_index" else v)) for n, v in one["input_dict"].items()},
+                         "pos_item_index": f(one["pos_item_index"]), "neg_items_index": f(one["neg_items_index"])}
+    resident, pinned = compact(lambda v: v.clone()), compact(lambda v: v.cpu().pin_memory())
+    res[f"batch_bytes_b{B}"] = int(sum(v.numel() * 4 for v in (*[t for n, t in resident["input_dict"].items() if n != "task"], resident["neg_items_index"])))
+    n_steps = ds.steps_per_epoch(B, drop_last=True)
+    legs = {"resident": [], "hostfed": [], "devicefed": []}
+    for r in range(a.device_rounds):                                            # the three feeds alternate: each round times every one of them
+        for leg in legs:
+            tr = CIRTrainer(m, steps_per_epoch=10 ** 9, cfg=CIRTrainConfig(accumulation_steps=1), params=params)
+            s = [0]
+
+            def step():
+                i = s[0]; s[0] += 1
+                if leg == "devicefed":
+                    b = ds.batch(order[(i % n_steps) * B:(i % n_steps + 1) * B], ds.draw_of(r, i))
+                else:
+                    b = resident if leg == "resident" else pinned
+                tr.micro_step(b, i)
+            legs[leg].append(timed(step, a.steps, a.warmup))
+            del tr
+    for leg, t in legs.items():
+        res[f"ms_step_{leg}_b{B}"] = float(np.median(t))
+        res[f"ms_step_{leg}_rounds_b{B}"] = [float(v) for v in t]
+    lo, hi = min(legs["resident"]), max(legs["resident"])
+    res[f"devicefed_inside_resident_range_b{B}"] = bool(lo <= res[f"ms_step_devicefed_b{B}"] <= hi)
+    res[f"devicefed_over_resident_b{B}"] = res[f"ms_step_devicefed_b{B}"] / res[f"ms_step_resident_b{B}"]
+    try:                                                                        # the committed host-side figure the device build replaces
+        with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "cir_indexed_collate_bench.json")) as f:
+            c = json.loads(f.readline())
+        res["ms_host_collate_indexed_committed"], res["host_collate_batch"] = c["ms_collate_indexed"], c["batch"]
+    except (OSError, ValueError, KeyError):
+        pass
+    del m.embedding_table
+    return res
+
+
 def cir_main(a, m, params):
     from outfitx_amd.engine import set_rank_loss
     from outfitx_amd.trainer import CIRTrainConfig, CIRTrainer
@@ -215,6 +288,17 @@ def cir_main(a, m, params):
     params = [p for p in params if id(p) not in off]
     res = {"workload": f"CIR trainer step, outfits x {a.items} items (padded {a.pad}), {K} negatives per query, precomputed embeddings",
            "precision": a.precision, "loss_reps": a.loss_reps}
+
+    def device_leg():
+        dres = cir_device_bench(a, m, params, a.device_batch, K)
+        if a.device_out:
+            with open(a.device_out, "w") as f:
+                f.write(json.dumps(dres) + "\n")
+        return dres
+
+    if a.device_only:
+        print(json.dumps(device_leg()))
+        return
     for B in [int(v) for v in a.cir_batches.split(",")]:
         emb, mask = synth.outfit_batch(99, B, a.pad, a.items)
         batch = {"input_dict": {"task": CIR, "outfit_embedding": torch.from_numpy(emb).cuda(), "outfit_mask": torch.from_numpy(mask).cuda(),
@@ -257,6 +341,7 @@ def cir_main(a, m, params):
     for B in [int(v) for v in a.cir_batches.split(",")]:
         cir_indexed_bench(a, m, params, B, K, ires)
     res.update({k: v for k, v in ires.items() if k not in res})
+    res.update({k: v for k, v in device_leg().items() if k not in res})
     print(json.dumps(res))
     if a.indexed_out:
         with open(a.indexed_out, "w") as f:
@@ -271,6 +356,11 @@ def main():
     ap.add_argument("--loss-reps", type=int, default=30)
     ap.add_argument("--table", type=int, default=100_000, help="rows of the device-resident embedding table (CIR task, index form)")
     ap.add_argument("--indexed-out", default="", help="also write the index-form keys to this file (CIR task)")
+    ap.add_argument("--pools", type=int, default=32, help="negative pools the table's rows fall into (CIR task, device-built batches)")
+    ap.add_argument("--device-batch", type=int, default=3072, help="batch of the device-built leg (CIR task)")
+    ap.add_argument("--device-rounds", type=int, default=5, help="rounds over the resident / host-fed / device-fed steps, alternating (CIR task)")
+    ap.add_argument("--device-out", default="", help="also write the device-built leg's line to this file (CIR task)")
+    ap.add_argument("--device-only", action="store_true", help="CIR task: the device-built leg alone")
     ap.add_argument("--boundary-reps", type=int, default=30)
     ap.add_argument("--boundary-out", default="", help="also write the JSON line to this file (CP task)")
     ap.add_argument("--batch", type=int, default=256)
