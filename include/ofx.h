@@ -146,6 +146,21 @@ int ofx_clip_text_fwd(ofx_handle* h, const int64_t* ids, const int64_t* attn_mas
  * Non-finite inputs follow torch: a NaN distance wins over every number and the first NaN is returned; +inf is an ordinary (largest) value. */
 int ofx_fitb_argmin(const float* y_hat, const float* cand, int B, int C, int D, int64_t* idx, float* dist,
                     ofx_stream stream);
+/* Row H with the candidates named by row of a device-resident embedding table (the index form of a FITB batch: no [B, C, D] tensor exists
+ * anywhere):  exactly ofx_fitb_argmin with cand[b, c] = table[cand_index[b, c]] - the same kernel body reading its candidate rows through the
+ * indices, the same summation order, hence the same bits in idx and dist as the dense call on the gathered rows, the tie and NaN rules included.
+ *   table [n_table, ld] fp32, ld >= D, ld % 4 == 0, 16-byte aligned (a row's first D floats are used); cand_index int32 [B, C], contiguous;
+ *   y_hat [B, D] fp32, 16-byte aligned; idx int64 [B]; dist fp32 [B, C] optional.
+ *   answer int64 [B] with n_correct DEVICE int [1], both or neither: *n_correct += the number of b with idx[b] == answer[b] (the reference's
+ *   `correct` of fill_in_the_blank_trainer.py:56).  It accumulates - the caller zeroes it - so a whole test epoch adds into one counter and
+ *   reads it once, without a host synchronisation per batch.  Integer atomics only: the count does not depend on the order of arrival.
+ *   cand_index lives on the device, so the host cannot check its values: the kernel clamps every entry into [0, n_table).  A wrong index
+ *   gives a wrong answer, never an access outside the table.
+ * NULL table / cand_index / y_hat / idx, only one of answer / n_correct, table or y_hat not 16-byte aligned: OFX_EINVAL; B < 1, C < 1,
+ * D % 4 != 0 or D < 4, ld < D, ld % 4 != 0, n_table outside [1, INT_MAX]: OFX_ESHAPE - a rejected call launches nothing.  One launch on
+ * `stream`, no workspace, no handle, no allocation, copy or wait (capturable). */
+int ofx_fitb_argmin_indexed(const float* table, int ld, long long n_table, const int* cand_index, const float* y_hat, int B, int C, int D,
+                            const int64_t* answer, int64_t* idx, float* dist, int* n_correct, ofx_stream stream);
 /* Row I: torch.cdist(Q,P) -> topk(k, largest=False) (complementary_item_retrieval_trainer.py:240-249).
  * fp32-exact distances; ascending; ties -> smaller pool index.  idx int64 [nq,k] = row + index_base.
  * Preconditions, checked: D a multiple of 32 and 1 <= k <= min(128, np) (else OFX_ESHAPE), Q and P 16-byte aligned and no NULL argument

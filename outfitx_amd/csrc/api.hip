@@ -165,6 +165,8 @@ int ofx_launch_adamw_step(const ofx_opt_segment* segments, int n_segments, float
 int ofx_launch_cp_head_bwd(const float* dlogits, const float* w_or_rows, const int* cu, float* dX, void* dXb, float* db, int B, int D, int op_dtype,
                            const DropArgs& head, const DropArgs& below, hipStream_t s, int accumulate = 0);
 int ofx_launch_fitb(const float* y, const float* cand, int B, int C, int D, int64_t* idx, float* dist, hipStream_t s);
+int ofx_launch_fitb_indexed(const float* table, int ld, int n_table, const int* cand_index, const float* y, int B, int C, int D, const int64_t* answer,
+                            int64_t* idx, float* dist, int* n_correct, hipStream_t s);
 int ofx_launch_l2_topk(const float* Q, const float* P, int nq, int np, int D, int k, int64_t index_base, int64_t* idx,
                        float* dist, void* ws, size_t ws_bytes, hipStream_t s);
 size_t ofx_l2_topk_ws(int nq, int np);
@@ -985,6 +987,17 @@ extern "C" int ofx_clip_text_fwd(ofx_handle* h, const int64_t* ids, const int64_
 extern "C" int ofx_fitb_argmin(const float* y, const float* cand, int B, int C, int D, int64_t* idx, float* dist, ofx_stream stream) {
     OFX_REQUIRE(y && cand && idx && B > 0 && C > 0 && D > 0 && D % 4 == 0, OFX_EINVAL, "fitb_argmin: bad argument");
     return ofx_launch_fitb(y, cand, B, C, D, idx, dist, (hipStream_t)stream);
+}
+extern "C" int ofx_fitb_argmin_indexed(const float* table, int ld, long long n_table, const int* cand_index, const float* y_hat, int B, int C, int D,
+                                       const int64_t* answer, int64_t* idx, float* dist, int* n_correct, ofx_stream stream) {
+    OFX_REQUIRE(table && cand_index && y_hat && idx, OFX_EINVAL, "fitb_argmin_indexed: NULL argument");
+    OFX_REQUIRE((answer != nullptr) == (n_correct != nullptr), OFX_EINVAL, "fitb_argmin_indexed: answer and n_correct go together");
+    OFX_REQUIRE((((uintptr_t)table | (uintptr_t)y_hat) & 15) == 0, OFX_EINVAL, "fitb_argmin_indexed: table and y_hat must be 16-byte aligned");
+    OFX_REQUIRE(B >= 1 && C >= 1 && D >= 4 && D % 4 == 0, OFX_ESHAPE, "fitb_argmin_indexed: B = %d, C = %d, D = %d; needs B >= 1, C >= 1, D %% 4 == 0, D >= 4",
+                B, C, D);
+    OFX_REQUIRE(ld >= D && ld % 4 == 0 && n_table >= 1 && n_table <= INT_MAX, OFX_ESHAPE,
+                "fitb_argmin_indexed: ld = %d, n_table = %lld; needs ld >= D = %d, ld %% 4 == 0, 1 <= n_table <= INT_MAX", ld, n_table, D);
+    return ofx_launch_fitb_indexed(table, ld, (int)n_table, cand_index, y_hat, B, C, D, answer, idx, dist, n_correct, (hipStream_t)stream);
 }
 extern "C" int ofx_l2_topk(ofx_handle*, const float* Q, const float* P, int nq, int np, int D, int k, int64_t index_base,
                            int64_t* idx, float* dist, void* ws, size_t ws_bytes, ofx_stream stream) {

@@ -3,7 +3,8 @@
 // fp32 list) and ties are broken deterministically (smaller pool index first).
 //
 //  fitb_argmin : torch.cdist(y[B,1,D], cand[B,C,D]).squeeze(1).argmin(-1)
-//                (reference src/trains/trainers/fill_in_the_blank_trainer.py:50-56)
+//                (reference src/trains/trainers/fill_in_the_blank_trainer.py:50-56); its indexed form reads the candidates by row of the
+//                embedding table (the same kernel body, no [B,C,D] tensor) and can count idx == answer (:56) into a device integer.
 //  l2_topk     : torch.cdist(Q,P) -> torch.topk(k, largest=False)
 //                (reference src/trains/trainers/complementary_item_retrieval_trainer.py:240-249)
 //                = row norms + fp32-MFMA (v_mfma_f32_32x32x2_f32, an exact fmaf chain) distance
@@ -17,13 +18,38 @@
 
 namespace {
 
-__global__ __launch_bounds__(256) void fitb_kernel(const float* y, const float* cand, int B, int C, int D, int64_t* idx, float* dist) {
+// Where fitb_kernel's candidate rows come from - ONE body:
+//   DenseCand  cand [B, C, D] (ofx_fitb_argmin);
+//   TableCand  cand[b, c] = table[cand_index[b, c]], the row's first D floats (ofx_fitb_argmin_indexed).  The index is one load of one
+//              address per wave, clamped into [0, n_table) as it is fetched and made wave-uniform: a wrong index gives a wrong answer,
+//              never an access outside the table.
+// Same arithmetic in the same order on the same values: both forms return the same bits for the same rows.
+struct DenseCand {
+    const float* cand;
+    __device__ __forceinline__ const float* row(int b, int c, int C, int D) const { return cand + ((size_t)b * C + c) * D; }
+};
+struct TableCand {
+    const float* table;
+    const int* index;
+    int ld, last;
+    __device__ __forceinline__ const float* row(int b, int c, int C, int) const {
+        const int t = __builtin_amdgcn_readfirstlane(index[(size_t)b * C + c]);
+        return table + (size_t)min(max(t, 0), last) * ld;
+    }
+};
+
+// One wave per question.  answer / n_correct (both or neither): *n_correct += the number of questions with idx[b] == answer[b] - an integer
+// atomic, one per wave that scored a hit (its hits over the whole grid-stride walk), so the count does not depend on arrival order.
+template <class SRC>
+__global__ __launch_bounds__(256) void fitb_kernel(const float* y, const SRC src, int B, int C, int D, int64_t* idx, float* dist, const int64_t* answer,
+                                                   int* n_correct) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int hits = 0;
     for (int b = blockIdx.x * 4 + w; b < B; b += gridDim.x * 4) {
         float best = INFINITY;
         int arg = 0;
         for (int c = 0; c < C; ++c) {
-            const float* cp = cand + ((size_t)b * C + c) * D;
+            const float* cp = src.row(b, c, C, D);
             float s = 0.f;
             for (int i = lane; i < D / 4; i += 64) {
                 const f32x4 a = *(const f32x4*)(y + (size_t)b * D + i * 4), k = *(const f32x4*)(cp + i * 4);
@@ -36,7 +62,9 @@ __global__ __launch_bounds__(256) void fitb_kernel(const float* y, const float* 
             if (dd < best || (dd != dd && best == best)) { best = dd; arg = c; }
         }
         if (lane == 0) idx[b] = arg;
+        if (answer) hits += (int64_t)arg == answer[b];        // arg is wave-uniform (wave_sum leaves the sum in every lane): so is hits; lane 0's copy is used
     }
+    if (hits && lane == 0) atomicAdd(n_correct, hits);
 }
 
 __global__ __launch_bounds__(256) void sqnorm_kernel(const float* x, float* out, int rows, int D) {
@@ -443,7 +471,16 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const int64_t* idx_in, 
 
 int ofx_launch_fitb(const float* y, const float* cand, int B, int C, int D, int64_t* idx, float* dist, hipStream_t s) {
     int grid = (B + 3) / 4; if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(fitb_kernel, dim3(grid), dim3(256), 0, s, y, cand, B, C, D, idx, dist);
+    hipLaunchKernelGGL(fitb_kernel<DenseCand>, dim3(grid), dim3(256), 0, s, y, DenseCand{cand}, B, C, D, idx, dist, (const int64_t*)nullptr, (int*)nullptr);
+    OFX_LAUNCH_CHECK();
+    return OFX_OK;
+}
+
+int ofx_launch_fitb_indexed(const float* table, int ld, int n_table, const int* cand_index, const float* y, int B, int C, int D, const int64_t* answer,
+                            int64_t* idx, float* dist, int* n_correct, hipStream_t s) {
+    int grid = (B + 3) / 4; if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(fitb_kernel<TableCand>, dim3(grid), dim3(256), 0, s, y, TableCand{table, cand_index, ld, n_table - 1}, B, C, D, idx, dist, answer,
+                       n_correct);
     OFX_LAUNCH_CHECK();
     return OFX_OK;
 }

@@ -491,6 +491,57 @@ def fitb_argmin(y_hat: torch.Tensor, cand: torch.Tensor, return_dist: bool = Fal
     return (idx, dist) if return_dist else idx
 
 
+def fitb_argmin_indexed(table: torch.Tensor, cand_index: torch.Tensor, y_hat: torch.Tensor, answer: Optional[torch.Tensor] = None,
+                        n_correct: Optional[torch.Tensor] = None, return_dist: bool = False):
+    """fitb_argmin with cand[b, c] = table[cand_index[b, c]] read straight from the table (ofx_fitb_argmin_indexed): no [B, C, D] tensor is
+    gathered; same bits as fitb_argmin on the gathered rows.
+    table [n, ld] fp32 on y_hat's device with unit column stride: a column slice of a wider table is taken as it is (ld = its row stride,
+    ld % 4 == 0, first element 16-byte aligned).  A table in any other layout is refused (ValueError), never copied: a copy per call
+    would move the whole table for every batch.
+    cand_index [B, C] integer; y_hat [B, D], D <= ld: a row's first D floats are used.
+    answer [B] integer with n_correct, a 1-element int32 tensor on y_hat's device, both or neither: the call adds the number of questions
+    with idx == answer to n_correct in place (zero it first; nothing waits for the device).
+    A cand_index on the host is range-checked here (IndexError); one on the device is trusted - the kernel clamps it into the table.
+    -> idx [B] int64 (, dist [B, C])."""
+    lib = L.load()
+    dev = y_hat.device
+    if dev.type != "cuda":
+        raise L.OfxError("fitb_argmin_indexed needs HIP tensors; there is no CPU path")
+    if table.dim() != 2 or y_hat.dim() != 2 or cand_index.dim() != 2 or cand_index.shape[0] != y_hat.shape[0] or table.shape[1] < y_hat.shape[1]:
+        raise ValueError(f"fitb_argmin_indexed: table {tuple(table.shape)}, cand_index {tuple(cand_index.shape)}, y_hat {tuple(y_hat.shape)} "
+                         "are not [n,>=D], [B,C], [B,D]")
+    if (answer is None) != (n_correct is None):
+        raise ValueError("fitb_argmin_indexed: answer and n_correct go together")
+    B, D = y_hat.shape
+    Cn = cand_index.shape[1]
+    if cand_index.device.type == "cpu" and cand_index.numel():
+        lo, hi = int(cand_index.min()), int(cand_index.max())
+        if lo < 0 or hi >= table.shape[0]:
+            raise IndexError(f"cand_index out of range [0, {table.shape[0]}): min {lo}, max {hi}")
+    tb = table.detach()
+    # the table is read in place or not at all: a private fp32 copy per call would move the whole table for every batch
+    if (tb.device != dev or tb.dtype != torch.float32 or tb.stride(1) != 1 or tb.stride(0) < tb.shape[1] or tb.stride(0) % 4
+            or tb.data_ptr() % 16):
+        raise ValueError(f"fitb_argmin_indexed: the table must be fp32 on {dev} with unit column stride, a row stride that is a multiple of 4 "
+                         f"floats and a 16-byte aligned first element (a column slice must start at a multiple of 4 columns); got "
+                         f"{tb.dtype} on {tb.device}, strides {tuple(tb.stride())}, offset {tb.data_ptr() % 16} bytes past alignment")
+    y = _f32c(y_hat.detach(), dev)
+    ci = cand_index.to(device=dev, dtype=torch.int32, non_blocking=True).contiguous()
+    ans = None
+    if answer is not None:
+        if answer.numel() != B:
+            raise ValueError(f"fitb_argmin_indexed: answer holds {answer.numel()} entries, the batch {B} questions")
+        if n_correct.device != dev or n_correct.dtype != torch.int32 or n_correct.numel() != 1:
+            raise ValueError(f"fitb_argmin_indexed: n_correct must be a 1-element int32 tensor on {dev}")
+        ans = answer.reshape(-1).to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
+    idx = torch.empty(B, dtype=torch.int64, device=dev)
+    dist = torch.empty(B, Cn, dtype=torch.float32, device=dev) if return_dist else None
+    with torch.cuda.device(dev):
+        L.check(lib.ofx_fitb_argmin_indexed(_ptr(tb), tb.stride(0), tb.shape[0], _ptr(ci), _ptr(y), B, Cn, D, _ptr(ans), _ptr(idx), _ptr(dist),
+                                            _ptr(n_correct), _stream(dev)), "ofx_fitb_argmin_indexed")
+    return (idx, dist) if return_dist else idx
+
+
 def dropout_mask(p: float, seed: int, site: int, rows: int, cols: int, device) -> torch.Tensor:
     """keep-mask / (1 - p) of one dropout site exactly as the training kernels compute it (test aid)."""
     lib = L.load()

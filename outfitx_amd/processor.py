@@ -124,15 +124,28 @@ class OutfitXIndexedProcessor:
     -1 where that processor's `neg_items_mask` is True.  The trainer's loss reads the rows from the table
     (`SetWiseRankingLoss.forward_indexed`): a batch is a few hundred KB of int32 instead of hundreds of MB of fp32.
 
+    FITB (`fitb_candidates` 'embedding' | 'index', ignored for CP / CIR): 'embedding', the default, takes the reference dataset's samples
+    `(query, candidate_embeddings [C, D], answer_index)` and ships `candidate_item_embedding` fp32 [B, C, D] and a dense
+    `target_item_text_embedding` beside the indexed outfit.  'index' takes `(query, candidate_item_ids, answer_index)` - the ids the
+    reference dataset holds before it looks the embeddings up (polyvore_fill_in_the_blank_dataset.py:36-43) - and everything the batch
+    names is a table row: `input_dict = {task (the CIR class, as the reference's FITB processor emits), item_index, cu_seqlens,
+    target_item_index}` with `target_item_index` the row of `query.target_item` (the answer candidate, :37-40), `candidate_item_index`
+    int32 [B, C] and `answer_index` long [B]; `trainer.FITBEvaluator` scores such a batch straight from the table.  Unequal candidate
+    counts inside a batch raise ValueError (the reference's torch.stack fails there too).
+
     id_to_row: item_id -> row of the table (embedding_store.EmbeddingTable.index)."""
 
     def __init__(self, task: Type, cfg: Optional[OutfitXConfig] = None, id_to_row=None,
-                 run_mode: Optional[Literal["train", "valid", "test"]] = None):
+                 run_mode: Optional[Literal["train", "valid", "test"]] = None,
+                 fitb_candidates: Literal["embedding", "index"] = "embedding"):
         self.task, self.cfg = task, cfg if cfg is not None else OutfitXConfig()
         self.id_to_row = id_to_row
         if task is OutfitComplementaryItemRetrievalTask and run_mode not in ("train", "valid", "test"):
             raise ValueError(f"the indexed CIR collate needs run_mode 'train' | 'valid' | 'test', got {run_mode!r}")
+        if fitb_candidates not in ("embedding", "index"):
+            raise ValueError(f"fitb_candidates must be 'embedding' or 'index', got {fitb_candidates!r}")
         self.run_mode = run_mode
+        self.fitb_candidates = fitb_candidates
 
     def _row(self, item_id) -> int:
         return int(item_id) if self.id_to_row is None else int(self.id_to_row[item_id])
@@ -166,6 +179,15 @@ class OutfitXIndexedProcessor:
         if self.task is OutfitFillInTheBlankTask:
             queries, cands, answers = zip(*batch)
             idx, cu = self._index([q.outfit for q in queries])
+            if self.fitb_candidates == "index":
+                if len({len(c) for c in cands}) != 1:
+                    raise ValueError(f"FITB questions of one batch must have the same number of candidates, got {sorted({len(c) for c in cands})}")
+                ci = np.array([[self._row(j) for j in c] for c in cands], np.int32).reshape(len(cands), -1)
+                target = torch.from_numpy(np.fromiter((self._row(q.target_item.item_id) for q in queries), np.int32, count=len(queries)))
+                return {"input_dict": {"task": OutfitComplementaryItemRetrievalTask, "item_index": idx, "cu_seqlens": cu,
+                                       "target_item_index": target},
+                        "candidate_item_index": torch.from_numpy(ci),
+                        "answer_index": torch.tensor(answers, dtype=torch.long)}
             txt = torch.from_numpy(np.stack([np.asarray(q.target_item.text_embedding, np.float32) for q in queries]))
             return {"input_dict": {"task": OutfitComplementaryItemRetrievalTask, "item_index": idx, "cu_seqlens": cu,
                                    "target_item_text_embedding": txt},

@@ -10,6 +10,9 @@ not Python's `random` stream; a draw is a pure function of (seed, draw, batch sl
     pools = {"easy": CIRNegativePools(semantic_category_of_row), "hard": CIRNegativePools(category_id_of_row)}
     ds = CIRDeviceDataset(outfits, pools["easy"], positive_idx_lists, negatives=10)
     trainer.train_epoch(ds.epoch(3072, epoch))          # ... ds.set_pools(pools["hard"]) is the easy -> hard switch
+
+`FITBDeviceSplit` does the same for the fill-in-the-blank test, which draws nothing: the split's questions, candidates and answers are
+uploaded once and every batch is a set of device views (`trainer.FITBEvaluator(model).test_epoch(split.batches(1024))`).
 """
 from __future__ import annotations
 
@@ -69,6 +72,70 @@ class CIRNegativePools:
         self.dev: Optional[Dict[str, torch.Tensor]] = None
         if self.device is not None:
             self.dev = {k: _upload(getattr(self, k), self.device) for k in ("pool_cu", "pool_rows", "row_pool", "row_slot")}
+
+
+class FITBDeviceSplit:
+    """A fill-in-the-blank split (the questions of polyvore's fill_in_the_blank/test.json) on the device, uploaded once: `question_rows`
+    int [total items] and `question_cu` int [N + 1] - question q's outfit is the table rows question_rows[question_cu[q] .. question_cu[q + 1])
+    -, `candidate_rows` int [N, C] - its candidates' table rows - and `answers` int [N] - which candidate is right.  `batches(batch_size)`
+    yields the index-form batches `trainer.FITBEvaluator` takes, every tensor a view of (or a device computation on) the uploaded arrays: no
+    H2D copy and no synchronisation per batch.  The host keeps `question_cu` to cut `item_index`; `cu_seqlens` is rebased to 0 on the device.
+    `target_item_index` is the answer candidate's row, what the reference's dataset puts into `query.target_item`
+    (polyvore_fill_in_the_blank_dataset.py:37-40); computed once at upload.
+    ValueError: arrays that do not fit together, offsets that do not start at 0, ascend and end at len(question_rows), an answer outside
+    [0, C); with `n_table` given also a row outside [0, n_table) (afterwards the rows are device-side and trusted: the kernels clamp)."""
+
+    def __init__(self, question_rows, question_cu, candidate_rows, answers, device=None, n_table: Optional[int] = None):
+        rows = np.ascontiguousarray(np.asarray(question_rows).reshape(-1), dtype=np.int32)
+        cu = np.asarray(question_cu, dtype=np.int64).reshape(-1)
+        cand = np.ascontiguousarray(np.asarray(candidate_rows), dtype=np.int32)
+        ans = np.asarray(answers, dtype=np.int64).reshape(-1)
+        n = cu.size - 1
+        if n < 1 or cand.ndim != 2 or cand.shape[0] != n or cand.shape[1] < 1 or ans.size != n:
+            raise ValueError(f"question_cu [{cu.size}], candidate_rows {cand.shape}, answers [{ans.size}] are not [N + 1], [N, C], [N] with N, C >= 1")
+        if int(cu[0]) != 0 or bool((np.diff(cu) < 0).any()) or int(cu[-1]) != rows.size:
+            raise ValueError("question_cu must start at 0, be non-decreasing and end at len(question_rows)")
+        if int(ans.min()) < 0 or int(ans.max()) >= cand.shape[1]:
+            raise ValueError(f"answers span [{int(ans.min())}, {int(ans.max())}]: outside [0, {cand.shape[1]})")
+        if n_table is not None:
+            lo = min(int(rows.min()) if rows.size else 0, int(cand.min()))
+            hi = max(int(rows.max()) if rows.size else 0, int(cand.max()))
+            if lo < 0 or hi >= n_table:
+                raise ValueError(f"rows span [{lo}, {hi}]: outside the table's [0, {n_table})")
+        self.n_questions, self.n_candidates = int(n), int(cand.shape[1])
+        self.question_cu = cu                                   # host copy: where a batch's item_index starts and ends
+        self.max_items = int(np.diff(cu).max())
+        self.device = _device(device)
+        self.dev: Optional[Dict[str, torch.Tensor]] = None
+        if self.device is not None:
+            target = cand[np.arange(n), ans]
+            self.dev = {"question_rows": _upload(rows, self.device), "question_cu": _upload(cu, self.device),
+                        "candidate_rows": _upload(cand, self.device).view(n, -1), "target_rows": _upload(target, self.device),
+                        "answers": torch.from_numpy(ans).to(self.device)}
+
+    def __len__(self) -> int:
+        return self.n_questions
+
+    def steps(self, batch_size: int) -> int:
+        return math.ceil(self.n_questions / batch_size)
+
+    def batches(self, batch_size: int, rank: int = 0, world: int = 1) -> Iterator[dict]:
+        """Index-form FITB batches of `batch_size` consecutive questions (the last one ragged): {'input_dict': {'task' (the CIR class),
+        'item_index', 'cu_seqlens' [B + 1] starting at 0, 'target_item_index' [B]}, 'candidate_item_index' int32 [B, C], 'answer_index'
+        long [B]}, all on the device.  rank r of `world` takes batches r, r + world, ... (a test split needs no padding: the ranks may hold
+        different batch counts, FITBEvaluator sums the counts)."""
+        if self.dev is None:
+            raise L.OfxError("FITBDeviceSplit has no HIP device: its batches are device views, there is no CPU path")
+        if batch_size < 1 or not 0 <= rank < world:
+            raise ValueError(f"batch_size = {batch_size}, rank = {rank}, world = {world}")
+        d = self.dev
+        for step in range(rank, self.steps(batch_size), world):
+            q0, q1 = step * batch_size, min((step + 1) * batch_size, self.n_questions)
+            i0, i1 = int(self.question_cu[q0]), int(self.question_cu[q1])
+            cu = d["question_cu"][q0:q1 + 1]
+            yield {"input_dict": {"task": OutfitComplementaryItemRetrievalTask, "item_index": d["question_rows"][i0:i1], "cu_seqlens": cu - cu[:1],
+                                  "target_item_index": d["target_rows"][q0:q1]},
+                   "candidate_item_index": d["candidate_rows"][q0:q1], "answer_index": d["answers"][q0:q1]}
 
 
 class CIRDeviceDataset:

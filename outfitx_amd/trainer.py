@@ -26,6 +26,10 @@ Differences from DDP by design (MI355X / xGMI, point-to-point links, per-link bo
 pass on HIP tensors) -> / accumulation_steps -> the hand-written CIR backward, then the identical boundary step.  Both trainers share
 `FlatGradTrainer` below (arena, gradient sink, per-layer slices, armed layer events, overlapped reduction, clip, AdamW, OneCycleLR).
 
+Evaluation: `CPTrainer.valid_epoch` / `test_epoch` (compatibility_prediction_trainer.py:131-239), `CIRTrainer.valid_epoch` (loss + grouped
+recall@k) and `FITBEvaluator` (fill_in_the_blank_trainer.py:37-64) run in eval mode without gradients, touch neither parameters nor
+optimizer, scheduler or arena, and sum their metrics over the ranks.
+
 The loop itself is device-agnostic torch host code (the CPU tests drive it with a stub module over gloo); the model it is
 meant for, `outfitx_amd.OutfitX` in train() mode, only runs on a HIP device.
 """
@@ -149,9 +153,12 @@ def cp_metrics(y_hats: torch.Tensor, labels: torch.Tensor) -> Dict[str, float]:
     return {"Accuracy": float((pred == lab).float().mean()), "Precision": precision, "Recall": recall, "F1": f1, "AUC": auc}
 
 
-def gather_epoch(local_y: torch.Tensor, local_labels: torch.Tensor, local_loss: torch.Tensor, batch_count: int, group=None):
+def gather_epoch(local_y: torch.Tensor, local_labels: torch.Tensor, local_loss: torch.Tensor, batch_count: float, group=None):
     """cp_trainer:372-405: all-gather every rank's epoch logits / labels / summed loss -> global metrics on every rank.
-    Ranks may hold different sample counts (the reference assumes equal ones): sizes are gathered first."""
+    Ranks may hold different sample counts (the reference assumes equal ones): sizes are gathered first.
+    'loss' = mean over the ranks of their summed losses / batch_count.  batch_count is the number of batches PER RANK: the reference
+    passes len(dataloader), the same on every rank.  Where the ranks hold different counts, pass all ranks' batches / world size - it
+    need not be whole (CPTrainer.valid_epoch does): the result is then the summed loss of all ranks / the number of all batches."""
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     if world > 1:
         n = torch.tensor([local_y.numel()], dtype=torch.int64, device=local_y.device)
@@ -355,6 +362,112 @@ class CPTrainer(FlatGradTrainer):
             loss, y, lab = self.micro_step(batch, step)
             total += loss; ys.append(y); ls.append(lab); n += 1
         return gather_epoch(torch.cat(ys), torch.cat(ls), total, max(n, 1), self.group)
+
+    def _eval_epoch(self, batches: Iterable[dict], with_loss: bool) -> Dict[str, float]:
+        """This rank's batches in eval mode without gradients -> gather_epoch over the ranks.  Only the model's forward and the loss run:
+        parameters, optimizer state, scheduler and the gradient arena are not touched; the model's training flag is left as it was."""
+        was_training = self.model.training
+        self.model.eval()
+        dev = self.grads.flat.device
+        total = torch.zeros((), dtype=torch.float32, device=dev)
+        ys: List[torch.Tensor] = []; ls: List[torch.Tensor] = []
+        n = 0
+        try:
+            with torch.no_grad():
+                for batch in batches:
+                    labels = batch["label"].to(dev, non_blocking=True)
+                    y_hat = self.model(**self._inputs(batch)).squeeze(dim=-1)
+                    if with_loss:
+                        total += self.loss_fn(y_hat=y_hat, y_true=labels).detach()
+                    ys.append(y_hat.detach()); ls.append(labels); n += 1
+                # gather_epoch returns mean over the ranks of the summed losses / batch_count: the reference's formula, whose ranks hold
+                # equal batch counts.  With batches per rank = all batches / world it is the summed loss / number of batches whatever
+                # the ranks hold - one small all-reduce for the count
+                batch_count = float(max(n, 1))
+                if with_loss and self._world() > 1:
+                    count = torch.tensor([n], dtype=torch.int64, device=dev)
+                    dist.all_reduce(count, op=dist.ReduceOp.SUM, group=self.group)
+                    batch_count = max(int(count), 1) / self._world()
+                empty = torch.empty(0, dtype=torch.float32, device=dev)            # a rank without batches still joins the all-gathers
+                return gather_epoch(torch.cat(ys) if ys else empty, torch.cat(ls) if ls else empty, total, batch_count, self.group)
+        finally:
+            self.model.train(was_training)
+
+    def valid_epoch(self, batches: Iterable[dict]) -> Dict[str, float]:
+        """CompatibilityPredictionTrainer.valid_epoch (compatibility_prediction_trainer.py:131-182, without checkpointing and logging):
+        eval mode, no gradients, per batch the forward and the loss; at the end the logits, labels and summed loss of all ranks ->
+        {'loss': summed batch loss / number of batches, 'Accuracy', 'Precision', 'Recall', 'F1', 'AUC'} (the reference keeps its
+        `best_AUC` checkpoint from this).  Dense or indexed batches, as train_epoch takes them."""
+        return self._eval_epoch(batches, with_loss=True)
+
+    def test_epoch(self, batches: Iterable[dict]) -> Dict[str, float]:
+        """CompatibilityPredictionTrainer.test (:197-239, without the checkpoint load): valid_epoch without the loss ->
+        {'Accuracy', 'Precision', 'Recall', 'F1', 'AUC'}.  The reference tests on one rank; here every rank may hold a share of the split,
+        the metrics are those of all ranks' logits."""
+        metrics = self._eval_epoch(batches, with_loss=False)
+        del metrics["loss"]
+        return metrics
+
+
+class FITBEvaluator:
+    """The fill-in-the-blank test (FillInTheBlankTrainer.test, fill_in_the_blank_trainer.py:37-64): per batch y_hat = model(question),
+    the candidate nearest to it in L2, and a hit when that is `answer_index`; `test_epoch` -> {'Accuracy': correct / total}.
+
+    Batches are the FITB collate dicts.  Dense ones ({'input_dict', 'candidate_item_embedding' [B, C, D], 'answer_index' [B]}) go through
+    `engine.fitb_argmin`.  Index-form ones ({'input_dict', 'candidate_item_index' int32 [B, C], 'answer_index'}:
+    processor.OutfitXIndexedProcessor(..., fitb_candidates='index') or sampler.FITBDeviceSplit) go through `engine.fitb_argmin_indexed`, which
+    reads the candidates straight from the embedding table - `embedding_table=` here, else `model.embedding_table` - and adds its hits to
+    ONE device counter that is read once, after the last batch: with FITBDeviceSplit batches an epoch runs without a host synchronisation.
+    Both forms can be mixed.  `argmin_fn(y_hat, cand [B, C, D]) -> idx [B]` replaces the HIP calls (index batches are then gathered from the
+    table); it is what a CPU run needs.  (correct, total) are summed over the ranks of `group` with one all-reduce: unlike the reference,
+    which refuses a distributed test, every rank may hold a share of the questions."""
+
+    def __init__(self, model: torch.nn.Module, embedding_table: Optional[torch.Tensor] = None, group=None, argmin_fn: Optional[Callable] = None):
+        self.model, self.group, self.argmin_fn = model, group, argmin_fn
+        p = next(model.parameters(), None)
+        self.device = p.device if p is not None else torch.device("cpu")
+        self.embedding_table = None if embedding_table is None else embedding_table.to(self.device)
+
+    def _table(self) -> torch.Tensor:
+        table = self.embedding_table if self.embedding_table is not None else getattr(self.model, "embedding_table", None)
+        if table is None:
+            raise ValueError("index-form FITB batches need an embedding table: pass embedding_table= or call model.set_embedding_table()")
+        return table
+
+    def test_epoch(self, batches: Iterable[dict]) -> Dict[str, float]:
+        dev = self.device
+        was_training = self.model.training
+        self.model.eval()
+        hits = torch.zeros(1, dtype=torch.int32, device=dev)          # every batch adds into it; read once below
+        total = 0
+        try:
+            with torch.no_grad():
+                for batch in batches:
+                    y_hat = self.model(**{k: (v if k == "task" else v.to(dev, non_blocking=True)) for k, v in batch["input_dict"].items()})
+                    answer = batch["answer_index"].to(dev, non_blocking=True).reshape(-1)
+                    total += answer.numel()
+                    indexed = "candidate_item_index" in batch
+                    if indexed and self.argmin_fn is None:
+                        from .engine import fitb_argmin_indexed
+                        fitb_argmin_indexed(self._table(), batch["candidate_item_index"], y_hat, answer=answer, n_correct=hits)
+                        continue
+                    if indexed:
+                        cand = self._table()[:, : y_hat.shape[-1]][batch["candidate_item_index"].to(dev).long()]
+                    else:
+                        cand = batch["candidate_item_embedding"].to(dev, non_blocking=True)
+                    if self.argmin_fn is not None:
+                        idx = self.argmin_fn(y_hat, cand)
+                    else:
+                        from .engine import fitb_argmin
+                        idx = fitb_argmin(y_hat, cand)
+                    hits += (idx.reshape(-1) == answer).sum().to(torch.int32)
+                counts = torch.cat([hits.to(torch.int64), torch.tensor([total], dtype=torch.int64, device=dev)])
+                if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1:
+                    dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.group)
+                correct, total = (int(v) for v in counts.tolist())
+        finally:
+            self.model.train(was_training)
+        return {"Accuracy": correct / total if total else 0.0}
 
 
 class CIRTrainer(FlatGradTrainer):
