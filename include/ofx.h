@@ -503,6 +503,44 @@ int ofx_colsum(const void* x, int x_kind, int ld, const int* gather, const float
                int C, int valid, int M, const int* m_dev, int accumulate, int op_dtype, void* ws, size_t ws_bytes, ofx_stream stream);
 int ofx_head_bwd(const float* dlogits, const float* w, const int* cu, float* dX, void* dXb, float* db, int B, int D, float dropout_p,
                  unsigned seed, int head_site, int below_site, int accumulate, int op_dtype, ofx_stream stream);
+/* The kernels of the towers' LayerNorm-fold chain (knob 6), one call each, through the launchers the ViT and text layers use.  The residual
+ * stream is an operand-type pair (hi at xb, lo = x - hi at xlo); no LayerNorm is materialised.  NULL required pointers, misaligned pointers
+ * and an op_dtype that is not OFX_BF16 / OFX_F16 are OFX_EINVAL, an unsupported shape OFX_ESHAPE; a refused call launches nothing.
+ * w_form names the weight operand: 0 = plain W [N, K]; 1 = split W2 [N, 2K], row n = [hi(K) | lo(K)] (ofx_gemm_w2); 2 = split plus the fp8
+ * copy (W8, scale8) of its lo half (ofx_gemm_w2f8; f16 only, N and K multiples of 128).  W8 / scale8 are ignored for w_form 0 and 1.  The
+ * kernel is chosen as for ofx_gemm / ofx_gemm_w2 / ofx_gemm_w2f8: knob 2 and knob 11 apply.
+ *
+ *   ofx_gemm_fold_producer: the out-proj / fc2 form.  v = fp32(A W^T + bias) + (fp32(xb) + fp32(xlo)), per element; xb := cast(v),
+ *     xlo := cast(v - xb), both [M, N] with row stride N, updated IN PLACE; stat_part [M, N / 64, 2] fp32 = per row and 64-column segment
+ *     (sum of v, sum of v^2), of the fp32 v before the split.  Rows at or past M of xb, xlo and stat_part are not touched.  N a multiple
+ *     of 128 (OFX_ESHAPE); act must be OFX_ACT_NONE and resid NULL - the stream is the residual - else OFX_EINVAL (they are taken so that
+ *     the launcher's refusal can be reached).  A, W, W8, xb, xlo, bias 16-byte aligned, stat_part 8-byte aligned.
+ *   ofx_gemm_fold: the qkv / fc1 form for w_form 0 and 1 (w_form 2 is ofx_gemm_w2f8_fold, which stays):  C [M, ldc >= N] operand type =
+ *     act((A W^T - col_sum[n] mean[m]) rstd[m] + bias[n]), (mean, rstd)[m] = row_stat[2 m stat_ld], [2 m stat_ld + 1]; columns N .. ldc - 1
+ *     are not written.  W holds the gamma-scaled rows and col_sum, bias what ofx_fold_pack returns.  stat_ld >= 1 (with lda = stat_ld K:
+ *     every stat_ld-th row of a stream, the pruned last ViT layer).  row_stat and col_sum are required (OFX_EINVAL); no residual.
+ *   ofx_stats_finalize: stat [rows, 2] = (mean, rstd) from stat_part [rows, slots, 2]: s = sum of the slots' sums, q = of their sums of
+ *     squares, in slot order; mean = s / W, rstd = rsqrt(max(q / W - mean^2, 0) + eps), all fp32 - ONE pass: the relative error of rstd
+ *     grows as 2^-24 E[x^2] / Var[x] (tests/test_gpu_fold_ops.py holds the kernel to the derived bound).
+ *   ofx_row_stats_cast: x fp32 [rows, W] -> xb = cast(x), xlo = cast(x - xb), stat [rows, 2] = two-pass (mean, rstd) of x's rows.  W % 4 == 0.
+ *   ofx_fold_pack: w fp32 [N, K], gamma, beta [K], bias [N] -> wf [N, K] = cast(fp32(w gamma)), or with split != 0 wf [N, 2K] = [hi | lo],
+ *     lo = cast(fp32(w gamma) - hi); col_sum [N] = the fp32 sum of the ROUNDED values wf holds (hi and lo); bias_f [N] = bias + sum_k beta[k] w[n, k].
+ *   ofx_vit_embed_ln: row n S + t = LN((t == 0 ? cls : patch_out[n (S - 1) + t - 1]) + pos[t]) gamma + beta, patch_out fp32 [N (S - 1), D],
+ *     cls, gamma, beta [D], pos [S, D].  Writes EITHER x fp32 [N S, D], OR the stream form of the same values: xb = cast(x), xlo = cast(x - xb)
+ *     and stat [N S, 2] = two-pass (mean, rstd) of x's rows.  Passing both or neither is OFX_EINVAL.  D in {512, 768, 1024} (OFX_ESHAPE).
+ *   ofx_gather_hilo: dst fp32 [rows, W] = fp32(hi[idx[r]]) + fp32(lo[idx[r]]), hi and lo operand type [*, W], W % 4 == 0.  idx lives on the
+ *     device and is not checked: every entry must name a row of hi / lo. */
+int ofx_gemm_fold_producer(const void* A, const void* W, const void* W8, const void* scale8, void* xb, void* xlo, float* stat_part, const float* bias,
+                           const float* resid, int M, int N, int K, int lda, int ldr, int act, int w_form, int op_dtype, ofx_stream stream);
+int ofx_gemm_fold(const void* A, const void* W, void* C, const float* bias, const float* row_stat, int stat_ld, const float* col_sum, int M, int N, int K,
+                  int lda, int ldc, int act, int w_form, int op_dtype, ofx_stream stream);
+int ofx_stats_finalize(const float* stat_part, int slots, int W, float eps, float* stat, int rows, ofx_stream stream);
+int ofx_row_stats_cast(const float* x, void* xb, void* xlo, float* stat, int rows, int W, float eps, int op_dtype, ofx_stream stream);
+int ofx_fold_pack(const float* w, const float* gamma, const float* beta, const float* bias, void* wf, float* col_sum, float* bias_f, int N, int K, int split,
+                  int op_dtype, ofx_stream stream);
+int ofx_vit_embed_ln(const float* patch_out, const float* cls, const float* pos, const float* gamma, const float* beta, float* x, void* xb, void* xlo,
+                     float* stat, int N, int S, int D, float eps, int op_dtype, ofx_stream stream);
+int ofx_gather_hilo(const void* hi, const void* lo, const int* idx, float* dst, int rows, int W, int op_dtype, ofx_stream stream);
 int ofx_layernorm(const float* x, const int* row_idx, const float* gamma, const float* beta, void* y, int rows,
                   int D, int ldy, int out_kind, int op_dtype, float eps, ofx_stream stream);
 int ofx_attention(const void* qkv, void* out, const int64_t* key_mask, int nseq, int seq_len, int n_head, int ld,

@@ -192,6 +192,13 @@ SIGNATURES = {
     "ofx_colsum_ws": (_sz, [_i]),
     "ofx_colsum": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _sz, _vp]),
     "ofx_head_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, C.c_uint, _i, _i, _i, _i, _vp]),
+    "ofx_gemm_fold_producer": (_i, [_vp] * 9 + [_i] * 8 + [_vp]),
+    "ofx_gemm_fold": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "ofx_stats_finalize": (_i, [_vp, _i, _i, _f, _vp, _i, _vp]),
+    "ofx_row_stats_cast": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp]),
+    "ofx_fold_pack": (_i, [_vp] * 7 + [_i, _i, _i, _i, _vp]),
+    "ofx_vit_embed_ln": (_i, [_vp] * 9 + [_i, _i, _i, _f, _i, _vp]),
+    "ofx_gather_hilo": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "ofx_layernorm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "ofx_attention": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "ofx_fused_qkv_attention": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),

@@ -1540,6 +1540,73 @@ extern "C" int ofx_head_bwd(const float* dlogits, const float* w, const int* cu,
     return ofx_launch_cp_head_bwd(dlogits, w, cu, dX, dXb, db, B, D, op_dtype, head_site < 0 ? none : make_drop(dropout_p, seed, (unsigned)head_site),
                                   below_site < 0 ? none : make_drop(dropout_p, seed, (unsigned)below_site), (hipStream_t)stream, accumulate ? 1 : 0);
 }
+// the towers' LayerNorm-fold chain, one call each: thin wrappers over the launchers the ViT and text layers use
+static int fold_gemm_args(GemmArgs& g, const char* who, const void* A, const void* W, const void* W8, const void* scale8, int K, int w_form, int& op_dtype) {
+    OFX_REQUIRE(w_form >= 0 && w_form <= 2 && op_dtype_ok(op_dtype) && (w_form != 2 || op_dtype == OFX_F16), OFX_EINVAL,
+                "%s: w_form = %d (0 plain, 1 split, 2 split + fp8 lo copy, f16 only), op_dtype = %d", who, w_form, op_dtype);
+    OFX_REQUIRE(A && W && (w_form != 2 || (W8 && scale8)), OFX_EINVAL, "%s: NULL operand", who);
+    g.A = A; g.W = W; g.K = w_form ? 2 * K : K;
+    if (w_form) g.a_wrap = K;
+    if (w_form == 2) { g.W8 = W8; g.w8_scale = scale8; }
+    return OFX_OK;
+}
+extern "C" int ofx_gemm_fold_producer(const void* A, const void* W, const void* W8, const void* scale8, void* xb, void* xlo, float* stat_part,
+                                      const float* bias, const float* resid, int M, int N, int K, int lda, int ldr, int act, int w_form, int op_dtype,
+                                      ofx_stream stream) {
+    GemmArgs g = op_gemm(nullptr, nullptr, xb, bias, resid, M, N, K, lda, N, ldr, act, OFX_OUT_OP);
+    TRY(fold_gemm_args(g, "gemm_fold_producer", A, W, W8, scale8, K, w_form, op_dtype));
+    OFX_REQUIRE(xb && xlo && stat_part, OFX_EINVAL, "gemm_fold_producer: xb, xlo and stat_part are all required");
+    OFX_REQUIRE(aligned_to(15, {A, W, W8, xb, xlo, bias, resid}) && aligned_to(7, {stat_part}), OFX_EINVAL,
+                "gemm_fold_producer: A, W, W8, xb, xlo, bias must be 16-byte aligned, stat_part 8-byte aligned");
+    g.xb_out = xb; g.xlo = xlo; g.stat_part = stat_part;
+    return ofx_launch_gemm(g, op_dtype, (hipStream_t)stream);
+}
+extern "C" int ofx_gemm_fold(const void* A, const void* W, void* C, const float* bias, const float* row_stat, int stat_ld, const float* col_sum,
+                             int M, int N, int K, int lda, int ldc, int act, int w_form, int op_dtype, ofx_stream stream) {
+    GemmArgs g = op_gemm(nullptr, nullptr, C, bias, nullptr, M, N, K, lda, ldc, 0, act, OFX_OUT_OP);
+    OFX_REQUIRE(w_form != 2, OFX_EINVAL, "gemm_fold: w_form 2 is ofx_gemm_w2f8_fold");
+    TRY(fold_gemm_args(g, "gemm_fold", A, W, nullptr, nullptr, K, w_form, op_dtype));
+    OFX_REQUIRE(C && row_stat && col_sum, OFX_EINVAL, "gemm_fold: C, row_stat and col_sum are required");
+    OFX_REQUIRE(aligned_to(15, {A, W, C, bias, col_sum}) && aligned_to(7, {row_stat}), OFX_EINVAL,
+                "gemm_fold: A, W, C, bias and col_sum must be 16-byte aligned, row_stat 8-byte aligned");
+    OFX_REQUIRE(stat_ld >= 1, OFX_ESHAPE, "gemm_fold: stat_ld = %d; needs >= 1", stat_ld);
+    g.row_stat = row_stat; g.col_sum = col_sum; g.stat_ld = stat_ld;
+    return ofx_launch_gemm(g, op_dtype, (hipStream_t)stream);
+}
+extern "C" int ofx_stats_finalize(const float* stat_part, int slots, int W, float eps, float* stat, int rows, ofx_stream stream) {
+    OFX_REQUIRE(stat_part && stat && aligned_to(7, {stat_part, stat}), OFX_EINVAL, "stats_finalize: stat_part and stat are required, 8-byte aligned");
+    OFX_REQUIRE(rows > 0 && slots > 0 && W > 0, OFX_ESHAPE, "stats_finalize: rows = %d, slots = %d, W = %d; all must be positive", rows, slots, W);
+    return ofx_launch_stats_finalize(stat_part, slots, W, eps, stat, rows, (hipStream_t)stream);
+}
+extern "C" int ofx_row_stats_cast(const float* x, void* xb, void* xlo, float* stat, int rows, int W, float eps, int op_dtype, ofx_stream stream) {
+    OFX_REQUIRE(x && xb && xlo && stat && op_dtype_ok(op_dtype), OFX_EINVAL, "row_stats_cast: bad argument");
+    OFX_REQUIRE(aligned_to(15, {x}) && aligned_to(7, {xb, xlo, stat}), OFX_EINVAL, "row_stats_cast: x must be 16-byte aligned, xb, xlo and stat 8-byte aligned");
+    OFX_REQUIRE(rows > 0 && W > 0 && W % 4 == 0, OFX_ESHAPE, "row_stats_cast: rows = %d, W = %d; needs rows >= 1, W a positive multiple of 4", rows, W);
+    return ofx_launch_row_stats_cast(x, xb, xlo, stat, rows, W, eps, op_dtype, (hipStream_t)stream);
+}
+extern "C" int ofx_fold_pack(const float* w, const float* gamma, const float* beta, const float* bias, void* wf, float* col_sum, float* bias_f, int N, int K,
+                             int split, int op_dtype, ofx_stream stream) {
+    OFX_REQUIRE(w && gamma && beta && bias && wf && col_sum && bias_f && op_dtype_ok(op_dtype), OFX_EINVAL, "fold_pack: bad argument");
+    OFX_REQUIRE(aligned_to(3, {w, gamma, beta, bias, col_sum, bias_f}) && aligned_to(1, {wf}), OFX_EINVAL, "fold_pack: misaligned pointer");
+    OFX_REQUIRE(N > 0 && K > 0, OFX_ESHAPE, "fold_pack: N = %d, K = %d; both must be positive", N, K);
+    return ofx_launch_fold_pack(w, gamma, beta, bias, wf, col_sum, bias_f, N, K, op_dtype, (hipStream_t)stream, split ? 1 : 0);
+}
+extern "C" int ofx_vit_embed_ln(const float* patch_out, const float* cls, const float* pos, const float* gamma, const float* beta, float* x, void* xb,
+                                void* xlo, float* stat, int N, int S, int D, float eps, int op_dtype, ofx_stream stream) {
+    OFX_REQUIRE(patch_out && cls && pos && gamma && beta && op_dtype_ok(op_dtype), OFX_EINVAL, "vit_embed_ln: bad argument");
+    OFX_REQUIRE(x ? !xb && !xlo && !stat : xb && xlo && stat, OFX_EINVAL, "vit_embed_ln: writes either x or (xb, xlo, stat)");
+    OFX_REQUIRE(aligned_to(15, {patch_out, cls, pos, gamma, beta, x}) && aligned_to(7, {xb, xlo, stat}), OFX_EINVAL,
+                "vit_embed_ln: the fp32 arrays must be 16-byte aligned, xb, xlo and stat 8-byte aligned");
+    OFX_REQUIRE(N > 0 && S > 0 && (long long)N * S <= INT_MAX, OFX_ESHAPE, "vit_embed_ln: N = %d, S = %d", N, S);
+    return ofx_launch_vit_embed_ln(patch_out, cls, pos, gamma, beta, x, N, S, D, eps, (hipStream_t)stream, xb, stat, op_dtype, xlo);
+}
+extern "C" int ofx_gather_hilo(const void* hi, const void* lo, const int* idx, float* dst, int rows, int W, int op_dtype, ofx_stream stream) {
+    OFX_REQUIRE(hi && lo && idx && dst && op_dtype_ok(op_dtype), OFX_EINVAL, "gather_hilo: bad argument");
+    OFX_REQUIRE(aligned_to(7, {hi, lo}) && aligned_to(15, {dst}) && aligned_to(3, {idx}), OFX_EINVAL,
+                "gather_hilo: hi and lo must be 8-byte aligned, dst 16-byte aligned");
+    OFX_REQUIRE(rows > 0 && W > 0 && W % 4 == 0, OFX_ESHAPE, "gather_hilo: rows = %d, W = %d; needs rows >= 1, W a positive multiple of 4", rows, W);
+    return ofx_launch_gather_hilo(hi, lo, idx, dst, rows, W, op_dtype, (hipStream_t)stream);
+}
 extern "C" int ofx_layernorm(const float* x, const int* row_idx, const float* gamma, const float* beta, void* y, int rows,
                              int D, int ldy, int out_kind, int op_dtype, float eps, ofx_stream stream) {
     LnArgs a{x, row_idx, gamma, beta, y, rows, D, ldy, out_kind, eps};

@@ -457,7 +457,11 @@ __global__ __launch_bounds__(256) void fold_pack_kernel(const float* Wsrc, const
         float cs = 0.f, bb = 0.f;
         for (int k = lane; k < K; k += 64) {
             const float wv = Wsrc[(size_t)n * K + k];
-            const float wg = wv * gamma[k];
+            float wg = wv * gamma[k];
+            // The fp32 product is a value of its own: hi is ITS cast and lo is taken from IT.  Left to the compiler, the multiplication and the
+            // f16 conversion become one mixed-precision instruction that rounds the exact product once (a different hi for ~1 weight in 10^4,
+            // bf16 has no such instruction); the empty statement keeps them apart.  tests/test_gpu_fold_ops.py holds Wf to cast(fp32(w gamma)).
+            asm volatile("" : "+v"(wg));
             const T r = (T)wg;
             Wf[(size_t)n * ld + k] = r;
             cs += (float)r;
