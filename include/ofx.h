@@ -198,10 +198,24 @@ int ofx_topk_merge(const int64_t* idx_in, const float* dist_in, int parts, int n
  * vertical, 8-bit intermediate — bit-exact), centre crop size x size, x 1/255, (x - mean) / std -> out [N, 3, size, size] fp32
  * (device), equal to the host pipeline bit for bit.  src: device buffer holding the N uint8 images row-major with `channels`
  * (3 = RGB interleaved, 1 = grey, replicated) at byte offsets[i]; offsets / heights / widths are HOST arrays.  RGB pixels are
- * fetched as unaligned dwords: src must stay readable 1 byte past the end of every image (give the buffer >= 4 bytes of slack). */
+ * fetched as unaligned dwords: src must stay readable 1 byte past the end of every image (give the buffer >= 4 bytes of slack);
+ * that byte never reaches a result, and offsets need no alignment.  mean / stdv: HOST arrays of 3 floats. */
 size_t ofx_clip_preprocess_ws(const int* heights, const int* widths, int N, int channels, int size);
 int ofx_clip_preprocess(const uint8_t* src, const long long* offsets, const int* heights, const int* widths, int N, int channels, int size,
                         const float* mean, const float* stdv, float* out, void* ws, size_t ws_bytes, ofx_stream stream);
+/* Op-level forms of the two kernels that build the patch-embedding GEMM's operand (tests and tools; the model path does not go through them).
+ *   ofx_clip_preprocess_patches: the same resize / crop / normalise, the vertical pass writing `patches` [N (size / patch)^2, 3 patch^2] operand
+ *     type (device) instead of fp32 pixels: row n g^2 + py g + px (g = size / patch), column c patch^2 + ky patch + kx = cast(the fp32 value
+ *     ofx_clip_preprocess gives pixel (n, c, py patch + ky, px patch + kx)) - the im2col of Conv2d(3, width, patch, stride patch) in its
+ *     weight.reshape(width, -1) column order.  mean / stdv: HOST arrays of 3 floats (as for ofx_clip_preprocess); workspace: ofx_clip_preprocess_ws.
+ *     A NULL pointer or op_dtype other than OFX_BF16 / OFX_F16 is OFX_EINVAL; patch <= 0, size % patch != 0 and what ofx_clip_preprocess refuses
+ *     are OFX_ESHAPE; a short workspace OFX_EWORKSPACE.  A refused call launches nothing.
+ *   ofx_patchify: the pixel route's counterpart: pixels fp32 [N, 3, img, img] (device, 16-byte aligned) -> out [N (img / patch)^2, 3 patch^2]
+ *     operand type (16-byte aligned), same layout, out = cast(pixel).  img % patch == 0, img % 8 == 0, patch % 8 == 0, N >= 1 (OFX_ESHAPE). */
+int ofx_clip_preprocess_patches(const uint8_t* src, const long long* offsets, const int* heights, const int* widths, int N, int channels, int size,
+                                int patch, const float* mean, const float* stdv, void* patches, int op_dtype, void* ws, size_t ws_bytes,
+                                ofx_stream stream);
+int ofx_patchify(const float* pixels, void* out, int N, int img, int patch, int op_dtype, ofx_stream stream);
 /* The two fused: decoded uint8 images -> image embeddings (clip_image_encoder.py:66-76 in one call).  The preprocessor's
  * vertical pass writes the operand-type im2col rows of the patch-embedding GEMM directly, so neither the fp32 pixel_values
  * tensor (0.6 MB / image) nor the patchify pass exists; results equal ofx_clip_preprocess + ofx_vit_b32_fwd bit for bit.

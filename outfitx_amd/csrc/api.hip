@@ -1607,6 +1607,20 @@ extern "C" int ofx_gather_hilo(const void* hi, const void* lo, const int* idx, f
     OFX_REQUIRE(rows > 0 && W > 0 && W % 4 == 0, OFX_ESHAPE, "gather_hilo: rows = %d, W = %d; needs rows >= 1, W a positive multiple of 4", rows, W);
     return ofx_launch_gather_hilo(hi, lo, idx, dst, rows, W, op_dtype, (hipStream_t)stream);
 }
+extern "C" int ofx_clip_preprocess_patches(const uint8_t* src, const long long* offsets, const int* heights, const int* widths, int N, int channels, int size,
+                                           int patch, const float* mean, const float* stdv, void* patches, int op_dtype, void* ws, size_t ws_bytes,
+                                           ofx_stream stream) {
+    OFX_REQUIRE(src && offsets && heights && widths && mean && stdv && patches && ws && op_dtype_ok(op_dtype), OFX_EINVAL,
+                "clip_preprocess_patches: bad argument (a NULL pointer or op_dtype = %d)", op_dtype);
+    OFX_REQUIRE(patch > 0 && size > 0 && size % patch == 0, OFX_ESHAPE, "clip_preprocess_patches: size=%d patch=%d", size, patch);
+    return ofx_preprocess_to(src, offsets, heights, widths, N, channels, size, mean, stdv, nullptr, patches, patch, op_dtype, ws, ws_bytes, (hipStream_t)stream);
+}
+extern "C" int ofx_patchify(const float* pixels, void* out, int N, int img, int patch, int op_dtype, ofx_stream stream) {
+    OFX_REQUIRE(pixels && out && op_dtype_ok(op_dtype), OFX_EINVAL, "patchify: bad argument (a NULL pointer or op_dtype = %d)", op_dtype);
+    OFX_REQUIRE(aligned_to(15, {pixels, out}), OFX_EINVAL, "patchify: pixels and out must be 16-byte aligned");
+    OFX_REQUIRE(N > 0 && img > 0 && patch > 0, OFX_ESHAPE, "patchify: N = %d, img = %d, patch = %d; all must be positive", N, img, patch);
+    return ofx_launch_patchify(pixels, out, N, img, patch, op_dtype, (hipStream_t)stream);
+}
 extern "C" int ofx_layernorm(const float* x, const int* row_idx, const float* gamma, const float* beta, void* y, int rows,
                              int D, int ldy, int out_kind, int op_dtype, float eps, ofx_stream stream) {
     LnArgs a{x, row_idx, gamma, beta, y, rows, D, ldy, out_kind, eps};
