@@ -1,6 +1,7 @@
 // C ABI of libofx_hip.so: handle, weight packing and the launch sequences of the scoring path.
 // Everything here is host code; it only enqueues work on the caller's stream (no syncs, no
-// allocation on the launch path — the weight arenas are allocated by the pack calls).
+// allocation on the launch path — a pack call sizes its weight arena by walking the layout (ofx_weights.h), allocates it once and
+// reuses it, pointers unchanged, on every re-pack).
 #include <stdarg.h>
 #include <string.h>
 
@@ -9,7 +10,7 @@
 #include <mutex>
 #include <cstring>
 
-#include "ofx_common.h"
+#include "ofx_weights.h"
 
 static thread_local char g_err[512] = "";
 void ofx_set_error(const char* fmt, ...) {
@@ -137,121 +138,6 @@ extern "C" int ofx_profile_read(double* ms, double* flops, long long* launches) 
     return OFX_OK;
 }
 
-int ofx_launch_transpose_cast(const float* src, void* dst, int R, int C, int ldd, int op_dtype, hipStream_t s, void* row_dst = nullptr, int ld_row = 0);
-size_t ofx_colsum_part_floats(int C);
-int ofx_launch_colsum(const void* x, int x_kind, int ld, const int* gather, const float* row_scale, float* out0, float* out1, float* out2, int seg,
-                      float* part, int C, const int* m_dev, int M, int op_dtype, hipStream_t s, int valid = 0, int accumulate = 0);
-size_t ofx_ln_bwd_part_floats(int D);
-int ofx_launch_row_map(const int* cu, int* map, int B, int M, hipStream_t s);
-int ofx_launch_ln_bwd(const float* dy, const float* x, const float* stats, const float* gamma, const float* add, const int* add_map, float* dx_out, void* dx_op,
-                      float* dgamma, float* dbeta, float* dcols, float* part, int D, const int* m_dev, int M, int op_dtype, const DropArgs& drop, hipStream_t s,
-                      int accumulate = 0);
-int ofx_launch_set_attention_bwd(const void* qkv, const float* d_o, void* dqkv, const int* cu, int nseq, int n_head, int D, int max_len,
-                                 float scale, int op_dtype, const DropArgs& drop, int only_row0, hipStream_t s);
-int ofx_launch_set_attention_bwd_mfma(const void* qkv, const float* d_o, void* dqkv, const int* cu, int nseq, int n_head, int D, int max_len,
-                                      float scale, int op_dtype, const DropArgs& drop, int only_row0, hipStream_t s);
-int ofx_launch_drop_rows(float* x, int rows, int cols, const DropArgs& d, hipStream_t s);
-int ofx_launch_focal_loss(const float* logits, const float* labels, int B, float alpha, float gamma, float upstream, float* loss, float* dlogits, hipStream_t s,
-                          int reduction = 1, float* per_elem = nullptr);
-size_t ofx_set_rank_loss_ws(int B, int K);
-int ofx_launch_set_rank_loss(const float* y, const float* y_hat, const float* neg, const uint8_t* mask, int B, int K, int D, float margin, float upstream,
-                             float* loss, float* dy_hat, float* d_pos, float* d_neg, void* ws, hipStream_t s);
-int ofx_launch_set_rank_loss_indexed(const float* table, int ld, int n_table, const int* pos_index, const int* neg_index, const float* y_hat, int B, int K,
-                                     int D, float margin, float upstream, float* loss, float* dy_hat, float* d_pos, float* d_neg, void* ws, hipStream_t s);
-size_t ofx_adamw_step_ws(long long n_arena);
-int ofx_launch_adamw_step(const ofx_opt_segment* segments, int n_segments, float* grad, float* exp_avg, float* exp_avg_sq, long long n_arena,
-                          float* step, double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm, double grad_scale,
-                          float* grad_norm, int* skipped, void* ws, hipStream_t s);
-int ofx_launch_cp_head_bwd(const float* dlogits, const float* w_or_rows, const int* cu, float* dX, void* dXb, float* db, int B, int D, int op_dtype,
-                           const DropArgs& head, const DropArgs& below, hipStream_t s, int accumulate = 0);
-int ofx_launch_fitb(const float* y, const float* cand, int B, int C, int D, int64_t* idx, float* dist, hipStream_t s);
-int ofx_launch_fitb_indexed(const float* table, int ld, int n_table, const int* cand_index, const float* y, int B, int C, int D, const int64_t* answer,
-                            int64_t* idx, float* dist, int* n_correct, hipStream_t s);
-int ofx_launch_l2_topk(const float* Q, const float* P, int nq, int np, int D, int k, int64_t index_base, int64_t* idx,
-                       float* dist, void* ws, size_t ws_bytes, hipStream_t s);
-size_t ofx_l2_topk_ws(int nq, int np);
-int ofx_launch_l2_topk_grouped(const float* Q, const float* P, int nq, int np, int D, int k, const int* panels, int n_panels, int max_group_rows,
-                               const int64_t* gt, int64_t* idx, float* dist, int* gt_pos, void* ws, size_t ws_bytes, hipStream_t s);
-int ofx_launch_topk_merge(const int64_t* idx_in, const float* dist_in, int parts, int nq, int k, int64_t* idx, float* dist,
-                          hipStream_t s);
-
-namespace {
-
-struct Arena {                                      // library-owned HBM for packed weights
-    char* base = nullptr; size_t cap = 0, off = 0;
-    bool fresh = true;                              // newly allocated: zero padding has to be written (it survives re-packs)
-    int reserve(size_t bytes) {
-        if (base && cap >= bytes) { off = 0; return OFX_OK; }
-        if (base) (void)hipFree(base);
-        base = nullptr; cap = 0; off = 0;
-        OFX_HIP(hipMalloc((void**)&base, bytes));
-        cap = bytes; fresh = true;
-        return OFX_OK;
-    }
-    template <typename T> T* take(size_t n) {
-        off = align_up(off, 256);
-        T* r = (T*)(base + off);
-        off += n * sizeof(T);
-        return r;
-    }
-    void release() { if (base) (void)hipFree(base); base = nullptr; cap = off = 0; }
-};
-
-struct OutfitLayer { void *w_in, *w_out, *w_1, *w_2; float *b_in, *b_out, *b_1, *b_2, *g1, *be1, *g2, *be2;
-                     void *w_in_t, *w_out_t, *w_1_t, *w_2_t; };   // transposed operand copies (dgrad), single-product precisions only
-// fp8 companion of a split-weight copy (gemm_w2f8.hip): {e4m3 lo rows, per-row scale bytes}; filled at pack time for f16 towers and kept
-// next to the [hi | lo] rows pointer it belongs to (in the layer / the handle: no process-wide table, nothing shared between handles or threads)
-struct F8Pair { void* w8 = nullptr; void* s8 = nullptr; };
-static void use_split(GemmArgs& g, const void* w2, int K, const F8Pair& f8) {
-    g.W = w2; g.K = 2 * K; g.a_wrap = K;
-    g.W8 = f8.w8; g.w8_scale = f8.s8;
-}
-// One tower GEMM as its launch reads it: the weight rows in ONE form - plain [N, K], split [N, hi(K) | lo(K)] (GemmArgs::a_wrap; with
-// the fp8 companion of the lo halves, a null pair where the shape / type has none) or three-product [N, hi | hi | lo] -, the bias, and
-// for a LayerNorm-folded weight (W . gamma rounded) the column sums of the rounded rows, its bias being bias + W beta (null: not folded)
-struct ClipGemm { void* w = nullptr; float* bias = nullptr; float* col_sum = nullptr; int mode = 0; F8Pair f8; };   // mode: 0 plain, 3 split, 2 three-product (ofx_launch_pack_rows)
-// K = the logical depth; the A rows are [M, K], or [hi | lo | hi] rows of 3 K elements for a three-product weight
-static void use_gemm(GemmArgs& g, const ClipGemm& c, int K) {
-    g.W = c.w; g.K = K; g.lda = K; g.bias = c.bias; g.col_sum = c.col_sum;
-    if (c.mode == 3) use_split(g, c.w, K, c.f8);
-    if (c.mode == 2) { g.K = 3 * K; g.k_mult = 3; g.lda = 3 * K; }
-}
-struct ClipLayer { ClipGemm qkv, o, fc1, fc2; float *g1, *be1, *g2, *be2; };
-
-}  // namespace
-
-struct ofx_handle {
-    int device;
-    ofx_model_desc d;
-    // outfit transformer
-    Arena a_out; bool out_ready = false;
-    int ot_dtype, ot_kmul, ot_ffn_pad; bool ot_w2 = false;      // ot_w2: OFX_PREC_F16W2 - weights packed [hi | lo], GEMMs with a wrapping A index (two products per weight)
-    std::vector<OutfitLayer> ol;
-    float *outfit_token, *tgt_img_emb, *cp_w, *cp_b; void* cir_w; void* cir_w_t = nullptr;   // cir_w_t: W^T operand copy (training dgrad)
-    // towers
-    int tw_dtype;
-    int vit_w2_mask = 0, txt_x3 = 0, proj_x3 = 0, vit_x3 = 0, txt_w2_mask = 0;    // operand scheme (ofx_model_desc); x3 towers hold ONLY the K-concatenated [hi | hi | lo] weight copies
-    F8Pair f8_patch;        // fp8 companion of v_patch_w when it is split (OFX_W2_PATCH)
-    // training: events armed for the NEXT backward call (ofx_train_arm_layer_events), one per outfit-transformer layer
-    std::vector<hipEvent_t> bwd_events;
-    Arena a_vis; bool vis_ready = false;
-    std::vector<ClipLayer> vl;
-    void *v_patch_w, *v_proj_w; float *v_cls, *v_pos, *v_pre_g, *v_pre_b, *v_post_g, *v_post_b;
-    Arena a_txt; bool txt_ready = false;
-    std::vector<ClipLayer> tl;
-    float *t_tok, *t_pos, *t_fin_g, *t_fin_b; void* t_proj_w;
-};
-// One outfit-transformer GEMM against a weight of ofx_pack_outfit_weights, as the handle's precision packed it: plain [N, K], [hi | lo]
-// against one copy of the activations (f16w2: GemmArgs::a_wrap) or three-product [hi | hi | lo] against [hi | lo | hi] rows of 3 K
-// elements (bf16x3).  K = the logical depth; slab = the workspace's split-K scratch (null: the plan never splits).
-static GemmArgs outfit_gemm(const ofx_handle* h, const void* W, int K, void* slab, size_t slab_bytes) {
-    GemmArgs g{};
-    g.W = W; g.K = h->ot_kmul * K; g.k_mult = h->ot_kmul; g.lda = h->ot_kmul * K;
-    if (h->ot_w2) { g.K = 2 * K; g.a_wrap = K; }
-    g.slab = slab; g.slab_bytes = slab_bytes;
-    return g;
-}
-
 extern "C" void ofx_default_desc(ofx_model_desc* d) {
     memset(d, 0, sizeof(*d));
     d->d_model = 1024; d->n_head = 16; d->d_ffn = 2024; d->n_layers = 6; d->max_items = 16;
@@ -265,28 +151,11 @@ extern "C" void ofx_default_desc(ofx_model_desc* d) {
 
 extern "C" ofx_handle* ofx_create(int device, const ofx_model_desc* desc) {
     if (!desc) { ofx_set_error("ofx_create: desc is NULL"); return nullptr; }
-    const ofx_model_desc& d = *desc;
-    auto bad = [&](const char* why) { ofx_set_error("ofx_create: %s", why); return (ofx_handle*)nullptr; };
-    if (d.d_model != d.n_head * 64 || (d.d_model != 512 && d.d_model != 768 && d.d_model != 1024)) return bad("d_model must be n_head*64 and one of 512/768/1024");
-    if (d.vit_width != d.vit_heads * 64 || d.txt_width != d.txt_heads * 64) return bad("tower head_dim must be 64");
-    if (d.vit_width % 256 || d.txt_width % 256 || d.proj_dim % 128 || d.vit_mlp % 128 || d.txt_mlp % 128) return bad("tower dims must be multiples of 128/256");
-    if (d.vit_image % d.vit_patch || (d.vit_image / d.vit_patch) * (d.vit_image / d.vit_patch) + 1 > 64) return bad("ViT sequence (patches+1) must be <= 64");
-    if (d.max_items < 0 || d.max_items > 63) return bad("max_items must be in [0,63]");
-    if (d.tower_precision != OFX_PREC_BF16 && d.tower_precision != OFX_PREC_F16) return bad("tower_precision must be BF16 or F16");
-    if (d.outfit_precision < 0 || d.outfit_precision > 3) return bad("bad outfit_precision");
-    if (d.n_layers < 1 || d.vit_layers < 1 || d.txt_layers < 1 || d.d_ffn < 1) return bad("layer counts / d_ffn must be positive");
-    if (d.vit_w2_mask & ~(OFX_W2_PATCH | OFX_W2_QKV | OFX_W2_OUT | OFX_W2_FC1 | OFX_W2_FC2)) return bad("vit_w2_mask: unknown bit");
-    if (d.txt_w2_mask & ~(OFX_W2_QKV | OFX_W2_OUT | OFX_W2_FC1 | OFX_W2_FC2)) return bad("txt_w2_mask: unknown bit");
-    if (d.txt_w2_mask && d.txt_x3) return bad("txt_w2_mask applies to the single-product text tower (txt_x3 = 0)");
-    if (hipSetDevice(device) != hipSuccess) return bad("hipSetDevice failed");
     ofx_handle* h = new ofx_handle();
-    h->device = device; h->d = d;
-    h->ot_dtype = (d.outfit_precision == OFX_PREC_F16 || d.outfit_precision == OFX_PREC_F16W2) ? OFX_F16 : OFX_BF16;
-    h->ot_kmul = d.outfit_precision == OFX_PREC_BF16X3 ? 3 : 1;
-    h->ot_w2 = d.outfit_precision == OFX_PREC_F16W2;
-    h->ot_ffn_pad = pad128(d.d_ffn);
-    h->tw_dtype = d.tower_precision == OFX_PREC_F16 ? OFX_F16 : OFX_BF16;
-    h->vit_w2_mask = d.vit_w2_mask; h->txt_w2_mask = d.txt_w2_mask; h->txt_x3 = d.txt_x3 != 0; h->vit_x3 = d.vit_x3 != 0; h->proj_x3 = d.proj_x3 != 0 || h->vit_x3;
+    const char* why = ofx_configure(*h, *desc);
+    if (!why && hipSetDevice(device) != hipSuccess) why = "hipSetDevice failed";
+    if (why) { ofx_set_error("ofx_create: %s", why); delete h; return nullptr; }
+    h->device = device;
     return h;
 }
 
@@ -300,8 +169,6 @@ extern "C" void ofx_destroy(ofx_handle* h) {
 // The ~60 small fp32 tensors of a pack (biases, LayerNorm parameters, tokens) travel in ONE kernel launch instead of one
 // hipMemcpyAsync each: training re-packs after every optimizer step, and 60 x 3 us of copy launches were 0.2 ms of a 4 ms step.
 // Entries are collected while a CopyBatch is active on this thread and flushed at the end of the pack call.
-int ofx_launch_multi_copy(const void* table_host, int n, hipStream_t s);
-int ofx_launch_fill_f32(float* p, size_t n, float v, hipStream_t s);
 namespace {
 struct CopyEntry { const float* src; float* dst; long long n; };
 struct CopyBatch;
@@ -323,6 +190,16 @@ static int copy_f32(float* dst, const void* src, size_t n, hipStream_t s) {
     return OFX_OK;
 }
 
+// Sizes the arena by the layout walk over a counting arena, then places the handle's pointers by the same walk over the real one.
+// When this returns OFX_OK the arena holds the whole layout, and only then does a pack call enqueue anything against those pointers.
+// An arena that is large enough is reused, so a re-pack leaves every pointer where it was (captured graphs, the training loop).
+static int place(ofx_handle* h, Arena& A, size_t (*layout)(ofx_handle&, Arena&)) {
+    Arena count;
+    TRY(A.reserve(layout(*h, count)));
+    layout(*h, A);
+    return OFX_OK;
+}
+
 extern "C" int ofx_pack_outfit_weights(ofx_handle* h, const void* const* P, int n, ofx_stream stream) {
     OFX_REQUIRE(h, OFX_EINVAL, "pack_outfit: NULL handle");
     const ofx_model_desc& d = h->d;
@@ -330,120 +207,81 @@ extern "C" int ofx_pack_outfit_weights(ofx_handle* h, const void* const* P, int 
     for (int i = 0; i < n; ++i) OFX_REQUIRE(P[i], OFX_EINVAL, "pack_outfit: tensor %d is NULL", i);
     hipStream_t s = (hipStream_t)stream;
     const size_t D = d.d_model, F = d.d_ffn, Fp = h->ot_ffn_pad;
-    const size_t km = h->ot_w2 ? 2 : h->ot_kmul;          // K multiplier of the packed weight rows: 1 plain, 2 [hi | lo] (f16w2), 3 [hi | hi | lo] (bf16x3)
-    const bool trainable = h->ot_kmul == 1 && !h->ot_w2;  // single-product precisions also keep W^T operand copies for the backward
-    const size_t per_layer = 2 * km * (3 * D * D + D * D + Fp * D + D * Fp) + 4 * (3 * D + D + Fp + D + 4 * D) + 16 * 256;
-    const size_t per_layer_t = trainable ? 2 * (3 * D * D + D * D + 2 * Fp * D) + 8 * 256 : 0;
-    TRY(h->a_out.reserve((per_layer + per_layer_t) * d.n_layers + 2 * (km + 1) * D * D + 4 * (3 * D + 8) + 16 * 256));
     Arena& A = h->a_out;
+    h->out_ready = false;                           // until the walk below has placed the pointers and the fill is enqueued
+    TRY(place(h, A, layout_outfit));
     const bool zero_pad = A.fresh;                  // padding written once per allocation
     CopyBatch copies;
-    const int dt = h->ot_dtype, mode = km == 3 ? 2 : (km == 2 ? 3 : 0);
-    h->outfit_token = A.take<float>(D); TRY(copy_f32(h->outfit_token, P[0], D, s));
-    h->tgt_img_emb = A.take<float>(D / 2); TRY(copy_f32(h->tgt_img_emb, P[1], D / 2, s));
-    h->cp_w = A.take<float>(D); TRY(copy_f32(h->cp_w, P[2], D, s));
-    h->cp_b = A.take<float>(1); TRY(copy_f32(h->cp_b, P[3], 1, s));
-    h->cir_w = A.take<char>(2 * km * D * D); TRY(ofx_launch_pack_rows((const float*)P[4], h->cir_w, D, D, D, D, D, mode, dt, s));
-    h->cir_w_t = nullptr;
-    if (trainable) { h->cir_w_t = A.take<char>(2 * D * D); TRY(ofx_launch_transpose_cast((const float*)P[4], h->cir_w_t, (int)D, (int)D, (int)D, dt, s)); }
-    h->ol.resize(d.n_layers);
+    const int dt = h->ot_dtype, mode = pack_rows_mode(h->ot_form);
+    const bool both = h->ot_form == W_PLAIN;        // single-product precisions: a layer weight's row-major copy and its W^T come out of ONE pass
+    TRY(copy_f32(h->outfit_token, P[0], D, s)); TRY(copy_f32(h->tgt_img_emb, P[1], D / 2, s));
+    TRY(copy_f32(h->cp_w, P[2], D, s)); TRY(copy_f32(h->cp_b, P[3], 1, s));
+    TRY(ofx_launch_pack_rows((const float*)P[4], h->cir.w, D, D, D, D, D, mode, dt, s));
+    if (h->cir.wt) TRY(ofx_launch_transpose_cast((const float*)P[4], h->cir.wt, (int)D, (int)D, (int)D, dt, s));
     for (int l = 0; l < d.n_layers; ++l) {
         const void* const* q = P + 5 + 12 * l;
         OutfitLayer& L = h->ol[l];
-        const bool both = trainable;        // single-product precisions: the row-major copy and W^T come out of ONE pass below
-        L.w_in = A.take<char>(2 * km * 3 * D * D); if (!both) TRY(ofx_launch_pack_rows((const float*)q[0], L.w_in, 3 * D, 3 * D, D, D, D, mode, dt, s));
-        L.b_in = A.take<float>(3 * D); TRY(copy_f32(L.b_in, q[1], 3 * D, s));
-        L.w_out = A.take<char>(2 * km * D * D); if (!both) TRY(ofx_launch_pack_rows((const float*)q[2], L.w_out, D, D, D, D, D, mode, dt, s));
-        L.b_out = A.take<float>(D); TRY(copy_f32(L.b_out, q[3], D, s));
-        L.w_1 = A.take<char>(2 * km * Fp * D);
-        if (!both) TRY(ofx_launch_pack_rows((const float*)q[4], L.w_1, F, Fp, D, D, D, mode, dt, s));
-        else if (zero_pad) OFX_HIP(hipMemsetAsync(L.w_1, 0, 2 * Fp * D, s));                       // rows F.. stay zero
-        L.b_1 = A.take<float>(Fp); if (zero_pad) OFX_HIP(hipMemsetAsync(L.b_1, 0, Fp * 4, s)); TRY(copy_f32(L.b_1, q[5], F, s));
-        L.w_2 = A.take<char>(2 * km * D * Fp);
-        if (!both) TRY(ofx_launch_pack_rows((const float*)q[6], L.w_2, D, D, F, Fp, F, mode, dt, s));
-        else if (zero_pad) OFX_HIP(hipMemsetAsync(L.w_2, 0, 2 * D * Fp, s));                       // columns F.. stay zero
-        L.b_2 = A.take<float>(D); TRY(copy_f32(L.b_2, q[7], D, s));
-        L.g1 = A.take<float>(D); TRY(copy_f32(L.g1, q[8], D, s));
-        L.be1 = A.take<float>(D); TRY(copy_f32(L.be1, q[9], D, s));
-        L.g2 = A.take<float>(D); TRY(copy_f32(L.g2, q[10], D, s));
-        L.be2 = A.take<float>(D); TRY(copy_f32(L.be2, q[11], D, s));
-        L.w_in_t = L.w_out_t = L.w_1_t = L.w_2_t = nullptr;
-        if (trainable) {    // W^T copies for the backward dgrad GEMMs: [K_w, N_w] operand, zero padded
-            L.w_in_t = A.take<char>(2 * D * 3 * D); TRY(ofx_launch_transpose_cast((const float*)q[0], L.w_in_t, (int)(3 * D), (int)D, (int)(3 * D), dt, s, L.w_in, (int)D));
-            L.w_out_t = A.take<char>(2 * D * D); TRY(ofx_launch_transpose_cast((const float*)q[2], L.w_out_t, (int)D, (int)D, (int)D, dt, s, L.w_out, (int)D));
-            L.w_1_t = A.take<char>(2 * D * Fp); if (zero_pad) OFX_HIP(hipMemsetAsync(L.w_1_t, 0, 2 * D * Fp, s));      // [D, Fp], columns F.. stay zero
-            TRY(ofx_launch_transpose_cast((const float*)q[4], L.w_1_t, (int)F, (int)D, (int)Fp, dt, s, L.w_1, (int)D));
-            L.w_2_t = A.take<char>(2 * Fp * D); if (zero_pad) OFX_HIP(hipMemsetAsync(L.w_2_t, 0, 2 * Fp * D, s));      // [Fp, D], rows F.. stay zero
-            TRY(ofx_launch_transpose_cast((const float*)q[6], L.w_2_t, (int)D, (int)F, (int)D, dt, s, L.w_2, (int)Fp));
+        if (!both) TRY(ofx_launch_pack_rows((const float*)q[0], L.in.w, 3 * D, 3 * D, D, D, D, mode, dt, s));
+        TRY(copy_f32(L.in.bias, q[1], 3 * D, s));
+        if (!both) TRY(ofx_launch_pack_rows((const float*)q[2], L.out.w, D, D, D, D, D, mode, dt, s));
+        TRY(copy_f32(L.out.bias, q[3], D, s));
+        if (!both) TRY(ofx_launch_pack_rows((const float*)q[4], L.l1.w, F, Fp, D, D, D, mode, dt, s));
+        else if (zero_pad) OFX_HIP(hipMemsetAsync(L.l1.w, 0, 2 * Fp * D, s));                       // rows F.. stay zero
+        if (zero_pad) OFX_HIP(hipMemsetAsync(L.l1.bias, 0, Fp * 4, s));
+        TRY(copy_f32(L.l1.bias, q[5], F, s));
+        if (!both) TRY(ofx_launch_pack_rows((const float*)q[6], L.l2.w, D, D, F, Fp, F, mode, dt, s));
+        else if (zero_pad) OFX_HIP(hipMemsetAsync(L.l2.w, 0, 2 * D * Fp, s));                       // columns F.. stay zero
+        TRY(copy_f32(L.l2.bias, q[7], D, s));
+        TRY(copy_f32(L.g1, q[8], D, s)); TRY(copy_f32(L.be1, q[9], D, s));
+        TRY(copy_f32(L.g2, q[10], D, s)); TRY(copy_f32(L.be2, q[11], D, s));
+        if (both) {         // W^T copies for the backward dgrad GEMMs: [K_w, N_w] operand, zero padded
+            TRY(ofx_launch_transpose_cast((const float*)q[0], L.in.wt, (int)(3 * D), (int)D, (int)(3 * D), dt, s, L.in.w, (int)D));
+            TRY(ofx_launch_transpose_cast((const float*)q[2], L.out.wt, (int)D, (int)D, (int)D, dt, s, L.out.w, (int)D));
+            if (zero_pad) OFX_HIP(hipMemsetAsync(L.l1.wt, 0, 2 * D * Fp, s));      // [D, Fp], columns F.. stay zero
+            TRY(ofx_launch_transpose_cast((const float*)q[4], L.l1.wt, (int)F, (int)D, (int)Fp, dt, s, L.l1.w, (int)D));
+            if (zero_pad) OFX_HIP(hipMemsetAsync(L.l2.wt, 0, 2 * Fp * D, s));      // [Fp, D], rows F.. stay zero
+            TRY(ofx_launch_transpose_cast((const float*)q[6], L.l2.wt, (int)D, (int)F, (int)D, dt, s, L.l2.w, (int)Fp));
         }
     }
-    OFX_REQUIRE(A.off <= A.cap, OFX_ESTATE, "pack_outfit: arena overflow");
     TRY(copies.flush(s));
     A.fresh = false;
     h->out_ready = true;
     return OFX_OK;
 }
 
-// fp8 copy of a split-weight matrix's lo halves (f16 towers, shapes gemm_w2f8 takes) -> `out` (a null pair where the shape / type has none)
-static bool has_f8(size_t N, size_t K, int dt) { return dt == OFX_F16 && N % 128 == 0 && K % 128 == 0 && K >= 256; }
-static int pack_f8(Arena& A, const void* w2, size_t N, size_t K, int dt, hipStream_t s, F8Pair& out) {
-    out = F8Pair{};
-    if (!has_f8(N, K, dt)) return OFX_OK;
-    char* w8 = A.take<char>(N * K); char* s8 = A.take<char>(N);
-    TRY(ofx_launch_pack_lo8(w2, w8, s8, (int)N, (int)K, s));
-    out = F8Pair{w8, s8};
-    return OFX_OK;
+// fp8 copy of a split weight's lo halves, where the layout gave the record one
+static int pack_f8(const PackedGemm& c, size_t N, size_t K, hipStream_t s) {
+    return c.f8.w8 ? ofx_launch_pack_lo8(c.w, c.f8.w8, c.f8.s8, (int)N, (int)K, s) : OFX_OK;
 }
-
-// The one copy of a tower GEMM that its launch reads.  `q` points at the 16 per-layer tensors in HF order: k.w,k.b,v.w,v.b,q.w,q.b,
-// out.w,out.b,ln1.w,ln1.b,fc1.w,fc1.b,fc2.w,fc2.b,ln2.w,ln2.b; `blocks` lists the weights (their biases follow them) stacked as row
-// blocks of Nb rows each (q | k | v: {4, 0, 2}).  mode: 0 plain, 3 split, 2 three-product (ofx_launch_pack_rows); ln >= 0 folds the
-// LayerNorm whose gamma / beta sit at q[ln], q[ln + 1] into the weight (plain or split).
-static int clip_gemm_mode(int w2_mask, int bit, bool x3) { return x3 ? 2 : ((w2_mask & bit) ? 3 : 0); }
-static size_t clip_gemm_bytes(size_t N, size_t K, int mode, bool folded, int dt) {      // the arena bytes pack_clip_gemm takes
-    const size_t km = mode == 2 ? 3 : (mode == 3 ? 2 : 1);
-    return align_up(2 * km * N * K, 256) + (folded ? 2 : 1) * align_up(4 * N, 256) + (mode == 3 && has_f8(N, K, dt) ? align_up(N * K, 256) + align_up(N, 256) : 0);
-}
-static int pack_clip_gemm(Arena& A, ClipGemm& c, const void* const* q, std::initializer_list<int> blocks, size_t Nb, size_t K, int mode, int ln,
-                          int dt, hipStream_t s) {
-    const size_t N = Nb * blocks.size(), km = mode == 2 ? 3 : (mode == 3 ? 2 : 1);
-    c = ClipGemm{};
-    char* w = A.take<char>(2 * km * N * K);
-    c.w = w; c.mode = mode; c.bias = A.take<float>(N);
-    if (ln >= 0) c.col_sum = A.take<float>(N);
+// Fills the one copy of a tower GEMM that its launch reads, in the record's form.  `q` points at the 16 per-layer tensors in HF order:
+// k.w,k.b,v.w,v.b,q.w,q.b,out.w,out.b,ln1.w,ln1.b,fc1.w,fc1.b,fc2.w,fc2.b,ln2.w,ln2.b; `blocks` lists the weights (their biases follow
+// them) stacked as row blocks of Nb rows each (q | k | v: {4, 0, 2}).  A record with column sums is folded (plain or split): the
+// LayerNorm whose gamma / beta sit at q[ln], q[ln + 1] goes into the weight.
+static int pack_clip_gemm(const PackedGemm& c, const void* const* q, std::initializer_list<int> blocks, size_t Nb, size_t K, int ln, int dt, hipStream_t s) {
+    const size_t km = w_kmul(c.form);
+    char* w = (char*)c.w;
     size_t r = 0;
     for (int i : blocks) {
         const float* src = (const float*)q[i];
-        if (ln >= 0)
+        if (c.col_sum)
             TRY(ofx_launch_fold_pack(src, (const float*)q[ln], (const float*)q[ln + 1], (const float*)q[i + 1], w + 2 * km * r * K, c.col_sum + r, c.bias + r,
-                                     (int)Nb, (int)K, dt, s, mode == 3));
+                                     (int)Nb, (int)K, dt, s, c.form == W_SPLIT));
         else {
-            TRY(ofx_launch_pack_rows(src, w + 2 * km * r * K, (int)Nb, (int)Nb, (int)K, (int)K, (int)K, mode, dt, s));
+            TRY(ofx_launch_pack_rows(src, w + 2 * km * r * K, (int)Nb, (int)Nb, (int)K, (int)K, (int)K, pack_rows_mode(c.form), dt, s));
             TRY(copy_f32(c.bias + r, q[i + 1], Nb, s));
         }
         r += Nb;
     }
-    if (mode == 3) TRY(pack_f8(A, w, N, K, dt, s, c.f8));       // one [N, K] matrix: q | k | v row blocks
-    return OFX_OK;
+    return pack_f8(c, r, K, s);       // one [N, K] matrix: q | k | v row blocks
 }
-
-// Folded towers (x3 = false): qkv folds LayerNorm 1 in every layer; fc1 folds LayerNorm 2 except in the pooled last layer, which
-// materialises it on the pooled rows.  Three-product towers materialise every LayerNorm.  Split copies where the layer's mask says so.
-static int pack_clip_layer(Arena& A, ClipLayer& L, const void* const* q, size_t W, size_t MLP, int dt, hipStream_t s, int w2_mask, bool x3, bool last) {
-    TRY(pack_clip_gemm(A, L.qkv, q, {4, 0, 2}, W, W, clip_gemm_mode(w2_mask, OFX_W2_QKV, x3), x3 ? -1 : 8, dt, s));
-    TRY(pack_clip_gemm(A, L.o, q, {6}, W, W, clip_gemm_mode(w2_mask, OFX_W2_OUT, x3), -1, dt, s));
-    TRY(pack_clip_gemm(A, L.fc1, q, {10}, MLP, W, clip_gemm_mode(w2_mask, OFX_W2_FC1, x3), x3 || last ? -1 : 14, dt, s));
-    TRY(pack_clip_gemm(A, L.fc2, q, {12}, W, MLP, clip_gemm_mode(w2_mask, OFX_W2_FC2, x3), -1, dt, s));
-    L.g1 = A.take<float>(W); TRY(copy_f32(L.g1, q[8], W, s));
-    L.be1 = A.take<float>(W); TRY(copy_f32(L.be1, q[9], W, s));
-    L.g2 = A.take<float>(W); TRY(copy_f32(L.g2, q[14], W, s));
-    L.be2 = A.take<float>(W); TRY(copy_f32(L.be2, q[15], W, s));
+static int pack_clip_layer(const ClipLayer& L, const void* const* q, size_t W, size_t MLP, int dt, hipStream_t s) {
+    TRY(pack_clip_gemm(L.qkv, q, {4, 0, 2}, W, W, 8, dt, s));
+    TRY(pack_clip_gemm(L.o, q, {6}, W, W, -1, dt, s));
+    TRY(pack_clip_gemm(L.fc1, q, {10}, MLP, W, 14, dt, s));
+    TRY(pack_clip_gemm(L.fc2, q, {12}, W, MLP, -1, dt, s));
+    TRY(copy_f32(L.g1, q[8], W, s)); TRY(copy_f32(L.be1, q[9], W, s));
+    TRY(copy_f32(L.g2, q[14], W, s)); TRY(copy_f32(L.be2, q[15], W, s));
     return OFX_OK;
-}
-static size_t clip_layer_bytes(size_t W, size_t MLP, int w2_mask, bool x3, bool last, int dt) {
-    return clip_gemm_bytes(3 * W, W, clip_gemm_mode(w2_mask, OFX_W2_QKV, x3), !x3, dt) + clip_gemm_bytes(W, W, clip_gemm_mode(w2_mask, OFX_W2_OUT, x3), false, dt) +
-           clip_gemm_bytes(MLP, W, clip_gemm_mode(w2_mask, OFX_W2_FC1, x3), !x3 && !last, dt) + clip_gemm_bytes(W, MLP, clip_gemm_mode(w2_mask, OFX_W2_FC2, x3), false, dt) +
-           4 * align_up(4 * W, 256);
 }
 
 extern "C" int ofx_pack_vision_weights(ofx_handle* h, const void* const* P, int n, ofx_stream stream) {
@@ -453,36 +291,18 @@ extern "C" int ofx_pack_vision_weights(ofx_handle* h, const void* const* P, int 
     for (int i = 0; i < n; ++i) OFX_REQUIRE(P[i], OFX_EINVAL, "pack_vision: tensor %d is NULL", i);
     hipStream_t s = (hipStream_t)stream;
     const size_t W = d.vit_width, MLP = d.vit_mlp, KP = 3 * (size_t)d.vit_patch * d.vit_patch, g = d.vit_image / d.vit_patch, S = g * g + 1, PD = d.proj_dim;
-    const bool vx3 = h->vit_x3 != 0, psplit = (h->vit_w2_mask & OFX_W2_PATCH) != 0;
     const int dt = h->tw_dtype;
-    std::vector<int> masks(d.vit_layers);
-    size_t layer_bytes = 0;
-    for (int l = 0; l < d.vit_layers; ++l) {       // per-layer rungs: a layer outside vit_w2_qkv_layers / vit_w2_fc1_layers keeps the single-product copy of that GEMM
-        int m = h->vit_w2_mask;
-        if (d.vit_w2_qkv_layers && !((d.vit_w2_qkv_layers >> l) & 1)) m &= ~OFX_W2_QKV;
-        if (d.vit_w2_fc1_layers && !((d.vit_w2_fc1_layers >> l) & 1)) m &= ~OFX_W2_FC1;
-        if (d.vit_w2_out_layers && !((d.vit_w2_out_layers >> l) & 1)) m &= ~OFX_W2_OUT;
-        if (d.vit_w2_fc2_layers && !((d.vit_w2_fc2_layers >> l) & 1)) m &= ~OFX_W2_FC2;
-        masks[l] = m;
-        layer_bytes += clip_layer_bytes(W, MLP, m, vx3, l + 1 == d.vit_layers, dt);
-    }
-    TRY(h->a_vis.reserve(layer_bytes + (psplit ? 5 * W * KP + W : 2 * W * KP) + (h->proj_x3 ? 6 : 2) * PD * W + 4 * (W + S * W + 4 * W) + 12 * 256));
-    Arena& A = h->a_vis;
+    h->vis_ready = false;
+    TRY(place(h, h->a_vis, layout_vision));
     CopyBatch copies;
-    h->v_cls = A.take<float>(W); TRY(copy_f32(h->v_cls, P[0], W, s));
-    h->v_patch_w = A.take<char>((psplit ? 4 : 2) * W * KP); TRY(ofx_launch_pack_rows((const float*)P[1], h->v_patch_w, W, W, KP, KP, KP, psplit ? 3 : 0, dt, s));
-    h->f8_patch = F8Pair{};
-    if (psplit) TRY(pack_f8(A, h->v_patch_w, W, KP, dt, s, h->f8_patch));
-    h->v_pos = A.take<float>(S * W); TRY(copy_f32(h->v_pos, P[2], S * W, s));
-    h->v_pre_g = A.take<float>(W); TRY(copy_f32(h->v_pre_g, P[3], W, s));
-    h->v_pre_b = A.take<float>(W); TRY(copy_f32(h->v_pre_b, P[4], W, s));
-    h->vl.resize(d.vit_layers);
-    for (int l = 0; l < d.vit_layers; ++l) TRY(pack_clip_layer(A, h->vl[l], P + 5 + 16 * l, W, MLP, dt, s, masks[l], vx3, l + 1 == d.vit_layers));
+    TRY(copy_f32(h->v_cls, P[0], W, s));
+    TRY(ofx_launch_pack_rows((const float*)P[1], h->v_patch.w, W, W, KP, KP, KP, pack_rows_mode(h->v_patch.form), dt, s));
+    TRY(pack_f8(h->v_patch, W, KP, s));
+    TRY(copy_f32(h->v_pos, P[2], S * W, s)); TRY(copy_f32(h->v_pre_g, P[3], W, s)); TRY(copy_f32(h->v_pre_b, P[4], W, s));
+    for (int l = 0; l < d.vit_layers; ++l) TRY(pack_clip_layer(h->vl[l], P + 5 + 16 * l, W, MLP, dt, s));
     const void* const* t = P + 5 + 16 * d.vit_layers;
-    h->v_post_g = A.take<float>(W); TRY(copy_f32(h->v_post_g, t[0], W, s));
-    h->v_post_b = A.take<float>(W); TRY(copy_f32(h->v_post_b, t[1], W, s));
-    h->v_proj_w = A.take<char>(2 * (h->proj_x3 ? 3 : 1) * PD * W); TRY(ofx_launch_pack_rows((const float*)t[2], h->v_proj_w, PD, PD, W, W, W, h->proj_x3 ? 2 : 0, dt, s));
-    OFX_REQUIRE(A.off <= A.cap, OFX_ESTATE, "pack_vision: arena overflow");
+    TRY(copy_f32(h->v_post_g, t[0], W, s)); TRY(copy_f32(h->v_post_b, t[1], W, s));
+    TRY(ofx_launch_pack_rows((const float*)t[2], h->v_proj.w, PD, PD, W, W, W, pack_rows_mode(h->v_proj.form), dt, s));
     TRY(copies.flush(s));
     h->vis_ready = true;
     return OFX_OK;
@@ -495,22 +315,15 @@ extern "C" int ofx_pack_text_weights(ofx_handle* h, const void* const* P, int n,
     for (int i = 0; i < n; ++i) OFX_REQUIRE(P[i], OFX_EINVAL, "pack_text: tensor %d is NULL", i);
     hipStream_t s = (hipStream_t)stream;
     const size_t W = d.txt_width, MLP = d.txt_mlp, V = d.txt_vocab, NP = d.txt_max_pos, PD = d.proj_dim;
-    const bool x3 = h->txt_x3 != 0, x3p = x3 || h->proj_x3;          // x3p: the final LayerNorm + text_projection tail in three products
-    const int tmask = x3 ? 0 : h->txt_w2_mask;
     const int dt = h->tw_dtype;
-    TRY(h->a_txt.reserve(clip_layer_bytes(W, MLP, tmask, x3, false, dt) * (d.txt_layers - 1) + clip_layer_bytes(W, MLP, tmask, x3, true, dt) +
-                         4 * (V * W + NP * W + 2 * W) + 6 * PD * W + 16 * 256));
-    Arena& A = h->a_txt;
+    h->txt_ready = false;
+    TRY(place(h, h->a_txt, layout_text));
     CopyBatch copies;
-    h->t_tok = A.take<float>(V * W); TRY(copy_f32(h->t_tok, P[0], V * W, s));
-    h->t_pos = A.take<float>(NP * W); TRY(copy_f32(h->t_pos, P[1], NP * W, s));
-    h->tl.resize(d.txt_layers);
-    for (int l = 0; l < d.txt_layers; ++l) TRY(pack_clip_layer(A, h->tl[l], P + 2 + 16 * l, W, MLP, dt, s, tmask, x3, l + 1 == d.txt_layers));
+    TRY(copy_f32(h->t_tok, P[0], V * W, s)); TRY(copy_f32(h->t_pos, P[1], NP * W, s));
+    for (int l = 0; l < d.txt_layers; ++l) TRY(pack_clip_layer(h->tl[l], P + 2 + 16 * l, W, MLP, dt, s));
     const void* const* t = P + 2 + 16 * d.txt_layers;
-    h->t_fin_g = A.take<float>(W); TRY(copy_f32(h->t_fin_g, t[0], W, s));
-    h->t_fin_b = A.take<float>(W); TRY(copy_f32(h->t_fin_b, t[1], W, s));
-    h->t_proj_w = A.take<char>(2 * (x3p ? 3 : 1) * PD * W); TRY(ofx_launch_pack_rows((const float*)t[2], h->t_proj_w, PD, PD, W, W, W, x3p ? 2 : 0, dt, s));
-    OFX_REQUIRE(A.off <= A.cap, OFX_ESTATE, "pack_text: arena overflow");
+    TRY(copy_f32(h->t_fin_g, t[0], W, s)); TRY(copy_f32(h->t_fin_b, t[1], W, s));
+    TRY(ofx_launch_pack_rows((const float*)t[2], h->t_proj.w, PD, PD, W, W, W, pack_rows_mode(h->t_proj.form), dt, s));
     TRY(copies.flush(s));
     h->txt_ready = true;
     return OFX_OK;
@@ -520,7 +333,7 @@ extern "C" int ofx_pack_text_weights(ofx_handle* h, const void* const* P, int n,
 namespace {
 struct SetWs { int* cu; float* X; char* H; float* QKV; char* U; char* HP; char* UP; char* slab; size_t slab_bytes; };
 size_t carve_set(const ofx_handle* h, Bump& b, int B, int L, SetWs* w) {
-    const size_t M = (size_t)B * (L + 1), D = h->d.d_model, km = h->ot_kmul, Fp = h->ot_ffn_pad, wk = h->ot_w2 ? 2 : h->ot_kmul;
+    const size_t M = (size_t)B * (L + 1), D = h->d.d_model, km = a_kmul(h->ot_form), Fp = h->ot_ffn_pad, wk = w_kmul(h->ot_form);
     SetWs t;
     t.cu = b.take<int>(B + 1);
     t.X = b.take<float>(M * D);
@@ -646,8 +459,9 @@ static int set_encoder_core(ofx_handle* h, const SetInput& in, const float* pref
     SetWs w;
     carve_set(h, bump, B, L, &w);
     OFX_REQUIRE(bump.ok, OFX_EWORKSPACE, "set_encoder_fwd: workspace %zu < %zu bytes", ws_bytes, bump.off);
-    const int D = d.d_model, km = h->ot_kmul, Fp = h->ot_ffn_pad, dt = h->ot_dtype, M = B * (L + 1);
+    const int D = d.d_model, km = a_kmul(h->ot_form), Fp = h->ot_ffn_pad, dt = h->ot_dtype, M = B * (L + 1);
     const int okind = km == 3 ? OFX_OUT_SPLIT3 : OFX_OUT_OP;
+    auto slab_gemm = [&](const PackedGemm& c, int K) { GemmArgs g{}; use_gemm(g, c, K); g.slab = w.slab; g.slab_bytes = w.slab_bytes; return g; };
     if (!prefix) { prefix = h->outfit_token; prefix_stride = 0; }
     TRY(build_set(h, in, prefix, prefix_stride, w.cu, w.X, B, L, s));
     const int* m_dev = w.cu + B;
@@ -663,11 +477,11 @@ static int set_encoder_core(ofx_handle* h, const SetInput& in, const float* pref
             TRY(ofx_launch_layernorm_dev(ln, m_dev, dt, s));
         }
         ln1_done = false;
-        GemmArgs g1 = outfit_gemm(h, Ly.w_in, D, w.slab, w.slab_bytes);
-        g1.A = w.H; g1.C = w.QKV; g1.bias = Ly.b_in; g1.m_dev = m_dev; g1.M = M; g1.N = 3 * D; g1.ldc = 3 * D;
+        GemmArgs g1 = slab_gemm(Ly.in, D);
+        g1.A = w.H; g1.C = w.QKV; g1.m_dev = m_dev; g1.M = M; g1.N = 3 * D; g1.ldc = 3 * D;
         // single-product precisions: q|k|v stay in the operand type and the varlen MFMA attention runs (as in the training forward);
         // bf16x3 keeps fp32 q|k|v and the fp32 set attention (1e-5 parity)
-        const bool mfma_attn = km == 1 && !h->ot_w2 && g_train_mfma_attn;       // f16w2 keeps fp32 q | k | v and the fp32 set attention, as bf16x3 does
+        const bool mfma_attn = h->ot_form == W_PLAIN && g_train_mfma_attn;       // f16w2 keeps fp32 q | k | v and the fp32 set attention, as bf16x3 does
         g1.out_kind = mfma_attn ? OFX_OUT_OP : OFX_OUT_F32;
         int qkv_splits = 1;
         if (fuse_att && !mfma_attn) g1.defer_splits = &qkv_splits;
@@ -678,7 +492,7 @@ static int set_encoder_core(ofx_handle* h, const SetInput& in, const float* pref
             TRY(ofx_launch_attention_mfma(at, dt, s));
         } else {
             SetAttnArgs sa{w.QKV, w.H, w.cu, B, d.n_head, D, km * D, okind, L + 1, last ? 1 : 0, 0.125f};
-            if (qkv_splits > 1) { sa.qkv = w.slab; sa.splits = qkv_splits; sa.plane = (size_t)M * 3 * D; sa.bias = Ly.b_in; }
+            if (qkv_splits > 1) { sa.qkv = w.slab; sa.splits = qkv_splits; sa.plane = (size_t)M * 3 * D; sa.bias = g1.bias; }
             TRY(ofx_launch_set_attention(sa, dt, s));
         }
         float* X = w.X; char* H = w.H; char* U = w.U; int Ml = M; const int* md = m_dev;
@@ -687,8 +501,8 @@ static int set_encoder_core(ofx_handle* h, const SetInput& in, const float* pref
             TRY(ofx_launch_gather_rows(w.X, w.cu, out_row0, B, D * 4, D * 4, s));
             X = out_row0; H = w.HP; U = w.UP; Ml = B; md = nullptr;
         }
-        GemmArgs g2 = outfit_gemm(h, Ly.w_out, D, w.slab, w.slab_bytes);
-        g2.A = H; g2.C = X; g2.bias = Ly.b_out; g2.resid = X; g2.m_dev = md; g2.M = Ml; g2.N = D; g2.ldc = D; g2.ldr = D; g2.out_kind = OFX_OUT_F32;
+        GemmArgs g2 = slab_gemm(Ly.out, D);
+        g2.A = H; g2.C = X; g2.resid = X; g2.m_dev = md; g2.M = Ml; g2.N = D; g2.ldc = D; g2.ldr = D; g2.out_kind = OFX_OUT_F32;
         bool ln2_done = false;
         if (fuse) { g2.ln_gamma = Ly.g2; g2.ln_beta = Ly.be2; g2.ln_out = H; g2.ln_ld = km * D; g2.ln_kind = okind; g2.ln_eps = d.ln_eps; g2.ln_done = &ln2_done; }
         TRY(ofx_launch_gemm(g2, dt, s));
@@ -696,11 +510,11 @@ static int set_encoder_core(ofx_handle* h, const SetInput& in, const float* pref
             LnArgs ln2{X, nullptr, Ly.g2, Ly.be2, H, Ml, D, km * D, okind, d.ln_eps};
             TRY(ofx_launch_layernorm_dev(ln2, md, dt, s));
         }
-        GemmArgs g3 = outfit_gemm(h, Ly.w_1, D, w.slab, w.slab_bytes);
-        g3.A = H; g3.C = U; g3.bias = Ly.b_1; g3.m_dev = md; g3.M = Ml; g3.N = Fp; g3.ldc = km * Fp; g3.act = d.outfit_act; g3.out_kind = okind;
+        GemmArgs g3 = slab_gemm(Ly.l1, D);
+        g3.A = H; g3.C = U; g3.m_dev = md; g3.M = Ml; g3.N = Fp; g3.ldc = km * Fp; g3.act = d.outfit_act; g3.out_kind = okind;
         TRY(ofx_launch_gemm(g3, dt, s));
-        GemmArgs g4 = outfit_gemm(h, Ly.w_2, Fp, w.slab, w.slab_bytes);
-        g4.A = U; g4.C = X; g4.bias = Ly.b_2; g4.resid = X; g4.m_dev = md; g4.M = Ml; g4.N = D; g4.ldc = D; g4.ldr = D; g4.out_kind = OFX_OUT_F32;
+        GemmArgs g4 = slab_gemm(Ly.l2, Fp);
+        g4.A = U; g4.C = X; g4.resid = X; g4.m_dev = md; g4.M = Ml; g4.N = D; g4.ldc = D; g4.ldr = D; g4.out_kind = OFX_OUT_F32;
         if (fuse && !last) {                            // ... and the next layer's norm1
             const OutfitLayer& Nx = h->ol[l + 1];
             g4.ln_gamma = Nx.g1; g4.ln_beta = Nx.be1; g4.ln_out = w.H; g4.ln_ld = km * D; g4.ln_kind = okind; g4.ln_eps = d.ln_eps; g4.ln_done = &ln1_done;
@@ -719,13 +533,13 @@ extern "C" int ofx_cp_head(ofx_handle* h, const float* row0, int B, float* logit
 extern "C" int ofx_cir_head(ofx_handle* h, const float* row0, int B, float* emb, void* ws, size_t ws_bytes, ofx_stream stream) {
     OFX_REQUIRE(h && h->out_ready, OFX_ESTATE, "cir_head: outfit weights not packed");
     OFX_REQUIRE(row0 && emb && B > 0 && ws, OFX_EINVAL, "cir_head: bad argument");
-    const int D = h->d.d_model, km = h->ot_kmul;
+    const int D = h->d.d_model, km = a_kmul(h->ot_form);
     OFX_REQUIRE(ws_bytes >= (size_t)B * km * D * 2, OFX_EWORKSPACE, "cir_head: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     TRY(ofx_launch_pack_rows(row0, ws, B, B, D, D, D, km == 3 ? 1 : 0, h->ot_dtype, s));
-    GemmArgs g = outfit_gemm(h, h->cir_w, D, nullptr, 0);
+    GemmArgs g{};
+    use_cir_head(g, *h);
     g.A = ws; g.C = emb; g.M = B; g.N = D; g.ldc = D; g.out_kind = OFX_OUT_F32;
-    g.k_mult = 1;       // the head has always launched, and been recorded, as a plain GEMM over K = 3 D in bf16x3: from 6,144 rows on k_mult = 3 would select gemm_x3's kernel
     return ofx_launch_gemm(g, h->ot_dtype, s);
 }
 
@@ -742,8 +556,6 @@ int g_fuse_qkv = 1;     // ofx_tune(9, v): bit 0 (default on) = ViT layers with 
                         // (q | k | v stay in LDS); bit 1 (default OFF) = so do layers with split (hi, lo) weights, through its dual-weight variant: level with the
                         // persistent GEMM + attention-kernel pair in time, same error distribution, but on the 100-seed sweep it re-rolls two borderline small-logit weight draws from 8.0e-4 /
                         // 8.9e-4 to 1.05e-3 / 1.12e-3, so the default scheme keeps the dual-weight GEMM + attention-kernel pair
-int ofx_launch_fused_qkv_attn(const void* X, const void* Wqkv, const float* bias, const float* row_stat, const float* col_sum, void* out,
-                              int n_img, int S, int Wm, int heads, int ldx, int ldo, float scale, int op_dtype, hipStream_t s, bool w2 = false);
 int g_x3_vit_f32_attn = 0;   // ofx_tune(20, v), experiment: 1 = the three-product ViT keeps q | k | v in fp32 and runs the fp32 set attention (as the text tower does) instead of
                             // the MFMA attention on operand-rounded q | k | v - what the attention core's operand rounding costs under peaked attention
 int g_prune_q = 1;      // ofx_tune(8, v): 1 = the ViT's last layer computes queries for the CLS rows only
@@ -756,9 +568,9 @@ static int clip_layer(const ClipLayer& L, const ClipWs& w, int rows, int nseq, i
                       float eps, int causal, const int64_t* key_mask, int mask_ld, int dt, const int* pool_idx, hipStream_t s, bool pool_first) {
     // fused QKV projection + attention (non-pooled ViT layers: one 33..64-token tile per sequence, no mask): q | k | v never reach HBM;
     // split q | k | v weights: its dual-weight variant (ofx_tune(9, 3)), else the dual-weight GEMM + the attention kernel
-    const bool fused = (g_fuse_qkv & (L.qkv.mode == 3 ? 2 : 1)) && !pool_idx && !causal && !key_mask && S >= 33 && S <= 64 && (256 / S - 1) * S + 64 - 256 <= 16;   // (the kernel's key-row overshoot fits its 16 pad rows)
+    const bool fused = (g_fuse_qkv & (L.qkv.form == W_SPLIT ? 2 : 1)) && !pool_idx && !causal && !key_mask && S >= 33 && S <= 64 && (256 / S - 1) * S + 64 - 256 <= 16;   // (the kernel's key-row overshoot fits its 16 pad rows)
     if (fused) {
-        TRY(ofx_launch_fused_qkv_attn(w.XB, L.qkv.w, L.qkv.bias, w.S, L.qkv.col_sum, w.H, nseq, S, W, heads, W, W, 0.125f, dt, s, L.qkv.mode == 3));
+        TRY(ofx_launch_fused_qkv_attn(w.XB, L.qkv.w, L.qkv.bias, w.S, L.qkv.col_sum, w.H, nseq, S, W, heads, W, W, 0.125f, dt, s, L.qkv.form == W_SPLIT));
     } else {
         GemmArgs g1{}; g1.A = w.XB; g1.C = w.QKV; g1.row_stat = w.S; g1.M = rows; g1.N = 3 * W;
         g1.ldc = 3 * W; g1.act = OFX_ACT_NONE; g1.out_kind = OFX_OUT_OP;
@@ -908,9 +720,9 @@ static int vit_core(ofx_handle* h, const float* pixels, const RawImages* raw, in
                                   nullptr, w.U, d.vit_patch, dt, raw->ws, raw->ws_bytes, s));
         else
             TRY(ofx_launch_patchify(pixels + (size_t)n0 * px_per_img, w.U, n, d.vit_image, d.vit_patch, dt, s));
-        GemmArgs gp{}; gp.A = w.U; gp.W = h->v_patch_w; gp.C = w.QKV; gp.M = n * g * g; gp.N = W; gp.K = KP; gp.lda = KP; gp.ldc = W;
+        GemmArgs gp{}; gp.A = w.U; gp.C = w.QKV; gp.M = n * g * g; gp.N = W; gp.ldc = W;
         gp.act = OFX_ACT_NONE; gp.out_kind = OFX_OUT_F32;
-        if (h->vit_w2_mask & OFX_W2_PATCH) use_split(gp, h->v_patch_w, KP, h->f8_patch);
+        use_gemm(gp, h->v_patch, KP);
         TRY(ofx_launch_gemm(gp, dt, s));
         // the pre-LN kernel writes the stream the layers start from: X (three-product ViT), or the (hi, lo) pair + row statistics
         // (the carve leaves the other form's buffers null)
@@ -920,7 +732,8 @@ static int vit_core(ofx_handle* h, const float* pixels, const RawImages* raw, in
         const int pk = h->proj_x3 ? 3 : 1;            // the output tail in three products: post-LayerNorm rows [hi | lo | hi] x [hi | hi | lo]
         LnArgs ln{w.XP, nullptr, h->v_post_g, h->v_post_b, w.PL, n, W, pk * W, pk == 3 ? OFX_OUT_SPLIT3 : OFX_OUT_OP, d.ln_eps};
         TRY(ofx_launch_layernorm(ln, dt, s));
-        GemmArgs gj{}; gj.A = w.PL; gj.W = h->v_proj_w; gj.C = w.E; gj.M = n; gj.N = d.proj_dim; gj.K = pk * W; gj.k_mult = pk; gj.lda = pk * W; gj.ldc = d.proj_dim;
+        GemmArgs gj{}; gj.A = w.PL; gj.C = w.E; gj.M = n; gj.N = d.proj_dim; gj.ldc = d.proj_dim;
+        use_gemm(gj, h->v_proj, W);
         gj.act = OFX_ACT_NONE; gj.out_kind = OFX_OUT_F32; gj.slab = w.slab; gj.slab_bytes = w.slab_bytes;
         TRY(ofx_launch_gemm(gj, dt, s));
         TRY(ofx_launch_l2norm_store(w.E, emb + (size_t)n0 * emb_ld, n, d.proj_dim, emb_ld, emb_col, normalize, s));
@@ -977,7 +790,8 @@ extern "C" int ofx_clip_text_fwd(ofx_handle* h, const int64_t* ids, const int64_
     TRY(clip_layers(h->tl, w, rows, N, Tc, W, d.txt_mlp, d.txt_heads, d.txt_act, d.ln_eps, 1, attn_mask, T, dt, w.idx, s, false, x3));
     LnArgs ln{w.XP, nullptr, h->t_fin_g, h->t_fin_b, w.PL, N, W, pk * W, x3p ? OFX_OUT_SPLIT3 : OFX_OUT_OP, d.ln_eps};
     TRY(ofx_launch_layernorm(ln, dt, s));
-    GemmArgs gj{}; gj.A = w.PL; gj.W = h->t_proj_w; gj.C = w.E; gj.M = N; gj.N = d.proj_dim; gj.K = pk * W; gj.k_mult = pk; gj.lda = pk * W; gj.ldc = d.proj_dim;
+    GemmArgs gj{}; gj.A = w.PL; gj.C = w.E; gj.M = N; gj.N = d.proj_dim; gj.ldc = d.proj_dim;
+    use_gemm(gj, h->t_proj, W);
     gj.act = OFX_ACT_NONE; gj.out_kind = OFX_OUT_F32; gj.slab = w.slab; gj.slab_bytes = w.slab_bytes;
     TRY(ofx_launch_gemm(gj, dt, s));
     return ofx_launch_l2norm_store(w.E, emb, N, d.proj_dim, emb_ld, emb_col, normalize, s);
@@ -1113,7 +927,7 @@ static int cp_train_fwd_core(ofx_handle* h, const SetInput& in, int B, int L, fl
                              size_t ws_bytes, float dropout_p, unsigned seed, hipStream_t s, int head, const float* target_text) {
     OFX_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, OFX_EINVAL, "cp_train_fwd: dropout_p=%g", dropout_p);
     OFX_REQUIRE(h && h->out_ready, OFX_ESTATE, "cp_train_fwd: outfit weights not packed");
-    OFX_REQUIRE(h->ot_kmul == 1 && !h->ot_w2, OFX_ESTATE, "cp_train_fwd: training uses a single-product precision (bf16 / f16), not bf16x3 / f16w2");
+    OFX_REQUIRE(h->ot_form == W_PLAIN, OFX_ESTATE, "cp_train_fwd: training uses a single-product precision (bf16 / f16), not bf16x3 / f16w2");
     const ofx_model_desc& d = h->d;
     Bump tb(tape_mem, tape_bytes);
     Tape T;
@@ -1124,6 +938,7 @@ static int cp_train_fwd_core(ofx_handle* h, const SetInput& in, int B, int L, fl
     carve_set(h, wb, B, L, &w);
     OFX_REQUIRE(wb.ok, OFX_EWORKSPACE, "cp_train_fwd: workspace too small");
     const int D = d.d_model, Fp = h->ot_ffn_pad, dt = h->ot_dtype, M = B * (L + 1);
+    auto slab_gemm = [&](const PackedGemm& c, int K) { GemmArgs g{}; use_gemm(g, c, K); g.slab = w.slab; g.slab_bytes = w.slab_bytes; return g; };
     if (head == 1) {
         TRY(ofx_launch_cir_prefix(h->tgt_img_emb, target_text, T.prefix, B, D, s));
         TRY(build_set(h, in, T.prefix, D, T.cu, T.L[0].Xin, B, L, s));
@@ -1137,8 +952,8 @@ static int cp_train_fwd_core(ofx_handle* h, const SetInput& in, int B, int L, fl
         const bool last = l + 1 == d.n_layers;
         LnArgs ln{t.Xin, nullptr, Ly.g1, Ly.be1, t.H1, M, D, D, OFX_OUT_OP, d.ln_eps}; ln.stats = t.st1;
         TRY(ofx_launch_layernorm_dev(ln, m_dev, dt, s));
-        GemmArgs g1 = outfit_gemm(h, Ly.w_in, D, w.slab, w.slab_bytes);
-        g1.A = t.H1; g1.C = t.QKV; g1.bias = Ly.b_in; g1.m_dev = m_dev; g1.M = M; g1.N = 3 * D; g1.ldc = 3 * D; g1.out_kind = OFX_OUT_OP;      // q|k|v kept in the operand type
+        GemmArgs g1 = slab_gemm(Ly.in, D);
+        g1.A = t.H1; g1.C = t.QKV; g1.m_dev = m_dev; g1.M = M; g1.N = 3 * D; g1.ldc = 3 * D; g1.out_kind = OFX_OUT_OP;      // q|k|v kept in the operand type
         TRY(ofx_launch_gemm(g1, dt, s));
         if (g_train_mfma_attn) {           // varlen MFMA attention on the operand-type q|k|v (probabilities rounded to the operand type, as autocast SDPA does)
             AttnArgs at{t.QKV, t.O, nullptr, B, L + 1, d.n_head, 3 * D, D, D, 2 * D, 0, 0, 0.125f};
@@ -1158,24 +973,24 @@ static int cp_train_fwd_core(ofx_handle* h, const SetInput& in, int B, int L, fl
             TRY(ofx_launch_gather_rows(t.Xin, T.cu, T.pX, B, D * 4, D * 4, s));
             rows = B; md = nullptr; O = T.pO; Xin = T.pX;
         }
-        GemmArgs g2 = outfit_gemm(h, Ly.w_out, D, w.slab, w.slab_bytes);
-        g2.A = O; g2.C = t.Xmid; g2.bias = Ly.b_out; g2.resid = Xin; g2.m_dev = md; g2.M = rows; g2.N = D; g2.ldc = D; g2.ldr = D; g2.out_kind = OFX_OUT_F32;
+        GemmArgs g2 = slab_gemm(Ly.out, D);
+        g2.A = O; g2.C = t.Xmid; g2.resid = Xin; g2.m_dev = md; g2.M = rows; g2.N = D; g2.ldc = D; g2.ldr = D; g2.out_kind = OFX_OUT_F32;
         g2.drop = make_drop(dropout_p, seed, 4 * l + 1);
         TRY(ofx_launch_gemm(g2, dt, s));
         LnArgs ln2{t.Xmid, nullptr, Ly.g2, Ly.be2, t.H2, rows, D, D, OFX_OUT_OP, d.ln_eps}; ln2.stats = t.st2;
         TRY(ofx_launch_layernorm_dev(ln2, md, dt, s));
-        GemmArgs g3 = outfit_gemm(h, Ly.w_1, D, w.slab, w.slab_bytes);
-        g3.A = t.H2; g3.C = t.A; g3.bias = Ly.b_1; g3.aux_out = t.Upre; g3.m_dev = md; g3.M = rows; g3.N = Fp; g3.ldc = Fp; g3.act = d.outfit_act; g3.out_kind = OFX_OUT_OP;
+        GemmArgs g3 = slab_gemm(Ly.l1, D);
+        g3.A = t.H2; g3.C = t.A; g3.aux_out = t.Upre; g3.m_dev = md; g3.M = rows; g3.N = Fp; g3.ldc = Fp; g3.act = d.outfit_act; g3.out_kind = OFX_OUT_OP;
         g3.drop = make_drop(dropout_p, seed, 4 * l + 2);
         TRY(ofx_launch_gemm(g3, dt, s));
-        GemmArgs g4 = outfit_gemm(h, Ly.w_2, Fp, w.slab, w.slab_bytes);
-        g4.A = t.A; g4.C = Xout; g4.bias = Ly.b_2; g4.resid = t.Xmid; g4.m_dev = md; g4.M = rows; g4.N = D; g4.ldc = D; g4.ldr = D; g4.out_kind = OFX_OUT_F32;
+        GemmArgs g4 = slab_gemm(Ly.l2, Fp);
+        g4.A = t.A; g4.C = Xout; g4.resid = t.Xmid; g4.m_dev = md; g4.M = rows; g4.N = D; g4.ldc = D; g4.ldr = D; g4.out_kind = OFX_OUT_F32;
         g4.drop = make_drop(dropout_p, seed, 4 * l + 3);
         TRY(ofx_launch_gemm(g4, dt, s));
     }
     if (head == 1) {                                                // cir_ffn = Linear(D, d_embed, bias=False): no dropout (outfit_x.py:61-63)
         TRY(ofx_launch_pack_rows(T.row0, T.row0b, B, B, D, D, D, 0, dt, s));
-        GemmArgs g = outfit_gemm(h, h->cir_w, D, w.slab, w.slab_bytes);
+        GemmArgs g = slab_gemm(h->cir, D);
         g.A = T.row0b; g.C = logits; g.M = B; g.N = D; g.ldc = D; g.out_kind = OFX_OUT_F32;
         return ofx_launch_gemm(g, dt, s);
     }
@@ -1219,7 +1034,7 @@ static int set_train_bwd_core(ofx_handle* h, void* tape_mem, size_t tape_bytes, 
     // per-layer completion events (data-parallel overlap): consumed by this call whatever its outcome
     std::vector<hipEvent_t> layer_ev;
     if (h) layer_ev.swap(h->bwd_events);
-    OFX_REQUIRE(h && h->out_ready && h->ot_kmul == 1 && !h->ot_w2, OFX_ESTATE, "cp_train_bwd: needs packed single-product weights");
+    OFX_REQUIRE(h && h->out_ready && h->ot_form == W_PLAIN, OFX_ESTATE, "cp_train_bwd: needs packed single-product weights");
     OFX_REQUIRE(tape_mem && dlogits && (grads || grad_ptrs) && ws && B > 0, OFX_EINVAL, "cp_train_bwd: bad argument");
     OFX_REQUIRE(h->d.outfit_act == OFX_ACT_MISH, OFX_ESTATE, "cp_train_bwd: only the Mish activation has a backward epilogue");
     const ofx_model_desc& d = h->d;
@@ -1250,10 +1065,11 @@ static int set_train_bwd_core(ofx_handle* h, void* tape_mem, size_t tape_bytes, 
     auto wgrad = [&](int rows, const int* md, const void* dY, int n_w, const void* X, int k_w, float* out, int ldc = 0, int mv = 0, int nv = 0) {
         return ofx_launch_gemm_tn(dY, n_w, X, k_w, out, ldc ? ldc : k_w, n_w, k_w, rows, md, w.slab, w.slab_bytes, dt, s, mv, nv, acc);
     };
-    // dgrad: C[rows, n] = epilogue(dY[rows, k] Wt[n, k]^T), Wt the W^T operand copy of the pack
-    auto dgrad = [&](int rows, const int* md, const void* dY, const void* Wt, void* C, int n, int k, int out_kind = OFX_OUT_F32, int act = OFX_ACT_NONE,
+    // dgrad: C[rows, n] = epilogue(dY[rows, k] Wt[n, k]^T), Wt the record's W^T operand copy: a plain weight, no bias
+    auto dgrad = [&](int rows, const int* md, const void* dY, const PackedGemm& rec, void* C, int n, int k, int out_kind = OFX_OUT_F32, int act = OFX_ACT_NONE,
                      const float* resid = nullptr, const DropArgs& drop = DropArgs()) {
-        GemmArgs g = outfit_gemm(h, Wt, k, w.slab, w.slab_bytes);
+        PackedGemm wt; wt.w = rec.wt;
+        GemmArgs g{}; use_gemm(g, wt, k); g.slab = w.slab; g.slab_bytes = w.slab_bytes;
         g.A = dY; g.C = C; g.M = rows; g.N = n; g.ldc = n; g.out_kind = out_kind; g.act = act; g.resid = resid; g.ldr = resid ? n : 0; g.m_dev = md; g.drop = drop;
         return ofx_launch_gemm(g, dt, s);
     };
@@ -1265,7 +1081,7 @@ static int set_train_bwd_core(ofx_handle* h, void* tape_mem, size_t tape_bytes, 
         // y = row0 Wc^T:  dWc = dy^T row0 (TN GEMM over the B rows), d row0 = dy Wc
         TRY(ofx_launch_pack_rows(dlogits, w.dyb, B, B, D, D, D, 0, dt, s));
         TRY(wgrad(B, nullptr, w.dyb, D, T.row0b, D, G(4)));
-        TRY(dgrad(B, nullptr, w.dyb, h->cir_w_t, w.d_row0, D, D));
+        TRY(dgrad(B, nullptr, w.dyb, h->cir, w.d_row0, D, D));
         TRY(ofx_launch_cp_head_bwd(nullptr, w.d_row0, nullptr, w.d_row0, w.gXb, nullptr, B, D, dt, nodrop, site(lastl, 3), s));
     } else {
         TRY(ofx_launch_cp_head_bwd(dlogits, h->cp_w, nullptr, w.d_row0, w.gXb, G(3), B, D, dt, site(d.n_layers, 0), site(lastl, 3), s, acc));
@@ -1286,18 +1102,18 @@ static int set_train_bwd_core(ofx_handle* h, void* tape_mem, size_t tape_bytes, 
         // ---- FFN branch: Xout = Xmid + mish(H2 W1^T + b1) W2^T + b2        (gXb = operand copy of dXout)
         if (last) TRY(ofx_launch_colsum(w.gXb, 1, D, nullptr, nullptr, G(g0 + 7), nullptr, nullptr, D, w.part, D, nullptr, B, dt, s, 0, acc));   // db2: no layer above supplies it
         TRY(wgrad(rows, md, w.gXb, D, t.A, Fp, G(g0 + 6), Fv, D, Fv));                                                                 // dW2 [D, Fp]
-        TRY(dgrad(rows, md, w.gXb, Ly.w_2_t, w.dU, Fp, D, OFX_OUT_OP, OFX_ACT_MISH_GRAD, t.Upre, site(l, 2)));                          // dU = (dXout W2) * mish'(Upre)
+        TRY(dgrad(rows, md, w.gXb, Ly.l2, w.dU, Fp, D, OFX_OUT_OP, OFX_ACT_MISH_GRAD, t.Upre, site(l, 2)));                          // dU = (dXout W2) * mish'(Upre)
         TRY(ofx_launch_colsum(w.dU, 1, Fp, nullptr, nullptr, G(g0 + 5), nullptr, nullptr, Fp, w.part, Fp, md, rows, dt, s, Fv, acc));    // db1
         TRY(wgrad(rows, md, w.dU, Fp, t.H2, D, G(g0 + 4), D, Fv, D));                                                                  // dW1 [Fp, D]
-        TRY(dgrad(rows, md, w.dU, Ly.w_1_t, w.dH, D, Fp));                                                                             // dH2
+        TRY(dgrad(rows, md, w.dU, Ly.l1, w.dH, D, Fp));                                                                             // dH2
         TRY(ofx_launch_ln_bwd(w.dH, t.Xmid, t.st2, Ly.g2, dXout, nullptr, dX2, w.gXb, G(g0 + 10), G(g0 + 11), G(g0 + 3), w.part, D, md, rows, dt, site(l, 1), s, acc));   // dXmid (+ dbo)
         // ---- attention branch: Xmid = Xin + O Wo^T + bo
         TRY(wgrad(rows, md, w.gXb, D, O, D, G(g0 + 2)));                                                                               // dWo [D, D]
-        TRY(dgrad(rows, md, w.gXb, Ly.w_out_t, w.dO, D, D));                                                                           // dO
+        TRY(dgrad(rows, md, w.gXb, Ly.out, w.dO, D, D));                                                                           // dO
         TRY(attention_bwd(t.QKV, w.dO, w.gQb, T.cu, B, d.n_head, D, L + 1, 0.125f, dt, site(l, 0), last ? 1 : 0, s));                  // (last layer: only row 0 has a dO, all rows get dK, dV)
         TRY(ofx_launch_colsum(w.gQb, 1, 3 * D, nullptr, nullptr, G(g0 + 1), nullptr, nullptr, 3 * D, w.part, 3 * D, m_dev, M, dt, s, 0, acc));   // dbin
         TRY(wgrad(M, m_dev, w.gQb, 3 * D, t.H1, D, G(g0 + 0)));                                                                        // dWin [3D, D]
-        TRY(dgrad(M, m_dev, w.gQb, Ly.w_in_t, w.dH, D, 3 * D));                                                                        // dH1
+        TRY(dgrad(M, m_dev, w.gQb, Ly.in, w.dH, D, 3 * D));                                                                        // dH1
         // dXin = LayerNorm-1 backward + dXmid (last layer: at the prefix rows); its column sums are the bias gradient of the layer
         // below's linear2
         TRY(ofx_launch_ln_bwd(w.dH, t.Xin, t.st1, Ly.g1, dX2, last ? w.rowmap : nullptr, dX, w.gXb, G(g0 + 8), G(g0 + 9), l > 0 ? G(g0 - 12 + 7) : nullptr, w.part, D,
@@ -1403,8 +1219,6 @@ extern "C" int ofx_adamw_step(const ofx_opt_segment* segments, int n_segments, f
 }
 
 // ------------------------------------------------------------------------------------- tuning
-extern int g_topk_filter, g_epi_direct;
-extern int g_gemm_kernel, g_gemm_splitk, g_w2_persist, g_x3_kernel, g_x3_persist;
 extern "C" int ofx_tune(int knob, int value) {
     ++g_config_generation;
     switch (knob) {
@@ -1545,8 +1359,9 @@ static int fold_gemm_args(GemmArgs& g, const char* who, const void* A, const voi
     OFX_REQUIRE(w_form >= 0 && w_form <= 2 && op_dtype_ok(op_dtype) && (w_form != 2 || op_dtype == OFX_F16), OFX_EINVAL,
                 "%s: w_form = %d (0 plain, 1 split, 2 split + fp8 lo copy, f16 only), op_dtype = %d", who, w_form, op_dtype);
     OFX_REQUIRE(A && W && (w_form != 2 || (W8 && scale8)), OFX_EINVAL, "%s: NULL operand", who);
-    g.A = A; g.W = W; g.K = w_form ? 2 * K : K;
-    if (w_form) g.a_wrap = K;
+    const WeightForm f = w_form ? W_SPLIT : W_PLAIN;
+    g.A = A; g.W = W; g.K = w_kmul(f) * K;
+    if (f == W_SPLIT) g.a_wrap = K;
     if (w_form == 2) { g.W8 = W8; g.w8_scale = scale8; }
     return OFX_OK;
 }

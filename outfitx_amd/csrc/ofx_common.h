@@ -417,3 +417,50 @@ struct SetAttnArgs {
     int splits = 1; size_t plane = 0; const float* bias = nullptr;
 };
 int ofx_launch_set_attention(const SetAttnArgs& a, int op_dtype, hipStream_t s);
+int ofx_launch_fused_qkv_attn(const void* X, const void* Wqkv, const float* bias, const float* row_stat, const float* col_sum, void* out,
+                              int n_img, int S, int Wm, int heads, int ldx, int ldo, float scale, int op_dtype, hipStream_t s, bool w2 = false);
+
+// ---- pack helpers, training backward, losses, optimizer, scoring
+int ofx_launch_multi_copy(const void* table_host, int n, hipStream_t s);
+int ofx_launch_fill_f32(float* p, size_t n, float v, hipStream_t s);
+int ofx_launch_transpose_cast(const float* src, void* dst, int R, int C, int ldd, int op_dtype, hipStream_t s, void* row_dst = nullptr, int ld_row = 0);
+size_t ofx_colsum_part_floats(int C);
+int ofx_launch_colsum(const void* x, int x_kind, int ld, const int* gather, const float* row_scale, float* out0, float* out1, float* out2, int seg,
+                      float* part, int C, const int* m_dev, int M, int op_dtype, hipStream_t s, int valid = 0, int accumulate = 0);
+size_t ofx_ln_bwd_part_floats(int D);
+int ofx_launch_row_map(const int* cu, int* map, int B, int M, hipStream_t s);
+int ofx_launch_ln_bwd(const float* dy, const float* x, const float* stats, const float* gamma, const float* add, const int* add_map, float* dx_out, void* dx_op,
+                      float* dgamma, float* dbeta, float* dcols, float* part, int D, const int* m_dev, int M, int op_dtype, const DropArgs& drop, hipStream_t s,
+                      int accumulate = 0);
+int ofx_launch_set_attention_bwd(const void* qkv, const float* d_o, void* dqkv, const int* cu, int nseq, int n_head, int D, int max_len,
+                                 float scale, int op_dtype, const DropArgs& drop, int only_row0, hipStream_t s);
+int ofx_launch_set_attention_bwd_mfma(const void* qkv, const float* d_o, void* dqkv, const int* cu, int nseq, int n_head, int D, int max_len,
+                                      float scale, int op_dtype, const DropArgs& drop, int only_row0, hipStream_t s);
+int ofx_launch_drop_rows(float* x, int rows, int cols, const DropArgs& d, hipStream_t s);
+int ofx_launch_focal_loss(const float* logits, const float* labels, int B, float alpha, float gamma, float upstream, float* loss, float* dlogits, hipStream_t s,
+                          int reduction = 1, float* per_elem = nullptr);
+size_t ofx_set_rank_loss_ws(int B, int K);
+int ofx_launch_set_rank_loss(const float* y, const float* y_hat, const float* neg, const uint8_t* mask, int B, int K, int D, float margin, float upstream,
+                             float* loss, float* dy_hat, float* d_pos, float* d_neg, void* ws, hipStream_t s);
+int ofx_launch_set_rank_loss_indexed(const float* table, int ld, int n_table, const int* pos_index, const int* neg_index, const float* y_hat, int B, int K,
+                                     int D, float margin, float upstream, float* loss, float* dy_hat, float* d_pos, float* d_neg, void* ws, hipStream_t s);
+size_t ofx_adamw_step_ws(long long n_arena);
+int ofx_launch_adamw_step(const ofx_opt_segment* segments, int n_segments, float* grad, float* exp_avg, float* exp_avg_sq, long long n_arena,
+                          float* step, double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm, double grad_scale,
+                          float* grad_norm, int* skipped, void* ws, hipStream_t s);
+int ofx_launch_cp_head_bwd(const float* dlogits, const float* w_or_rows, const int* cu, float* dX, void* dXb, float* db, int B, int D, int op_dtype,
+                           const DropArgs& head, const DropArgs& below, hipStream_t s, int accumulate = 0);
+int ofx_launch_fitb(const float* y, const float* cand, int B, int C, int D, int64_t* idx, float* dist, hipStream_t s);
+int ofx_launch_fitb_indexed(const float* table, int ld, int n_table, const int* cand_index, const float* y, int B, int C, int D, const int64_t* answer,
+                            int64_t* idx, float* dist, int* n_correct, hipStream_t s);
+int ofx_launch_l2_topk(const float* Q, const float* P, int nq, int np, int D, int k, int64_t index_base, int64_t* idx,
+                       float* dist, void* ws, size_t ws_bytes, hipStream_t s);
+size_t ofx_l2_topk_ws(int nq, int np);
+int ofx_launch_l2_topk_grouped(const float* Q, const float* P, int nq, int np, int D, int k, const int* panels, int n_panels, int max_group_rows,
+                               const int64_t* gt, int64_t* idx, float* dist, int* gt_pos, void* ws, size_t ws_bytes, hipStream_t s);
+int ofx_launch_topk_merge(const int64_t* idx_in, const float* dist_in, int parts, int nq, int k, int64_t* idx, float* dist,
+                          hipStream_t s);
+
+// ---- ofx_tune knobs defined outside api.hip (gemm.hip, scoring.hip)
+extern int g_topk_filter, g_epi_direct;
+extern int g_gemm_kernel, g_gemm_splitk, g_w2_persist, g_x3_kernel, g_x3_persist;

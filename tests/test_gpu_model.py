@@ -1144,3 +1144,81 @@ def test_cfg2_bench_batch_within_1e3_of_the_reference(wseed, scheme=None):
     assert e < 1e-3, e
     del m
     torch.cuda.empty_cache()
+
+
+def _repack_set_weights(seed, D, F, n_layers):
+    """Outfit-transformer tensors in pack order, fresh from a seed: O(1) rows scaled by 1 / sqrt(fan-in)."""
+    g = np.random.default_rng(seed)
+    mat = lambda n, k: torch.from_numpy((g.standard_normal((n, k), dtype=np.float32) / np.float32(np.sqrt(k)))).cuda()
+    vec = lambda n, base=0.0: torch.from_numpy(base + 0.1 * g.standard_normal(n, dtype=np.float32)).cuda()
+    out = [vec(D), vec(D // 2), vec(D), vec(1), mat(D, D)]
+    for _ in range(n_layers):
+        out += [mat(3 * D, D), vec(3 * D), mat(D, D), vec(D), mat(F, D), vec(F), mat(D, F), vec(D), vec(D, 1.0), vec(D), vec(D, 1.0), vec(D)]
+    return out
+
+
+def test_repack_into_a_live_arena_equals_a_fresh_pack():
+    """A second pack reuses the arena the first one allocated (same pointers; zero padding is written by the first pack only), placed by
+    the same layout walk: it must leave exactly what packing a fresh handle leaves.  Outfit transformer d_model 512, 8 heads, 2 layers,
+    d_ffn 200 - rows / columns 200..255 of the FFN weights are padding - on 8 outfits of up to 4 items, in the four outfit precisions:
+    pack A, run, pack B into the same handle, run, and compare bit for bit with a fresh handle packed with B.  Then the same for the
+    vision and the text tower, in the default scheme and in f16x3."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a HIP device")
+    from outfitx_amd import _lib as L
+    from outfitx_amd.encoders import ClipTextParams, ClipVisionParams
+    from outfitx_amd.engine import Engine
+    dev = torch.device("cuda", 0)
+    D, F, NL, B, Lq = 512, 200, 2, 8, 4
+    g = np.random.default_rng(5)
+    x = torch.from_numpy(g.standard_normal((B, Lq, D), dtype=np.float32)).cuda()
+    mask = torch.from_numpy(np.arange(Lq)[None, :] >= g.integers(1, Lq + 1, size=B)[:, None]).cuda()
+    wa, wb = _repack_set_weights(1, D, F, NL), _repack_set_weights(2, D, F, NL)
+
+    def set_engine(prec):
+        d = L.default_desc()
+        d.d_model, d.n_head, d.n_layers, d.d_ffn = D, D // 64, NL, F
+        return Engine(dev, d, precision=prec)
+
+    def run_set(eng):
+        row0 = eng.set_encoder((x, mask))
+        return row0, eng.cp_head(row0)
+
+    for prec in ("bf16x3", "f16w2", "f16", "bf16"):
+        live = set_engine(prec)
+        live.pack_outfit(wa)
+        a = run_set(live)
+        live.pack_outfit(wb)
+        b = run_set(live)
+        fresh = set_engine(prec)
+        fresh.pack_outfit(wb)
+        want = run_set(fresh)
+        assert torch.isfinite(want[1]).all() and not torch.equal(a[1], b[1]), prec
+        assert torch.equal(b[0], want[0]) and torch.equal(b[1], want[1]), prec
+
+    px = cu(synth.pixel_values(3, 2))
+    ids, att = synth.token_batch(3, 2, 64, 8)
+    towers = []
+    for seed in (1, 2):
+        v, t = ClipVisionParams(), ClipTextParams()
+        v.load_state_dict({k: torch.from_numpy(w) for k, w in synth.vision_weights(seed).items()}, strict=True)
+        t.load_state_dict({k: torch.from_numpy(w) for k, w in synth.text_weights(seed).items()}, strict=True)
+        towers.append(([p.detach().cuda() for p in v.pack_list()], [p.detach().cuda() for p in t.pack_list()]))
+
+    def run_towers(eng):
+        out = torch.zeros(2, 1024, device=dev)
+        eng.vit(px, out, 0, False)
+        eng.text(cu(ids), cu(att), out, 512, False)
+        return out
+
+    for scheme in (DEFAULT_TOWERS, "f16x3"):
+        outs = []
+        for packs in (towers, towers[1:]):          # the live handle packs A then B; the fresh one packs B alone
+            eng = Engine(dev, tower_precision=scheme)
+            for vis, txt in packs:
+                eng.pack_vision(vis)
+                eng.pack_text(txt)
+                outs.append(run_towers(eng))
+        a, b, want = outs
+        assert torch.isfinite(want).all() and not torch.equal(a, want), scheme
+        assert torch.equal(b, want), scheme
