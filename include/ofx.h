@@ -557,10 +557,50 @@ int ofx_vit_embed_ln(const float* patch_out, const float* cls, const float* pos,
 int ofx_gather_hilo(const void* hi, const void* lo, const int* idx, float* dst, int rows, int W, int op_dtype, ofx_stream stream);
 int ofx_layernorm(const float* x, const int* row_idx, const float* gamma, const float* beta, void* y, int rows,
                   int D, int ldy, int out_kind, int op_dtype, float eps, ofx_stream stream);
+/* MFMA attention over fixed-length sequences of 1 .. 64 rows (the CLIP towers): qkv [nseq * seq_len, ld] operand type, q at column 0, k at
+ * k_off, v at v_off, head h at + 64 h; out [nseq * seq_len, ldo] operand type = softmax(q k^T * scale + mask) v, columns n_head * 64 .. ldo - 1
+ * not written.  key_mask: optional int64 [nseq, mask_ld], 0 = key ignored; causal: key j > query i ignored.  ld, k_off, v_off multiples of 8,
+ * ldo of 4 (OFX_ESHAPE); qkv 16-byte and out 8-byte aligned (OFX_EINVAL).
+ * A FULLY MASKED QUERY ROW (key 0 masked under the causal mask; a sequence whose mask is all zero) has probabilities 0, so its output row is
+ * exactly 0 - in all three copies of a split3 row.  This is the library's own rule for both attention kernels (this one and the fp32 one
+ * below); HF's result for such a row depends on its version. */
 int ofx_attention(const void* qkv, void* out, const int64_t* key_mask, int nseq, int seq_len, int n_head, int ld,
                   int ldo, int k_off, int v_off, int mask_ld, int causal, float scale, int op_dtype, ofx_stream stream);
+/* ofx_attention plus the two fields of its launcher that ofx_attention cannot set, as the towers launch it:
+ *   only_row0 != 0: only query row 0 of every sequence (row b * seq_len of out) is computed and stored, the same bits as the full call's;
+ *     every other row of out is not written (the pruned last ViT layer).
+ *   split3_w = W > 0: out rows are [hi(W) | lo(W) | hi(W)] (the A operand of a three-product GEMM): hi = cast(o) at columns 64 h .., lo =
+ *     cast(o - hi) at W + 64 h .., hi again at 2 W + 64 h ..; W a multiple of 8, ldo >= 3 W (OFX_ESHAPE); columns 3 W .. ldo - 1 and, where
+ *     W > n_head * 64, the columns between the copies are not written.  split3_w = 0: ofx_attention's rows.
+ * NULL qkv / out and an op_dtype that is not OFX_BF16 / OFX_F16 are OFX_EINVAL; split3_w < 0, a key_mask with mask_ld < seq_len and what
+ * ofx_attention refuses are OFX_ESHAPE.  A refused call launches nothing. */
+int ofx_attention_ex(const void* qkv, void* out, const int64_t* key_mask, int nseq, int seq_len, int n_head, int ld, int ldo, int k_off,
+                     int v_off, int mask_ld, int causal, int only_row0, int split3_w, float scale, int op_dtype, ofx_stream stream);
+/* fp32 VALU attention over varlen sets (the outfit transformer): qkv fp32 [rows, 3 D] (q | k | v), sequence b = rows cu_seqlens[b] ..
+ * cu_seqlens[b + 1] (1 .. max_len <= 64 of them), D = n_head * 64.  out [rows, ldo]: out_kind 0 fp32 | 1 operand type | 2 [hi(D) | lo(D) |
+ * hi(D)] (ldo >= 3 D); operand-type rows need ldo % 8 == 0.  only_row0: query row 0 of every set alone is computed and stored. */
 int ofx_set_attention(const float* qkv, void* out, const int* cu_seqlens, int nseq, int n_head, int D, int ldo,
                       int out_kind, int max_len, int only_row0, float scale, int op_dtype, ofx_stream stream);
+/* ofx_set_attention reading q | k | v from the QKV GEMM's split-K slabs (small-batch scores): slabs fp32 [splits][rows, 3 D], slab s at
+ * slabs + s * plane_floats, bias fp32 [3 D]; element = (((s0 + s1) + ...) + s_{splits-1}) + bias, fp32 additions in exactly that order, so
+ * the result equals ofx_set_attention on that array bit for bit.  Under only_row0 q of rows > 0 is not read.  splits = 1 is ofx_set_attention
+ * itself (bias and plane_floats unused).  slabs, bias and out 16-byte aligned, plane_floats a multiple of 4, no NULL among slabs, out,
+ * cu_seqlens, nseq >= 1, splits >= 1, op_dtype OFX_BF16 / OFX_F16 (else OFX_EINVAL); with splits > 1 the launcher's own rules: max_len <= 32,
+ * bias given, plane_floats > 0 (OFX_EINVAL).  out_kind outside 0 .. 2 and what ofx_set_attention refuses are OFX_ESHAPE.  A refused call
+ * launches nothing. */
+int ofx_set_attention_slabs(const float* slabs, size_t plane_floats, int splits, const float* bias, void* out, const int* cu_seqlens, int nseq,
+                            int n_head, int D, int ldo, int out_kind, int max_len, int only_row0, float scale, int op_dtype, ofx_stream stream);
+/* Split-K second pass fused with the LayerNorm behind it (small batches of the outfit transformer), for the rows r < min(*m_dev, rows)
+ * (m_dev NULL: rows):  x[r] = ((((s0[r] + s1[r]) + ...) + bias) + resid[r]), fp32 additions in that order, then y[r] = LN(x[r]) gamma + beta
+ * with two-pass fp32 statistics (agrees with ofx_layernorm to fp32 rounding, not bit for bit: the sums take another order).
+ * slab fp32 [splits][rows, D], slab s at slab + s * plane_floats; bias [D] and resid [rows, ldr] optional, resid may alias x; x fp32
+ * [rows, ldx]; y [rows, ldy]: out_kind 0 fp32 | 1 operand type | 2 [hi(D) | lo(D) | hi(D)] (ldy >= 3 D).  Columns D .. of x, the columns of y
+ * behind its D (3 D) and all rows at or past the live count are not written.  D in {512, 768, 1024}, ldx, ldr, ldy multiples of 4 and >= D,
+ * rows >= 1, splits >= 1, slabs that do not overlap (OFX_ESHAPE); NULL slab / x / gamma / beta / y, pointers off 16 bytes (y: 8 for the
+ * operand-type kinds, m_dev: 4), plane_floats % 4 != 0, a bad op_dtype: OFX_EINVAL.  A refused call launches nothing. */
+int ofx_splitk_reduce_ln(const float* slab, size_t plane_floats, int splits, const float* bias, const float* resid, int ldr, float* x, int ldx,
+                         const float* gamma, const float* beta, void* y, int ldy, int out_kind, float eps, int rows, const int* m_dev, int D,
+                         int op_dtype, ofx_stream stream);
 /* The attention kernels of the training step, one call each (both settings of knob 7).  q | k | v and dqkv are operand-type rows [rows, 3 D]
  * (the tape's layout), sequence b = rows cu_seqlens[b] .. cu_seqlens[b + 1] (1 .. max_len of them, never none), head h at columns 64 h.
  * Dropout on the attention probabilities is site `site` of (dropout_p, seed): mask element (b * n_head + h, query * 32 + key), the values
@@ -589,7 +629,9 @@ int ofx_fused_qkv_attention(const void* X, const void* Wqkv, const float* bias, 
 int ofx_fused_qkv_attention_w2(const void* X, const void* Wqkv2, const float* bias, const float* row_stat, const float* col_sum, void* out,
                                int nseq, int seq_len, int width, int n_head, int ldx, int ldo, float scale, int op_dtype, ofx_stream stream);
 /* fp32-arithmetic attention over fixed-length sequences of <= 64 rows (the three-product CLIP text tower): qkv fp32 [nseq * seq_len, 3 D]
- * (q | k | v), HF's causal AND key-padding mask (key_mask [nseq, mask_ld] int64, 0 = ignored, may be NULL); out as ofx_set_attention. */
+ * (q | k | v), HF's causal AND key-padding mask (key_mask [nseq, mask_ld] int64, 0 = ignored, may be NULL); out as ofx_set_attention.
+ * A fully masked query row has probabilities 0: its output row is exactly 0, in all three copies of a split3 row (the library's own rule, as
+ * under ofx_attention; HF's result for such a row depends on its version). */
 int ofx_attention_f32(const float* qkv, void* out, const int64_t* key_mask, int nseq, int seq_len, int n_head, int D, int ldo, int out_kind,
                       int mask_ld, int causal, float scale, int op_dtype, ofx_stream stream);
 /* fp32 [rows, cols] -> operand type; mode 0 plain, 1 [hi|lo|hi] (activation split), 2 [hi|hi|lo] (weight split) */

@@ -1446,6 +1446,33 @@ extern "C" int ofx_attention(const void* qkv, void* out, const int64_t* key_mask
     AttnArgs a{qkv, out, key_mask, nseq, seq_len, n_head, ld, ldo, k_off, v_off, mask_ld, causal, scale};
     return ofx_launch_attention_mfma(a, op_dtype, (hipStream_t)stream);
 }
+extern "C" int ofx_attention_ex(const void* qkv, void* out, const int64_t* key_mask, int nseq, int seq_len, int n_head, int ld, int ldo, int k_off,
+                                int v_off, int mask_ld, int causal, int only_row0, int split3_w, float scale, int op_dtype, ofx_stream stream) {
+    OFX_REQUIRE(qkv && out && op_dtype_ok(op_dtype), OFX_EINVAL, "attention_ex: bad argument (a NULL pointer or op_dtype = %d)", op_dtype);
+    OFX_REQUIRE(split3_w >= 0 && (!key_mask || mask_ld >= seq_len), OFX_ESHAPE, "attention_ex: split3_w=%d mask_ld=%d", split3_w, mask_ld);
+    AttnArgs a{qkv, out, key_mask, nseq, seq_len, n_head, ld, ldo, k_off, v_off, mask_ld, causal ? 1 : 0, scale};
+    a.only_row0 = only_row0 ? 1 : 0; a.split3_w = split3_w;
+    return ofx_launch_attention_mfma(a, op_dtype, (hipStream_t)stream);
+}
+extern "C" int ofx_set_attention_slabs(const float* slabs, size_t plane_floats, int splits, const float* bias, void* out, const int* cu_seqlens, int nseq,
+                                       int n_head, int D, int ldo, int out_kind, int max_len, int only_row0, float scale, int op_dtype, ofx_stream stream) {
+    OFX_REQUIRE(slabs && out && cu_seqlens && nseq > 0 && n_head > 0 && splits >= 1 && op_dtype_ok(op_dtype) && aligned_to(15, {slabs, bias, out}) && plane_floats % 4 == 0,
+                OFX_EINVAL, "set_attention_slabs: bad argument (a NULL or misaligned pointer, nseq = %d, splits = %d, op_dtype = %d)", nseq, splits, op_dtype);
+    OFX_REQUIRE(out_kind >= 0 && out_kind <= 2, OFX_ESHAPE, "set_attention_slabs: out_kind=%d", out_kind);
+    SetAttnArgs a{slabs, out, cu_seqlens, nseq, n_head, D, ldo, out_kind, max_len, only_row0 ? 1 : 0, scale};
+    a.splits = splits; a.plane = plane_floats; a.bias = bias;
+    return ofx_launch_set_attention(a, op_dtype, (hipStream_t)stream);
+}
+extern "C" int ofx_splitk_reduce_ln(const float* slab, size_t plane_floats, int splits, const float* bias, const float* resid, int ldr, float* x, int ldx,
+                                    const float* gamma, const float* beta, void* y, int ldy, int out_kind, float eps, int rows, const int* m_dev, int D,
+                                    int op_dtype, ofx_stream stream) {
+    OFX_REQUIRE(slab && x && gamma && beta && y && op_dtype_ok(op_dtype) && aligned_to(15, {slab, bias, resid, x, gamma, beta}) && aligned_to(out_kind == 0 ? 15 : 7, {y}) && aligned_to(3, {m_dev}) &&
+                    plane_floats % 4 == 0,
+                OFX_EINVAL, "splitk_reduce_ln: bad argument (a NULL or misaligned pointer or op_dtype = %d)", op_dtype);
+    OFX_REQUIRE(out_kind >= 0 && out_kind <= 2 && (splits <= 1 || plane_floats >= (size_t)rows * D), OFX_ESHAPE, "splitk_reduce_ln: out_kind=%d, or slabs that overlap", out_kind);
+    SplitKLnArgs a{slab, plane_floats, splits, bias, resid, ldr, x, ldx, gamma, beta, y, ldy, out_kind, eps, rows, D, m_dev};
+    return ofx_launch_splitk_reduce_ln(a, op_dtype, (hipStream_t)stream);
+}
 extern "C" int ofx_fused_qkv_attention(const void* X, const void* Wqkv, const float* bias, const float* row_stat, const float* col_sum, void* out,
                                        int nseq, int seq_len, int width, int n_head, int ldx, int ldo, float scale, int op_dtype, ofx_stream stream) {
     return ofx_launch_fused_qkv_attn(X, Wqkv, bias, row_stat, col_sum, out, nseq, seq_len, width, n_head, ldx, ldo, scale, op_dtype, (hipStream_t)stream);

@@ -91,7 +91,7 @@ __device__ __forceinline__ void attn_softmax_p(typename OpT<T>::v8 (&pf)[NT][att
             }
         sum += __shfl_xor(sum, 16, 64);
         sum += __shfl_xor(sum, 32, 64);
-        const float inv = __builtin_amdgcn_rcpf(sum);
+        const float inv = sum > 0.f ? __builtin_amdgcn_rcpf(sum) : 0.f;      // a fully masked query: every e is 0, and 0 * rcp(0) would be NaN
         if constexpr (DROP) {
             if (drop.thresh) {
                 const int query = 16 * u + r16;
