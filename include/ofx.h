@@ -84,6 +84,10 @@ enum { OFX_W2_PATCH = 1, OFX_W2_QKV = 2, OFX_W2_OUT = 4, OFX_W2_FC1 = 8, OFX_W2_
 /* Fills *d with the configuration of the reference's type='clip' model. */
 void ofx_default_desc(ofx_model_desc* d);
 
+/* The outfit transformer is scored with heads of 64 columns at d_model in {512, 768, 1024} and with heads of 96 at d_model 1536 (16 x 96,
+ * the reference's default SigLIP model); any other (d_model, n_head) makes ofx_create return NULL with the rule in ofx_last_error().
+ * The tower rules are unchanged (heads of 64).  Training (every ofx_*_train_fwd / _bwd entry point) exists for heads of 64 and d_model in
+ * {512, 768, 1024}: on another handle those calls return OFX_ESHAPE at entry, before anything is launched. */
 ofx_handle* ofx_create(int device, const ofx_model_desc* desc);
 void ofx_destroy(ofx_handle* h);
 
@@ -238,7 +242,9 @@ int ofx_set_encoder_fwd_indexed(ofx_handle* h, const float* table, int ld, long 
 
 /* ------------------------------------------------------------------ training step ("next" row N1) --- */
 /* CP path on precomputed embeddings with a tape, and its backward: what torch autograd computes for the reference's
- * CP trainer step (compatibility_prediction_trainer.py:57-81) with dropout = 0.  Needs outfit_precision BF16 or F16.
+ * CP trainer step (compatibility_prediction_trainer.py:57-81) with dropout = 0.  Needs outfit_precision BF16 or F16, heads of 64 and
+ * d_model in {512, 768, 1024}: every forward and backward entry point of the step returns OFX_ESHAPE at entry on another handle
+ * (d_model 1536 scores only).
  * grads: one fp32 buffer, layout from ofx_cp_train_grad_floats (offsets per packed tensor, padded shapes:
  * linear1 [ffn_pad, D], linear2 [D, ffn_pad], ffn_pad = d_ffn rounded up to 128). */
 size_t ofx_cp_train_tape_bytes(ofx_handle* h, int B, int L);
@@ -577,8 +583,13 @@ int ofx_attention(const void* qkv, void* out, const int64_t* key_mask, int nseq,
 int ofx_attention_ex(const void* qkv, void* out, const int64_t* key_mask, int nseq, int seq_len, int n_head, int ld, int ldo, int k_off,
                      int v_off, int mask_ld, int causal, int only_row0, int split3_w, float scale, int op_dtype, ofx_stream stream);
 /* fp32 VALU attention over varlen sets (the outfit transformer): qkv fp32 [rows, 3 D] (q | k | v), sequence b = rows cu_seqlens[b] ..
- * cu_seqlens[b + 1] (1 .. max_len <= 64 of them), D = n_head * 64.  out [rows, ldo]: out_kind 0 fp32 | 1 operand type | 2 [hi(D) | lo(D) |
- * hi(D)] (ldo >= 3 D); operand-type rows need ldo % 8 == 0.  only_row0: query row 0 of every set alone is computed and stored. */
+ * cu_seqlens[b + 1] (1 .. max_len <= 64 of them), D = n_head * 64 or n_head * 96 (any other head width: OFX_ESHAPE), head h at columns
+ * D / n_head * h.  out [rows, ldo]: out_kind 0 fp32 | 1 operand type | 2 [hi(D) | lo(D) | hi(D)] (ldo >= 3 D); operand-type rows need
+ * ldo % 8 == 0.  only_row0: query row 0 of every set alone is computed and stored.  scale: the caller's, 1 / sqrt(head width) in the
+ * outfit transformer.  Heads of 96 (d_model 1536 = 16 x 96, the reference's default SigLIP width) run their own instances of the
+ * kernel: one wavefront per (set, head) as at 64, lanes 0 .. 31 owning a second column; every row count of the 64-wide instances is
+ * kept (the 64-row instance declares 68.6 KB of LDS, inside gfx950's 160 KiB per workgroup), so no set is refused at 96 that runs at 64.
+ * The same holds for ofx_set_attention_slabs, ofx_set_attention_op and ofx_attention_f32, which launch this kernel. */
 int ofx_set_attention(const float* qkv, void* out, const int* cu_seqlens, int nseq, int n_head, int D, int ldo,
                       int out_kind, int max_len, int only_row0, float scale, int op_dtype, ofx_stream stream);
 /* ofx_set_attention reading q | k | v from the QKV GEMM's split-K slabs (small-batch scores): slabs fp32 [splits][rows, 3 D], slab s at
@@ -595,7 +606,7 @@ int ofx_set_attention_slabs(const float* slabs, size_t plane_floats, int splits,
  * with two-pass fp32 statistics (agrees with ofx_layernorm to fp32 rounding, not bit for bit: the sums take another order).
  * slab fp32 [splits][rows, D], slab s at slab + s * plane_floats; bias [D] and resid [rows, ldr] optional, resid may alias x; x fp32
  * [rows, ldx]; y [rows, ldy]: out_kind 0 fp32 | 1 operand type | 2 [hi(D) | lo(D) | hi(D)] (ldy >= 3 D).  Columns D .. of x, the columns of y
- * behind its D (3 D) and all rows at or past the live count are not written.  D in {512, 768, 1024}, ldx, ldr, ldy multiples of 4 and >= D,
+ * behind its D (3 D) and all rows at or past the live count are not written.  D in {512, 768, 1024, 1536}, ldx, ldr, ldy multiples of 4 and >= D,
  * rows >= 1, splits >= 1, slabs that do not overlap (OFX_ESHAPE); NULL slab / x / gamma / beta / y, pointers off 16 bytes (y: 8 for the
  * operand-type kinds, m_dev: 4), plane_floats % 4 != 0, a bad op_dtype: OFX_EINVAL.  A refused call launches nothing. */
 int ofx_splitk_reduce_ln(const float* slab, size_t plane_floats, int splits, const float* bias, const float* resid, int ldr, float* x, int ldx,
@@ -603,6 +614,8 @@ int ofx_splitk_reduce_ln(const float* slab, size_t plane_floats, int splits, con
                          int op_dtype, ofx_stream stream);
 /* The attention kernels of the training step, one call each (both settings of knob 7).  q | k | v and dqkv are operand-type rows [rows, 3 D]
  * (the tape's layout), sequence b = rows cu_seqlens[b] .. cu_seqlens[b + 1] (1 .. max_len of them, never none), head h at columns 64 h.
+ * The MFMA kernels and both backward kernels are built for heads of 64 only: ofx_attention_varlen wants k_off = n_head * 64, v_off = 2 k_off
+ * and ld >= 3 k_off, ofx_set_attention_bwd D = n_head * 64 (else OFX_ESHAPE, nothing launched); ofx_set_attention_op also takes heads of 96.
  * Dropout on the attention probabilities is site `site` of (dropout_p, seed): mask element (b * n_head + h, query * 32 + key), the values
  * ofx_dropout_mask returns for the same arguments; dropout_p = 0 is no dropout, dropout needs max_len <= 32 (OFX_ESHAPE).  NULL pointers,
  * nseq <= 0 and dropout_p outside [0, 1) are OFX_EINVAL; a refused call launches nothing.

@@ -435,6 +435,14 @@ static int build_set(const ofx_handle* h, const SetInput& in, const float* prefi
 }
 static int set_encoder_core(ofx_handle* h, const SetInput& in, const float* prefix, int prefix_stride, int B, int L, float* out_row0, void* ws,
                             size_t ws_bytes, hipStream_t s);
+// softmax scale of the outfit transformer, 1 / sqrt(head_dim): 0.125f exactly at heads of 64
+static float set_attn_scale(const ofx_model_desc& d) { return 1.0f / sqrtf((float)(d.d_model / d.n_head)); }
+// The training step (MFMA attention forward and backward, ofx_layernorm_bwd) exists for heads of 64 and the widths layernorm_bwd takes;
+// every training entry point asks before it launches anything.
+static bool ln_bwd_d_ok(int D);
+static bool train_shape_ok(const ofx_model_desc& d) { return d.d_model == d.n_head * 64 && ln_bwd_d_ok(d.d_model); }
+#define OFX_REQUIRE_TRAIN_SHAPE(h, who) \
+    OFX_REQUIRE(!(h) || train_shape_ok((h)->d), OFX_ESHAPE, who ": training needs heads of 64 and d_model in {512, 768, 1024} (d_model=%d, n_head=%d scores only)", (h)->d.d_model, (h)->d.n_head)
 
 extern "C" int ofx_set_encoder_fwd(ofx_handle* h, const float* x, const uint8_t* pad_mask, const float* prefix,
                                    int prefix_stride, int B, int L, float* out_row0, void* ws, size_t ws_bytes,
@@ -461,6 +469,7 @@ static int set_encoder_core(ofx_handle* h, const SetInput& in, const float* pref
     OFX_REQUIRE(bump.ok, OFX_EWORKSPACE, "set_encoder_fwd: workspace %zu < %zu bytes", ws_bytes, bump.off);
     const int D = d.d_model, km = a_kmul(h->ot_form), Fp = h->ot_ffn_pad, dt = h->ot_dtype, M = B * (L + 1);
     const int okind = km == 3 ? OFX_OUT_SPLIT3 : OFX_OUT_OP;
+    const float scale = set_attn_scale(d);
     auto slab_gemm = [&](const PackedGemm& c, int K) { GemmArgs g{}; use_gemm(g, c, K); g.slab = w.slab; g.slab_bytes = w.slab_bytes; return g; };
     if (!prefix) { prefix = h->outfit_token; prefix_stride = 0; }
     TRY(build_set(h, in, prefix, prefix_stride, w.cu, w.X, B, L, s));
@@ -481,17 +490,18 @@ static int set_encoder_core(ofx_handle* h, const SetInput& in, const float* pref
         g1.A = w.H; g1.C = w.QKV; g1.m_dev = m_dev; g1.M = M; g1.N = 3 * D; g1.ldc = 3 * D;
         // single-product precisions: q|k|v stay in the operand type and the varlen MFMA attention runs (as in the training forward);
         // bf16x3 keeps fp32 q|k|v and the fp32 set attention (1e-5 parity)
-        const bool mfma_attn = h->ot_form == W_PLAIN && g_train_mfma_attn;       // f16w2 keeps fp32 q | k | v and the fp32 set attention, as bf16x3 does
+        // (heads of 96 have no MFMA attention: their single-product precisions take the fp32 set attention too)
+        const bool mfma_attn = h->ot_form == W_PLAIN && g_train_mfma_attn && D == d.n_head * 64;       // f16w2 keeps fp32 q | k | v and the fp32 set attention, as bf16x3 does
         g1.out_kind = mfma_attn ? OFX_OUT_OP : OFX_OUT_F32;
         int qkv_splits = 1;
         if (fuse_att && !mfma_attn) g1.defer_splits = &qkv_splits;
         TRY(ofx_launch_gemm(g1, dt, s));
         if (mfma_attn) {
-            AttnArgs at{w.QKV, w.H, nullptr, B, L + 1, d.n_head, 3 * D, D, D, 2 * D, 0, 0, 0.125f};
+            AttnArgs at{w.QKV, w.H, nullptr, B, L + 1, d.n_head, 3 * D, D, D, 2 * D, 0, 0, scale};
             at.cu_seqlens = w.cu; at.only_row0 = last ? 1 : 0;
             TRY(ofx_launch_attention_mfma(at, dt, s));
         } else {
-            SetAttnArgs sa{w.QKV, w.H, w.cu, B, d.n_head, D, km * D, okind, L + 1, last ? 1 : 0, 0.125f};
+            SetAttnArgs sa{w.QKV, w.H, w.cu, B, d.n_head, D, km * D, okind, L + 1, last ? 1 : 0, scale};
             if (qkv_splits > 1) { sa.qkv = w.slab; sa.splits = qkv_splits; sa.plane = (size_t)M * 3 * D; sa.bias = g1.bias; }
             TRY(ofx_launch_set_attention(sa, dt, s));
         }
@@ -926,6 +936,7 @@ extern "C" int ofx_cir_train_fwd(ofx_handle* h, const float* x, const uint8_t* p
 static int cp_train_fwd_core(ofx_handle* h, const SetInput& in, int B, int L, float* logits, void* tape_mem, size_t tape_bytes, void* ws,
                              size_t ws_bytes, float dropout_p, unsigned seed, hipStream_t s, int head, const float* target_text) {
     OFX_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, OFX_EINVAL, "cp_train_fwd: dropout_p=%g", dropout_p);
+    OFX_REQUIRE_TRAIN_SHAPE(h, "cp_train_fwd");       // a width that scores only is refused whatever the handle's state
     OFX_REQUIRE(h && h->out_ready, OFX_ESTATE, "cp_train_fwd: outfit weights not packed");
     OFX_REQUIRE(h->ot_form == W_PLAIN, OFX_ESTATE, "cp_train_fwd: training uses a single-product precision (bf16 / f16), not bf16x3 / f16w2");
     const ofx_model_desc& d = h->d;
@@ -938,6 +949,7 @@ static int cp_train_fwd_core(ofx_handle* h, const SetInput& in, int B, int L, fl
     carve_set(h, wb, B, L, &w);
     OFX_REQUIRE(wb.ok, OFX_EWORKSPACE, "cp_train_fwd: workspace too small");
     const int D = d.d_model, Fp = h->ot_ffn_pad, dt = h->ot_dtype, M = B * (L + 1);
+    const float scale = set_attn_scale(d);
     auto slab_gemm = [&](const PackedGemm& c, int K) { GemmArgs g{}; use_gemm(g, c, K); g.slab = w.slab; g.slab_bytes = w.slab_bytes; return g; };
     if (head == 1) {
         TRY(ofx_launch_cir_prefix(h->tgt_img_emb, target_text, T.prefix, B, D, s));
@@ -956,11 +968,11 @@ static int cp_train_fwd_core(ofx_handle* h, const SetInput& in, int B, int L, fl
         g1.A = t.H1; g1.C = t.QKV; g1.m_dev = m_dev; g1.M = M; g1.N = 3 * D; g1.ldc = 3 * D; g1.out_kind = OFX_OUT_OP;      // q|k|v kept in the operand type
         TRY(ofx_launch_gemm(g1, dt, s));
         if (g_train_mfma_attn) {           // varlen MFMA attention on the operand-type q|k|v (probabilities rounded to the operand type, as autocast SDPA does)
-            AttnArgs at{t.QKV, t.O, nullptr, B, L + 1, d.n_head, 3 * D, D, D, 2 * D, 0, 0, 0.125f};
+            AttnArgs at{t.QKV, t.O, nullptr, B, L + 1, d.n_head, 3 * D, D, D, 2 * D, 0, 0, scale};
             at.cu_seqlens = T.cu; at.only_row0 = last ? 1 : 0; at.drop = make_drop(dropout_p, seed, 4 * l + 0);
             TRY(ofx_launch_attention_mfma(at, dt, s));
         } else {
-            SetAttnArgs sa{t.QKV, t.O, T.cu, B, d.n_head, D, D, OFX_OUT_OP, L + 1, last ? 1 : 0, 0.125f};
+            SetAttnArgs sa{t.QKV, t.O, T.cu, B, d.n_head, D, D, OFX_OUT_OP, L + 1, last ? 1 : 0, scale};
             sa.drop = make_drop(dropout_p, seed, 4 * l + 0); sa.qkv_op = 1;
             TRY(ofx_launch_set_attention(sa, dt, s));
         }
@@ -1034,6 +1046,7 @@ static int set_train_bwd_core(ofx_handle* h, void* tape_mem, size_t tape_bytes, 
     // per-layer completion events (data-parallel overlap): consumed by this call whatever its outcome
     std::vector<hipEvent_t> layer_ev;
     if (h) layer_ev.swap(h->bwd_events);
+    OFX_REQUIRE_TRAIN_SHAPE(h, "cp_train_bwd");
     OFX_REQUIRE(h && h->out_ready && h->ot_form == W_PLAIN, OFX_ESTATE, "cp_train_bwd: needs packed single-product weights");
     OFX_REQUIRE(tape_mem && dlogits && (grads || grad_ptrs) && ws && B > 0, OFX_EINVAL, "cp_train_bwd: bad argument");
     OFX_REQUIRE(h->d.outfit_act == OFX_ACT_MISH, OFX_ESTATE, "cp_train_bwd: only the Mish activation has a backward epilogue");
@@ -1110,7 +1123,7 @@ static int set_train_bwd_core(ofx_handle* h, void* tape_mem, size_t tape_bytes, 
         // ---- attention branch: Xmid = Xin + O Wo^T + bo
         TRY(wgrad(rows, md, w.gXb, D, O, D, G(g0 + 2)));                                                                               // dWo [D, D]
         TRY(dgrad(rows, md, w.gXb, Ly.out, w.dO, D, D));                                                                           // dO
-        TRY(attention_bwd(t.QKV, w.dO, w.gQb, T.cu, B, d.n_head, D, L + 1, 0.125f, dt, site(l, 0), last ? 1 : 0, s));                  // (last layer: only row 0 has a dO, all rows get dK, dV)
+        TRY(attention_bwd(t.QKV, w.dO, w.gQb, T.cu, B, d.n_head, D, L + 1, set_attn_scale(d), dt, site(l, 0), last ? 1 : 0, s));                  // (last layer: only row 0 has a dO, all rows get dK, dV)
         TRY(ofx_launch_colsum(w.gQb, 1, 3 * D, nullptr, nullptr, G(g0 + 1), nullptr, nullptr, 3 * D, w.part, 3 * D, m_dev, M, dt, s, 0, acc));   // dbin
         TRY(wgrad(M, m_dev, w.gQb, 3 * D, t.H1, D, G(g0 + 0)));                                                                        // dWin [3D, D]
         TRY(dgrad(M, m_dev, w.gQb, Ly.in, w.dH, D, 3 * D));                                                                        // dH1
@@ -1493,6 +1506,9 @@ static bool train_attn_args_ok(const void* a, const void* b, const void* c, int 
 extern "C" int ofx_attention_varlen(const void* qkv, void* out, const int* cu_seqlens, int nseq, int max_len, int n_head, int ld, int ldo, int k_off,
                                     int v_off, int only_row0, float scale, float dropout_p, unsigned seed, int site, int op_dtype, ofx_stream stream) {
     OFX_REQUIRE(train_attn_args_ok(qkv, out, cu_seqlens, nseq, dropout_p), OFX_EINVAL, "attention_varlen: bad argument");
+    // q | k | v rows as the training step lays them out; the MFMA attention reads heads of 64 columns and nothing else
+    OFX_REQUIRE(n_head > 0 && k_off == n_head * 64 && v_off == 2 * k_off && ld >= 3 * k_off, OFX_ESHAPE,
+                "attention_varlen: q | k | v rows of D = n_head * 64 columns (k_off=%d v_off=%d ld=%d n_head=%d); heads of 96 take ofx_set_attention", k_off, v_off, ld, n_head);
     AttnArgs a{qkv, out, nullptr, nseq, max_len, n_head, ld, ldo, k_off, v_off, 0, 0, scale};
     a.cu_seqlens = cu_seqlens; a.only_row0 = only_row0 ? 1 : 0; a.drop = make_drop(dropout_p, seed, (unsigned)site);
     return ofx_launch_attention_mfma(a, op_dtype, (hipStream_t)stream);

@@ -1,4 +1,4 @@
-// Attention kernels of the scoring path (head_dim 64 everywhere).
+// Attention kernels of the scoring path (head_dim 64; the fp32 set attention also takes heads of 96).
 //
 // (1) attention_mfma: one wavefront per (sequence, head), whole sequence (S <= 64) in one tile —
 //     CLIP ViT-B/32 (S = 50, 12 heads) and CLIP text (S <= 64, causal ∧ key-padding, 8 heads);
@@ -7,7 +7,7 @@
 // (2) set_attention: fp32 VALU attention over an outfit's 1 + n items (S <= 32, 16 heads);
 //     replaces nn.MultiheadAttention's SDPA inside nn.TransformerEncoderLayer
 //     (src/models/outfit_x.py:137-140,165-168) with -inf on padded keys realised by pad-free
-//     compaction.  < 0.3 % of the path's FLOPs, kept exact.
+//     compaction.  < 0.3 % of the path's FLOPs, kept exact.  Heads of 64 or 96 columns (the reference's default model: 16 x 96).
 #include "attn_wave.h"
 
 namespace {
@@ -113,9 +113,17 @@ struct SetK {
     int splits; size_t plane; const float* bias;
 };
 
-template <typename T, int SMAX, typename TI = float>      // TI: element type of qkv (float: scoring path; T: training tape)
+// HD = columns per head, 64 or 96.  Lane = column throughout; at 96 lanes 0..31 own a second column (64 + lane) in the v registers, the
+// P.V sums and the stores.  Staged rows are STR floats apart: 68 (64 columns) and 100 (96 columns) are both = 4 mod 32 dwords, so the 16-byte
+// slots of consecutive rows start in different banks.  At 96 a row slice is 24 float4 chunks and an output row 12 chunks of 8: both are walked
+// as one flat (row, chunk) index over the 64 lanes, every lane busy, every access 16 bytes.  The 64-column instances keep their maps, their
+// arithmetic and their summation order as they were.
+template <typename T, int SMAX, typename TI = float, int HD = 64>      // TI: element type of qkv (float: scoring path; T: training tape)
 __global__ __launch_bounds__(64) void set_attention_kernel(SetK a) {
-    constexpr int STR = 68;                         // floats per staged row: 16-B slots of consecutive rows differ
+    static_assert(HD == 64 || HD == 96, "set_attention: heads of 64 or 96 columns");
+    constexpr int STR = HD == 64 ? 68 : 100;        // floats per staged row: 16-B slots of consecutive rows differ
+    constexpr int C4 = HD / 4, C8 = HD / 8;         // float4 chunks per row slice, 8-column chunks per output row
+    constexpr bool WIDE = HD > 64;
     __shared__ __attribute__((aligned(16))) float qs[SMAX * STR];
     __shared__ __attribute__((aligned(16))) float ks[SMAX * STR];
     __shared__ __attribute__((aligned(16))) float sc[SMAX * (SMAX + 4)];
@@ -126,58 +134,88 @@ __global__ __launch_bounds__(64) void set_attention_kernel(SetK a) {
     S = S < SMAX ? S : SMAX;
     const int nq = a.only_row0 ? 1 : S;
     const int D = a.D;
+    const bool two = WIDE && lane < HD - 64;        // this lane owns column 64 + lane as well
     float vreg[SMAX];
+    float vreg2[WIDE ? SMAX : 1];
     if (a.splits > 1) {
         // q | k | v still in the QKV GEMM's split-K slabs: sum them here in the reduce kernel's order (slab 0 + 1 + ... + bias), 16 lanes x
-        // float4 per 64-column row slice, four rows per pass; v goes through LDS to reach its lane = column layout
+        // float4 per 64-column row slice, four rows per pass (96 columns: the flat chunk walk); v goes through LDS to reach its lane =
+        // column layout
         constexpr int VS = SMAX <= 32 ? SMAX : 1;        // the launcher keeps the slab path to sets of <= 32 rows
         __shared__ __attribute__((aligned(16))) float vs[VS * STR];
-        const int c4 = (lane & 15) * 4, rsub = lane >> 4;
-        const float* bp = a.bias + h * 64 + c4;
-        const f32x4 bq = *(const f32x4*)bp, bk = *(const f32x4*)(bp + D), bv = *(const f32x4*)(bp + 2 * D);
-        for (int j0 = 0; j0 < S; j0 += 4) {
-            const int j = j0 + rsub;
-            if (j < S) {
-                const float* rp = (const float*)a.qkv + (size_t)(r0 + j) * 3 * D + h * 64 + c4;
-                f32x4 q = {0.f, 0.f, 0.f, 0.f}, kk = *(const f32x4*)(rp + D), vv = *(const f32x4*)(rp + 2 * D);
-                if (j < nq) q = *(const f32x4*)rp;
-                for (int sl = 1; sl < a.splits; ++sl) {
-                    const float* sp = rp + sl * a.plane;
-                    if (j < nq) q += *(const f32x4*)sp;
-                    kk += *(const f32x4*)(sp + D); vv += *(const f32x4*)(sp + 2 * D);
-                }
-                if (j < nq) *(f32x4*)(qs + j * STR + c4) = q + bq;
-                *(f32x4*)(ks + j * STR + c4) = kk + bk;
-                *(f32x4*)(vs + (j % VS) * STR + c4) = vv + bv;
+        auto slab_row = [&](int j, int c4) {
+            const float* bp = a.bias + h * HD + c4;
+            const f32x4 bq = *(const f32x4*)bp, bk = *(const f32x4*)(bp + D), bv = *(const f32x4*)(bp + 2 * D);
+            const float* rp = (const float*)a.qkv + (size_t)(r0 + j) * 3 * D + h * HD + c4;
+            f32x4 q = {0.f, 0.f, 0.f, 0.f}, kk = *(const f32x4*)(rp + D), vv = *(const f32x4*)(rp + 2 * D);
+            if (j < nq) q = *(const f32x4*)rp;
+            for (int sl = 1; sl < a.splits; ++sl) {
+                const float* sp = rp + sl * a.plane;
+                if (j < nq) q += *(const f32x4*)sp;
+                kk += *(const f32x4*)(sp + D); vv += *(const f32x4*)(sp + 2 * D);
             }
+            if (j < nq) *(f32x4*)(qs + j * STR + c4) = q + bq;
+            *(f32x4*)(ks + j * STR + c4) = kk + bk;
+            *(f32x4*)(vs + (j % VS) * STR + c4) = vv + bv;
+        };
+        if constexpr (!WIDE) {
+            const int c4 = (lane & 15) * 4, rsub = lane >> 4;
+            for (int j0 = 0; j0 < S; j0 += 4) {
+                const int j = j0 + rsub;
+                if (j < S) slab_row(j, c4);
+            }
+        } else {
+            for (int f = lane; f < S * C4; f += 64) slab_row(f / C4, (f % C4) * 4);
         }
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < SMAX; ++j) vreg[j] = j < S ? vs[(j % VS) * STR + lane] : 0.f;
+        if constexpr (WIDE) {
+#pragma unroll
+            for (int j = 0; j < SMAX; ++j) vreg2[j] = (j < S && two) ? vs[(j % VS) * STR + 64 + lane] : 0.f;
+        }
     } else if (sizeof(TI) == 4) {
-        // fp32 q | k | v: q and k rows as 16-byte loads (16 lanes per 64-column slice, four rows per instruction) straight into their LDS
-        // rows; v stays one dword per lane and row (its lane = column layout is what the P.V loop wants).  The kernel is bound by its
-        // vector-memory instruction count, not by bytes (S = 8: 12 loads + 3 stores per wave instead of 24 + 24)
-        const int c4 = (lane & 15) * 4, rsub = lane >> 4;
-        for (int j0 = 0; j0 < S; j0 += 4) {
-            const int j = j0 + rsub;
-            if (j < S) {
-                const float* rp = (const float*)a.qkv + (size_t)(r0 + j) * 3 * D + h * 64 + c4;
-                if (j < nq) *(f32x4*)(qs + j * STR + c4) = *(const f32x4*)rp;
-                *(f32x4*)(ks + j * STR + c4) = *(const f32x4*)(rp + D);
+        // fp32 q | k | v: q and k rows as 16-byte loads (16 lanes per 64-column slice, four rows per instruction; 96 columns: the flat
+        // chunk walk) straight into their LDS rows; v stays one dword per lane and row (its lane = column layout is what the P.V loop
+        // wants).  The kernel is bound by its vector-memory instruction count, not by bytes (S = 8: 12 loads + 3 stores per wave instead
+        // of 24 + 24)
+        auto f32_row = [&](int j, int c4) {
+            const float* rp = (const float*)a.qkv + (size_t)(r0 + j) * 3 * D + h * HD + c4;
+            if (j < nq) *(f32x4*)(qs + j * STR + c4) = *(const f32x4*)rp;
+            *(f32x4*)(ks + j * STR + c4) = *(const f32x4*)(rp + D);
+        };
+        if constexpr (!WIDE) {
+            const int c4 = (lane & 15) * 4, rsub = lane >> 4;
+            for (int j0 = 0; j0 < S; j0 += 4) {
+                const int j = j0 + rsub;
+                if (j < S) f32_row(j, c4);
             }
+        } else {
+            for (int f = lane; f < S * C4; f += 64) f32_row(f / C4, (f % C4) * 4);
         }
 #pragma unroll
-        for (int j = 0; j < SMAX; ++j) vreg[j] = j < S ? ((const float*)a.qkv)[(size_t)(r0 + j) * 3 * D + 2 * D + h * 64 + lane] : 0.f;
+        for (int j = 0; j < SMAX; ++j) vreg[j] = j < S ? ((const float*)a.qkv)[(size_t)(r0 + j) * 3 * D + 2 * D + h * HD + lane] : 0.f;
+        if constexpr (WIDE) {
+#pragma unroll
+            for (int j = 0; j < SMAX; ++j) vreg2[j] = (j < S && two) ? ((const float*)a.qkv)[(size_t)(r0 + j) * 3 * D + 2 * D + h * HD + 64 + lane] : 0.f;
+        }
     } else {
 #pragma unroll
         for (int j = 0; j < SMAX; ++j) {
             vreg[j] = 0.f;
+            if constexpr (WIDE) vreg2[j] = 0.f;
             if (j < S) {
-                const TI* rp = (const TI*)a.qkv + (size_t)(r0 + j) * 3 * D + h * 64 + lane;
+                const TI* rp = (const TI*)a.qkv + (size_t)(r0 + j) * 3 * D + h * HD + lane;
                 if (j < nq) qs[j * STR + lane] = (float)rp[0];
                 ks[j * STR + lane] = (float)rp[D];
                 vreg[j] = (float)rp[2 * D];
+                if constexpr (WIDE) {
+                    if (two) {
+                        if (j < nq) qs[j * STR + 64 + lane] = (float)rp[64];
+                        ks[j * STR + 64 + lane] = (float)rp[D + 64];
+                        vreg2[j] = (float)rp[2 * D + 64];
+                    }
+                }
             }
         }
     }
@@ -188,7 +226,7 @@ __global__ __launch_bounds__(64) void set_attention_kernel(SetK a) {
         const f32x4* kp = (const f32x4*)(ks + j * STR);
         float d = 0.f;
 #pragma unroll
-        for (int c = 0; c < 16; ++c) {
+        for (int c = 0; c < C4; ++c) {
             const f32x4 x = qp[c], y = kp[c];
             d += x[0] * y[0] + x[1] * y[1] + x[2] * y[2] + x[3] * y[3];
         }
@@ -215,27 +253,45 @@ __global__ __launch_bounds__(64) void set_attention_kernel(SetK a) {
             float acc = 0.f;
 #pragma unroll
             for (int j = 0; j < SMAX; ++j) acc += (j < S ? row[j] : 0.f) * vreg[j];
-            ((float*)a.out)[(size_t)(r0 + i) * a.ldo + h * 64 + lane] = acc;
+            ((float*)a.out)[(size_t)(r0 + i) * a.ldo + h * HD + lane] = acc;
+            if constexpr (WIDE) {
+                float acc2 = 0.f;
+#pragma unroll
+                for (int j = 0; j < SMAX; ++j) acc2 += (j < S ? row[j] : 0.f) * vreg2[j];
+                if (two) ((float*)a.out)[(size_t)(r0 + i) * a.ldo + h * HD + 64 + lane] = acc2;
+            }
         }
         return;
     }
     // operand-type outputs: the fp32 rows go through the (now free) q staging rows and leave as 16-byte stores - 8 lanes per 64-column
     // slice, 8 rows per instruction, one instruction per copy (hi | lo | hi) instead of one 2-byte store per lane, row and copy
+    // (96 columns: 12 chunks of 8 per row, walked flat)
     for (int i = 0; i < nq; ++i) {
         const float* row = sc + i * (SMAX + 4);
         float acc = 0.f;
 #pragma unroll
         for (int j = 0; j < SMAX; ++j) acc += (j < S ? row[j] : 0.f) * vreg[j];
         qs[i * STR + lane] = acc;
+        if constexpr (WIDE) {
+            float acc2 = 0.f;
+#pragma unroll
+            for (int j = 0; j < SMAX; ++j) acc2 += (j < S ? row[j] : 0.f) * vreg2[j];
+            if (two) qs[i * STR + 64 + lane] = acc2;
+        }
     }
     __syncthreads();
-    const int c8 = (lane & 7) * 8, r8 = lane >> 3;
-    for (int i0 = 0; i0 < nq; i0 += 8) {
-        const int i = i0 + r8;
-        if (i < nq) {
-            const f32x4 x0 = *(const f32x4*)(qs + i * STR + c8), x1 = *(const f32x4*)(qs + i * STR + c8 + 4);
-            store8<T>(a.out, (size_t)(r0 + i) * a.ldo + h * 64 + c8, x0, x1, a.out_kind, D);
+    auto store_row = [&](int i, int c8) {
+        const f32x4 x0 = *(const f32x4*)(qs + i * STR + c8), x1 = *(const f32x4*)(qs + i * STR + c8 + 4);
+        store8<T>(a.out, (size_t)(r0 + i) * a.ldo + h * HD + c8, x0, x1, a.out_kind, D);
+    };
+    if constexpr (!WIDE) {
+        const int c8 = (lane & 7) * 8, r8 = lane >> 3;
+        for (int i0 = 0; i0 < nq; i0 += 8) {
+            const int i = i0 + r8;
+            if (i < nq) store_row(i, c8);
         }
+    } else {
+        for (int f = lane; f < nq * C8; f += 64) store_row(f / C8, (f % C8) * 8);
     }
 }
 
@@ -487,9 +543,8 @@ int ofx_launch_attention_mfma(const AttnArgs& g, int op_dtype, hipStream_t s) {
 }
 
 int ofx_launch_set_attention(const SetAttnArgs& g, int op_dtype, hipStream_t s) {
-    OFX_REQUIRE(g.D == g.n_head * 64, OFX_ESHAPE, "set_attention: head_dim must be 64 (D=%d heads=%d)", g.D, g.n_head);
-    // 64 rows per sequence in both modes; the training features of varlen sets (hashed dropout keyed query * 32 + key, the split-K slab
-    // input, the backward kernel) stay at 32
+    OFX_REQUIRE(g.n_head > 0 && (g.D == g.n_head * 64 || g.D == g.n_head * 96), OFX_ESHAPE, "set_attention: head_dim must be 64 or 96 (D=%d heads=%d)", g.D, g.n_head);
+    const bool wide = g.D == g.n_head * 96;
     OFX_REQUIRE(g.max_len >= 1 && g.max_len <= 64, OFX_ESHAPE, "set_attention: %d rows per sequence exceed 64", g.max_len);
     OFX_REQUIRE(g.max_len <= 32 || !g.drop.thresh, OFX_ESHAPE, "set_attention: dropout columns are keyed query * 32 + key");
     OFX_REQUIRE(g.ldo >= (g.out_kind == 2 ? 3 * g.D : g.D) && (g.out_kind == 0 || g.ldo % 8 == 0), OFX_ESHAPE, "set_attention: bad ldo=%d (operand-type rows leave as 16-byte stores)", g.ldo);
@@ -502,7 +557,9 @@ int ofx_launch_set_attention(const SetAttnArgs& g, int op_dtype, hipStream_t s) 
     k.splits = g.splits > 1 ? g.splits : 1; k.plane = g.plane; k.bias = g.bias;
     const int grid = g.nseq * g.n_head;
     ProfScope prof(PROF_ATTN, s);
-#define SA(T, N) do { if (g.qkv_op) hipLaunchKernelGGL((set_attention_kernel<T, N, T>), dim3(grid), dim3(64), 0, s, k); \
+#define SA(T, N) do { if (wide) { if (g.qkv_op) hipLaunchKernelGGL((set_attention_kernel<T, N, T, 96>), dim3(grid), dim3(64), 0, s, k); \
+                                      else hipLaunchKernelGGL((set_attention_kernel<T, N, float, 96>), dim3(grid), dim3(64), 0, s, k); } \
+                      else if (g.qkv_op) hipLaunchKernelGGL((set_attention_kernel<T, N, T>), dim3(grid), dim3(64), 0, s, k); \
                       else hipLaunchKernelGGL((set_attention_kernel<T, N, float>), dim3(grid), dim3(64), 0, s, k); } while (0)
     // (8 rows: category-name texts computed to their EOS - a third of the 20-row variant's LDS, so 32 instead of 12 one-wave blocks per CU
     // hide each other's load latency)

@@ -287,7 +287,7 @@ int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
         // second pass of a split-K plan: left to the consumer (defer_splits), fused with the following LayerNorm (ln_gamma), or the plain reduce
         auto second_pass = [&]() -> int {
             if (g.defer_splits) { *g.defer_splits = splits; return OFX_OK; }
-            if (g.ln_gamma && g.out_kind == 0 && g.act == OFX_ACT_NONE && !g.aux_out && !g.drop.thresh && (g.N == 512 || g.N == 768 || g.N == 1024)) {
+            if (g.ln_gamma && g.out_kind == 0 && g.act == OFX_ACT_NONE && !g.aux_out && !g.drop.thresh && (g.N == 512 || g.N == 768 || g.N == 1024 || g.N == 1536)) {
                 SplitKLnArgs a{(const float*)g.slab, (size_t)g.M * g.N, splits, g.bias, g.resid, g.ldr, (float*)g.C, g.ldc,
                                g.ln_gamma, g.ln_beta, g.ln_out, g.ln_ld, g.ln_kind, g.ln_eps, g.M, g.N, g.m_dev};
                 TRY(ofx_launch_splitk_reduce_ln(a, op_dtype, s, true));

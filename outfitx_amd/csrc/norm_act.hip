@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnArgs a, const int* row
 }  // namespace
 
 int ofx_launch_layernorm_dev(const LnArgs& a, const int* rows_dev, int op_dtype, hipStream_t s) {
-    OFX_REQUIRE(a.D == 512 || a.D == 768 || a.D == 1024, OFX_ESHAPE, "layernorm: D=%d not in {512,768,1024}", a.D);
+    OFX_REQUIRE(a.D == 512 || a.D == 768 || a.D == 1024 || a.D == 1536, OFX_ESHAPE, "layernorm: D=%d not in {512,768,1024,1536}", a.D);
     OFX_REQUIRE(a.rows > 0, OFX_ESHAPE, "layernorm: rows=%d", a.rows);
     OFX_REQUIRE(a.ldy % 4 == 0 && a.ldy >= (a.out_kind == 2 ? 3 * a.D : a.D), OFX_ESHAPE, "layernorm: bad ldy=%d", a.ldy);
     int grid = (a.rows + 3) / 4;
@@ -52,9 +52,9 @@ int ofx_launch_layernorm_dev(const LnArgs& a, const int* rows_dev, int op_dtype,
     ProfScope prof(PROF_NORM, s);
 #define LN_CASE(T, N) hipLaunchKernelGGL((layernorm_kernel<T, N>), dim3(grid), dim3(256), 0, s, a, rows_dev)
     if (op_dtype == OFX_F16) {
-        if (a.D == 512) LN_CASE(f16_t, 2); else if (a.D == 768) LN_CASE(f16_t, 3); else LN_CASE(f16_t, 4);
+        if (a.D == 512) LN_CASE(f16_t, 2); else if (a.D == 768) LN_CASE(f16_t, 3); else if (a.D == 1024) LN_CASE(f16_t, 4); else LN_CASE(f16_t, 6);
     } else {
-        if (a.D == 512) LN_CASE(bf16_t, 2); else if (a.D == 768) LN_CASE(bf16_t, 3); else LN_CASE(bf16_t, 4);
+        if (a.D == 512) LN_CASE(bf16_t, 2); else if (a.D == 768) LN_CASE(bf16_t, 3); else if (a.D == 1024) LN_CASE(bf16_t, 4); else LN_CASE(bf16_t, 6);
     }
 #undef LN_CASE
     OFX_LAUNCH_CHECK();
@@ -70,9 +70,10 @@ namespace {
 // One block per row, one float4 per thread (D = 4 * blockDim.x): the slab loads of a row are spread over D / 4 lanes, so even
 // 16 slabs are one short load burst; the two LayerNorm reductions go wave_sum -> LDS -> every thread re-adds the per-wave partials
 // in the same order (any wave count gives every thread the same value).
-template <typename T>
-__global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(SplitKLnArgs a) {
-    __shared__ float part[2][4];
+// NW = the most waves a block has: 4 (D <= 1024) or 6 (D = 1536); the narrower instance is the kernel as it always was.
+template <typename T, int NW = 4>
+__global__ __launch_bounds__(64 * NW) void splitk_reduce_ln_kernel(SplitKLnArgs a) {
+    __shared__ float part[2][NW];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const int rows = a.m_dev ? min(*a.m_dev, a.rows) : a.rows;
     const int D = a.D, col = threadIdx.x * 4;
@@ -104,12 +105,15 @@ __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(SplitKLnArgs a) {
 }  // namespace
 
 int ofx_launch_splitk_reduce_ln(const SplitKLnArgs& a, int op_dtype, hipStream_t s, bool in_gemm_scope) {
-    OFX_REQUIRE(a.D == 512 || a.D == 768 || a.D == 1024, OFX_ESHAPE, "splitk_reduce_ln: D=%d not in {512,768,1024}", a.D);
+    OFX_REQUIRE(a.D == 512 || a.D == 768 || a.D == 1024 || a.D == 1536, OFX_ESHAPE, "splitk_reduce_ln: D=%d not in {512,768,1024,1536}", a.D);
     OFX_REQUIRE(a.rows > 0 && a.splits >= 1 && a.ldx % 4 == 0 && a.ldx >= a.D && (!a.resid || (a.ldr % 4 == 0 && a.ldr >= a.D)), OFX_ESHAPE, "splitk_reduce_ln: bad shape");
     OFX_REQUIRE(a.ldy % 4 == 0 && a.ldy >= (a.out_kind == 2 ? 3 * a.D : a.D), OFX_ESHAPE, "splitk_reduce_ln: bad ldy=%d", a.ldy);
     const int grid = a.rows > 8192 ? 8192 : a.rows;
     ProfScope prof(PROF_NORM, s, 0.0, false, !in_gemm_scope);
-    if (op_dtype == OFX_F16) OFX_PLAUNCH(in_gemm_scope, splitk_reduce_ln_kernel<f16_t>, dim3(grid), dim3(a.D / 4), 0, s, a);
+    if (a.D > 1024) {
+        if (op_dtype == OFX_F16) OFX_PLAUNCH(in_gemm_scope, (splitk_reduce_ln_kernel<f16_t, 6>), dim3(grid), dim3(a.D / 4), 0, s, a);
+        else OFX_PLAUNCH(in_gemm_scope, (splitk_reduce_ln_kernel<bf16_t, 6>), dim3(grid), dim3(a.D / 4), 0, s, a);
+    } else if (op_dtype == OFX_F16) OFX_PLAUNCH(in_gemm_scope, splitk_reduce_ln_kernel<f16_t>, dim3(grid), dim3(a.D / 4), 0, s, a);
     else OFX_PLAUNCH(in_gemm_scope, splitk_reduce_ln_kernel<bf16_t>, dim3(grid), dim3(a.D / 4), 0, s, a);
     OFX_LAUNCH_CHECK();
     return OFX_OK;

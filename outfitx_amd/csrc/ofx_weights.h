@@ -84,7 +84,11 @@ inline void use_cir_head(GemmArgs& g, const ofx_handle& h) {
 
 // Descriptor -> the handle's configuration (operand types, forms, masks, padded FFN width).  Returns why the descriptor is refused, or null.
 inline const char* ofx_configure(ofx_handle& h, const ofx_model_desc& d) {
-    if (d.d_model != d.n_head * 64 || (d.d_model != 512 && d.d_model != 768 && d.d_model != 1024)) return "d_model must be n_head*64 and one of 512/768/1024";
+    // heads of 64 at the widths the project has always scored, heads of 96 at 1536 = 16 x 96, the reference's default (SigLIP) model.
+    // (1536 as 24 heads of 64 is no model of the reference, and its single-product path - the MFMA attention at that width - is untested: refused.)
+    const bool head64 = d.n_head >= 1 && d.d_model == d.n_head * 64 && (d.d_model == 512 || d.d_model == 768 || d.d_model == 1024);
+    const bool head96 = d.n_head >= 1 && d.d_model == d.n_head * 96 && d.d_model == 1536;
+    if (!head64 && !head96) return "d_model must be n_head*64 with d_model in 512/768/1024, or n_head*96 with d_model 1536";
     if (d.vit_width != d.vit_heads * 64 || d.txt_width != d.txt_heads * 64) return "tower head_dim must be 64";
     if (d.vit_width % 256 || d.txt_width % 256 || d.proj_dim % 128 || d.vit_mlp % 128 || d.txt_mlp % 128) return "tower dims must be multiples of 128/256";
     if (d.vit_image % d.vit_patch || (d.vit_image / d.vit_patch) * (d.vit_image / d.vit_patch) + 1 > 64) return "ViT sequence (patches+1) must be <= 64";

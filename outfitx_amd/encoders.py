@@ -527,7 +527,7 @@ class ItemEncoder(nn.Module):
         if cfg.type != "clip":
             raise NotImplementedError(
                 f"ItemEncoderConfig(type='{cfg.type}') is outside the MI355X scoring path; build the model with "
-                "OutfitXConfig(item_encoder=ItemEncoderConfig(type='clip'))")
+                "OutfitXConfig(item_encoder=ItemEncoderConfig(type='clip')), or - for precomputed embeddings only - OutfitX(cfg, item_towers=False)")
         self.image_enc = CLIPImageEncoder(model_name_or_path=cfg.clip_model_name)
         self.text_enc = CLIPTextEncoder(model_name_or_path=cfg.clip_model_name)
         # side-stream text tower: its small kernels fill the tile-quantisation tails of the big ViT GEMMs.  Neutral with round 1's
@@ -606,3 +606,41 @@ class ItemEncoder(nn.Module):
         return aggregate_embeddings(image_embeddings=img, text_embeddings=txt, aggregation_method=self.cfg.aggregation_method)
 
     encode_items = forward   # north-star alias (the reference has no encode_items)
+
+
+# What ofx_create accepts for the outfit transformer: head width -> the d_model values scored with it
+SCORED_WIDTHS = {64: (512, 768, 1024), 96: (1536,)}
+
+
+class PrecomputedItemEncoder(nn.Module):
+    """Stand-in for the item encoder of a model that is fed precomputed embeddings only (`OutfitX(cfg, item_towers=False)`): no towers,
+    no parameters, no buffers.  It keeps what the host code reads of the reference's ItemEncoder (item_encoder.py:8-61) - `cfg` and
+    `d_embed`, derived the same way - for any `ItemEncoderConfig.type`, the reference's default 'slip' (2 x 768) among them, and raises
+    from everything that would need a tower."""
+
+    def __init__(self, cfg: ItemEncoderConfig):
+        super().__init__()
+        self.cfg = cfg
+        self.image_enc = None
+        self.text_enc = None
+
+    @property
+    def d_embed(self) -> int:
+        return self.cfg.dim_per_modality * 2 if self.cfg.aggregation_method == "concat" else self.cfg.dim_per_modality
+
+    @property
+    def image_size(self):
+        raise NotImplementedError(self._why("image_size"))
+
+    def _why(self, what: str) -> str:
+        return (f"{what}: this model was built with item_towers=False (ItemEncoderConfig(type='{self.cfg.type}')): it scores precomputed "
+                "item embeddings only; pass outfit_embedding= or the index form")
+
+    def set_precision(self, tower_precision: str) -> None:      # no towers to configure
+        pass
+
+    def forward(self, *args, **kwargs) -> torch.Tensor:
+        raise NotImplementedError(self._why("item_encoder.forward"))
+
+    encode_items = forward
+

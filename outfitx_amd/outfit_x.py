@@ -24,7 +24,7 @@ from . import _lib as L
 from .configs import OutfitXConfig
 from .datatypes import (OutfitCompatibilityPredictionTask, OutfitComplementaryItemRetrievalTask,
                         OutfitFillInTheBlankTask, OutfitPrecomputeEmbeddingTask)
-from .encoders import ItemEncoder
+from .encoders import SCORED_WIDTHS, ItemEncoder, PrecomputedItemEncoder
 from .engine import Engine
 
 _ACT_NAMES = {"mish": "mish", "gelu": "gelu", "relu": None}
@@ -133,11 +133,23 @@ class OutfitX(nn.Module):
                     OutfitFillInTheBlankTask, OutfitPrecomputeEmbeddingTask)
 
     def __init__(self, cfg: Optional[OutfitXConfig] = None, precision: str = "bf16x3", tower_precision: str = L.DEFAULT_TOWER_PRECISION,
-                 train_precision: str = "bf16"):
+                 train_precision: str = "bf16", item_towers: bool = True):
+        """item_towers=False: a model for precomputed embeddings only (what the reference's trainers and demo feed), for any
+        `ItemEncoderConfig.type` whose width the kernels score - 'clip' (1024 = 16 x 64) and the reference's default 'slip'
+        (1536 = 16 x 96).  `item_encoder` is then a parameter-less stand-in and `state_dict()` holds the outfit transformer only."""
         super().__init__()
         self.cfg = cfg if cfg is not None else OutfitXConfig()
         t = self.cfg.transformer
-        self.item_encoder = ItemEncoder(self.cfg.item_encoder)
+        self.item_towers = bool(item_towers)
+        if self.item_towers:
+            self.item_encoder = ItemEncoder(self.cfg.item_encoder)
+        else:
+            self.item_encoder = PrecomputedItemEncoder(self.cfg.item_encoder)
+            d, nh = self.item_encoder.d_embed, t.n_head
+            if d % nh or d not in SCORED_WIDTHS.get(d // nh, ()):
+                raise NotImplementedError(
+                    f"ItemEncoderConfig(type='{self.cfg.item_encoder.type}') gives d_model {d} with {nh} heads: heads of {d / nh:g} columns; "
+                    f"the set attention is built for heads of 64 (d_model 512 / 768 / 1024) and heads of 96 (d_model 1536)")
         d = self.item_encoder.d_embed
         layer = nn.TransformerEncoderLayer(d_model=d, nhead=t.n_head, dim_feedforward=t.d_ffn, dropout=t.dropout,
                                            batch_first=t.batch_first, norm_first=t.norm_first, activation=t.activation)
@@ -184,6 +196,20 @@ class OutfitX(nn.Module):
         s["_engines"] = {}
         s["_replay"] = None
         return s
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kwargs):
+        """A model without towers drops the keys under `item_encoder.` (a reference checkpoint of the SigLIP model carries the open_clip
+        tower there, and demo/app.py loads strictly) and stays as strict as asked about every other key."""
+        if not getattr(self, "item_towers", True):
+            state_dict = {k: v for k, v in state_dict.items() if not k.startswith("item_encoder.")}
+        return super().load_state_dict(state_dict, strict=strict, **kwargs)
+
+    def _check_trainable_width(self) -> None:
+        """The training step (attention backward, layernorm_bwd) exists for heads of 64 and d_model up to 1024."""
+        d, nh = self.item_encoder.d_embed, self.cfg.transformer.n_head
+        if d // nh != 64 or d > 1024:
+            raise NotImplementedError(f"training at d_model {d} ({nh} heads of {d // nh}) is not built: this width scores only "
+                                      "(model.eval() / torch.no_grad()); the backward kernels take heads of 64 and d_model in (512, 768, 1024)")
 
     def mark_weights_changed(self) -> None:
         """Force a re-pack of the operand copies on the next call.  `_engine` notices parameter updates through the tensors'
@@ -232,6 +258,8 @@ class OutfitX(nn.Module):
 
     def precompute_embeddings(self, images: List[List[Union[np.ndarray, Image.Image]]], texts: List[List[str]]):
         """outfit_x.py:107-118: one item per 'outfit' -> [B, d_embed]."""
+        if not self.item_towers:
+            raise NotImplementedError(self.item_encoder._why("precompute_embeddings"))
         return self.item_encoder(images, texts)[:, 0, :]
 
     def encode_items(self, images, texts):
@@ -280,6 +308,8 @@ class OutfitX(nn.Module):
         """outfit_x.py:120-144 -> raw compatibility logits [B,1].  Beyond the reference's arguments: the indexed form
         (item_index, cu_seqlens[, embedding_table, max_len]) — same result as the padded tensors built from those rows."""
         prec = None
+        if encoder_input_dict is not None and not self.item_towers:
+            raise NotImplementedError(self.item_encoder._why("encoder_input_dict="))
         if item_index is None and encoder_input_dict is not None:
             if outfit_embedding is None and not self.training and getattr(self, "graph_replay", False):
                 from .graphs import ForwardReplay
@@ -320,6 +350,7 @@ class OutfitX(nn.Module):
         """Trainer step of either head (compatibility_prediction_trainer.py:57-81, complementary_item_retrieval_trainer.py:73-92):
         forward with a tape, backward in libofx_hip.so."""
         t = self.cfg.transformer
+        self._check_trainable_width()
         if self.train_precision not in ("bf16", "f16"):
             raise ValueError("train_precision must be 'bf16' or 'f16'")
         x = setin[0] if len(setin) == 2 else None          # the indexed form's table is data

@@ -40,28 +40,30 @@ def _rng(seed: int, name: str) -> np.random.Generator:
     return np.random.Generator(np.random.PCG64(np.random.SeedSequence([int(seed), zlib.crc32(name.encode())])))
 
 
-def outfit_transformer_shapes() -> Dict[str, Tuple[int, ...]]:
-    """Key → shape for the 51,155,313 trainable parameters (no item encoder)."""
+def outfit_transformer_shapes(d_model: int = D_MODEL, n_layers: int = N_LAYERS) -> Dict[str, Tuple[int, ...]]:
+    """Key → shape for the trainable parameters without the item encoder: 51,155,313 at the defaults; d_model=1536 is the reference's
+    default (SigLIP) width."""
+    d = int(d_model)
     s: Dict[str, Tuple[int, ...]] = {
-        "outfit_token": (D_MODEL,),
-        "target_item_image_emb": (D_HALF,),
-        "cp_ffn.1.weight": (1, D_MODEL),
+        "outfit_token": (d,),
+        "target_item_image_emb": (d // 2,),
+        "cp_ffn.1.weight": (1, d),
         "cp_ffn.1.bias": (1,),
-        "cir_ffn.0.weight": (D_MODEL, D_MODEL),
+        "cir_ffn.0.weight": (d, d),
     }
-    for i in range(N_LAYERS):
+    for i in range(n_layers):
         p = f"transformer_encoder.layers.{i}."
-        s[p + "self_attn.in_proj_weight"] = (3 * D_MODEL, D_MODEL)
-        s[p + "self_attn.in_proj_bias"] = (3 * D_MODEL,)
-        s[p + "self_attn.out_proj.weight"] = (D_MODEL, D_MODEL)
-        s[p + "self_attn.out_proj.bias"] = (D_MODEL,)
-        s[p + "linear1.weight"] = (D_FFN, D_MODEL)
+        s[p + "self_attn.in_proj_weight"] = (3 * d, d)
+        s[p + "self_attn.in_proj_bias"] = (3 * d,)
+        s[p + "self_attn.out_proj.weight"] = (d, d)
+        s[p + "self_attn.out_proj.bias"] = (d,)
+        s[p + "linear1.weight"] = (D_FFN, d)
         s[p + "linear1.bias"] = (D_FFN,)
-        s[p + "linear2.weight"] = (D_MODEL, D_FFN)
-        s[p + "linear2.bias"] = (D_MODEL,)
+        s[p + "linear2.weight"] = (d, D_FFN)
+        s[p + "linear2.bias"] = (d,)
         for n in ("norm1", "norm2"):
-            s[p + n + ".weight"] = (D_MODEL,)
-            s[p + n + ".bias"] = (D_MODEL,)
+            s[p + n + ".weight"] = (d,)
+            s[p + n + ".bias"] = (d,)
     return s
 
 
@@ -145,8 +147,8 @@ def make_weights(seed: int, shapes: Dict[str, Tuple[int, ...]], prefix: str = ""
     return {prefix + k: _draw(seed, k, shp) for k, shp in shapes.items()}
 
 
-def outfit_transformer_weights(seed: int) -> Dict[str, np.ndarray]:
-    return make_weights(seed, outfit_transformer_shapes())
+def outfit_transformer_weights(seed: int, d_model: int = D_MODEL, n_layers: int = N_LAYERS) -> Dict[str, np.ndarray]:
+    return make_weights(seed, outfit_transformer_shapes(d_model, n_layers))
 
 
 def vision_weights(seed: int, prefix: str = "", n_layers: int = VIT_LAYERS) -> Dict[str, np.ndarray]:
@@ -250,13 +252,13 @@ def variant_state_dict(key) -> Dict[str, np.ndarray]:
 
 
 # ---- inputs ---------------------------------------------------------------
-def item_embeddings(seed: int, name: str, *lead: int) -> np.ndarray:
-    """[*lead, 1024] fp32 rows shaped like ItemEncoder output: each 512-half L2-normalised
+def item_embeddings(seed: int, name: str, *lead: int, d_model: int = D_MODEL) -> np.ndarray:
+    """[*lead, d_model] fp32 rows shaped like ItemEncoder output: each half L2-normalised
     (reference: base_image_encoder.py:46-47, base_text_encoder.py:37-38, model_utils.py:40-41)."""
     g = _rng(seed, name)
-    z = g.standard_normal((*lead, 2, D_HALF), dtype=np.float32)
+    z = g.standard_normal((*lead, 2, d_model // 2), dtype=np.float32)
     z /= np.maximum(np.linalg.norm(z, axis=-1, keepdims=True), 1e-12)
-    return z.reshape(*lead, D_MODEL).astype(np.float32)
+    return z.reshape(*lead, d_model).astype(np.float32)
 
 
 def unit_rows(seed: int, name: str, *shape: int) -> np.ndarray:
@@ -266,13 +268,13 @@ def unit_rows(seed: int, name: str, *shape: int) -> np.ndarray:
     return z.astype(np.float32)
 
 
-def outfit_batch(seed: int, B: int, L: int = 16, n_items=8, name: str = "outfits"):
-    """(outfit_embedding [B,L,1024] fp32, outfit_mask [B,L] bool) exactly as the reference's
+def outfit_batch(seed: int, B: int, L: int = 16, n_items=8, name: str = "outfits", d_model: int = D_MODEL):
+    """(outfit_embedding [B,L,d_model] fp32, outfit_mask [B,L] bool) exactly as the reference's
     collate emits them (outfit_x_base_processor.py:20-43): real rows first, zero pad rows after,
     mask True on the pad rows. `n_items` is an int or a length-B sequence."""
     n = np.full(B, n_items, dtype=np.int64) if np.isscalar(n_items) else np.asarray(n_items, dtype=np.int64)
     assert n.shape == (B,) and n.min() >= 0 and n.max() <= L
-    emb = item_embeddings(seed, name, B, L)
+    emb = item_embeddings(seed, name, B, L, d_model=d_model)
     mask = np.arange(L)[None, :] >= n[:, None]
     emb[mask] = 0.0
     return emb, mask

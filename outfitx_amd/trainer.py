@@ -195,6 +195,8 @@ class FlatGradTrainer:
     def __init__(self, model: torch.nn.Module, steps_per_epoch: int, cfg, loss_fn: Callable,
                  params: Optional[Iterable[torch.nn.Parameter]] = None, group=None):
         self.model, self.cfg, self.group = model, cfg, group
+        if hasattr(model, "_check_trainable_width"):
+            model._check_trainable_width()          # a width that scores only (d_model 1536): refuse before anything is allocated
         c = self.cfg
         ps = list(params) if params is not None else self._default_params(model)
         self.grads = FlatGrads(ps)

@@ -3,7 +3,9 @@
   cfg1  CP forward, 32 precomputed-embedding outfits (8 of 16 items)       [+ hipGraph replay]
   cfg3  FITB: CIR forward + 4-candidate argmin, 1024 outfits
   cfg4  CIR: 1000 queries vs 100k-item pool, k=50 (unsharded, and one 12.5k shard = 1/8 of the 8-GPU layout)
-Prints one JSON line per config.   python tools/bench_configs.py [cfg1] [cfg1x] [cfg3] [cfg4]   (default: all; cfg1 = 32 outfits only, cfg1x = its 256 / 1024-outfit variants; rocprofv3 passes name one)"""
+  cfgw  the wide model beside the default one, same run, alternating: CP forward at cfg1's 32 and cfg3's 1024 outfits, d_model 1024 (16 x 64) and
+        1536 (16 x 96, the reference's default SigLIP width, built without towers), bf16x3; median of 30 device-event-timed steps each + the ratio
+Prints one JSON line per config.   python tools/bench_configs.py [cfg1] [cfg1x] [cfg3] [cfg4] [cfgw]   (default: all; cfg1 = 32 outfits only, cfg1x = its 256 / 1024-outfit variants; rocprofv3 passes name one)"""
 import json, os, sys, time, warnings
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -32,7 +34,39 @@ def timeit(fn, iters=50, warm=5):
     return (time.perf_counter() - t0) / iters
 
 
+def wide_rows(steps=30, warm=5):
+    """d_model 1024 and 1536 side by side (models without towers, synthetic weights, the reference's 6 layers), steps alternating between the two widths."""
+    models = {}
+    for d, typ in ((1024, "clip"), (1536, "slip")):
+        m = OutfitX(OutfitXConfig(item_encoder=ItemEncoderConfig(type=typ)), item_towers=False)
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in synth.outfit_transformer_weights(7, d_model=d).items()}, strict=True)
+        models[d] = m.to(dev).eval()
+    for name, B in (("cfg1", 32), ("cfg3cp", 1024)):
+        calls = {}
+        for d, m in models.items():
+            emb, mask = synth.outfit_batch(1235, B, 16, 8, d_model=d)
+            e, k = cu(emb), cu(mask)
+            calls[d] = (lambda m=m, e=e, k=k: m(task=CP, outfit_embedding=e, outfit_mask=k))
+        for _ in range(warm):
+            for f in calls.values(): f()
+        torch.cuda.synchronize()
+        ev = {d: [] for d in calls}
+        for _ in range(steps):
+            for d, f in calls.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(); f(); b.record()
+                ev[d].append((a, b))
+        torch.cuda.synchronize()
+        med = {d: float(np.median([a.elapsed_time(b) for a, b in ev[d]])) for d in ev}
+        print(json.dumps({"config": f"{name}-wide", "what": f"CP forward, {B} precomputed outfits (8 of 16 items), bf16x3, d_model 1024 vs 1536, median of {steps} alternating steps",
+                          "ms_d1024": round(med[1024], 4), "ms_d1536": round(med[1536], 4), "ratio_1536_over_1024": round(med[1536] / med[1024], 3)}), flush=True)
+
+
 only = set(a for a in sys.argv[1:] if a.startswith("cfg"))
+if only == {"cfgw"}:
+    with torch.no_grad():
+        wide_rows()
+    sys.exit(0)
 with torch.no_grad():
     for B in ((32, 256, 1024) if not only else ((32,) if "cfg1" in only else ()) + ((256, 1024) if "cfg1x" in only else ())):
         emb, mask = synth.outfit_batch(1235, B, 16, 8)
@@ -85,3 +119,5 @@ with torch.no_grad():
     print(json.dumps({"config": "cfg4", "what": "CIR: 1000 queries vs 100k pool, top-50, fp32-exact", "query_forward_ms": round(t_fwd * 1e3, 3),
                       "topk_unsharded_ms": round(t_full * 1e3, 3), "topk_one_of_8_shards_ms": round(t_shard * 1e3, 3),
                       "distance_gemm_tflops_fp32": round(2 * nq * npool * 1024 / t_full / 1e12, 1)}), flush=True)
+    if not only or "cfgw" in only:
+        wide_rows()
