@@ -49,10 +49,6 @@ int device_cu_count() {
     if (c == 0) { int v = 0; c = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256; }
     return c;
 }
-int ofx_persistent_grid(int nwg, int persist, bool has_m_dev) {
-    if (persist < 0) persist = device_cu_count();
-    return (persist && !has_m_dev && nwg > persist) ? persist : nwg;
-}
 
 // ------------------------------------------------------------------------------- profiling
 bool g_ofx_prof_on = false;
@@ -1235,18 +1231,13 @@ extern "C" int ofx_adamw_step(const ofx_opt_segment* segments, int n_segments, f
 extern "C" int ofx_tune(int knob, int value) {
     ++g_config_generation;
     switch (knob) {
-        case 2: g_gemm_kernel = value; return OFX_OK;
-        case 5: g_gemm_splitk = value; return OFX_OK;
+        case 2: case 5: case 11: case 15: case 16: case 18: return ofx_gemm_tune(knob, value);      // the GEMM launch knobs (GemmKnobs, gemm_plan.h)
         case 6: if (value != 2) { ofx_set_error("ofx_tune(6): %d is not 2 (the towers' LayerNorms are always folded)", value); return OFX_EINVAL; } return OFX_OK;
         case 7: g_train_mfma_attn = value; return OFX_OK;
         case 8: g_prune_q = value; return OFX_OK;
         case 9: g_fuse_qkv = value; return OFX_OK;
         case 10: g_set_fuse = value; return OFX_OK;
-        case 11: g_w2_persist = value; return OFX_OK;
-        case 15: g_x3_kernel = value; return OFX_OK;
-        case 16: g_x3_persist = value != 0; return OFX_OK;
         case 17: g_topk_filter = value != 0; return OFX_OK;
-        case 18: if (value != 0 && value != 1) { ofx_set_error("ofx_tune(18): %d is not 0 or 1", value); return OFX_EINVAL; } g_epi_direct = value; return OFX_OK;
         case 20: g_x3_vit_f32_attn = value != 0; return OFX_OK;
         default: ofx_set_error("ofx_tune: unknown knob %d", knob); return OFX_EINVAL;
     }

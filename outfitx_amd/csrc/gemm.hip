@@ -17,8 +17,6 @@
 //    one XCD so the panel is fetched into that XCD's L2 once.
 #include "gemm_common.h"
 
-int g_gemm_splitk = 1;     // 0 disables split-K
-
 namespace {
 // MT = MFMA row tiles per wave: 4 -> the 128x128 block tile, 2 -> 64x128 (twice the blocks for grids that leave CUs idle: the
 // training step's M ~ 2k-row GEMMs with N = 1024; 48 KiB of LDS, three blocks per CU)
@@ -96,7 +94,6 @@ __global__ __launch_bounds__(256, 2) void gemm_128x128_kernel(KArgs p) {
         __builtin_amdgcn_s_barrier();
         OFX_LDS char* base = lds + cur * STAGE_T;
         // all 16 fragment reads of the k-tile go out first; the MFMAs then wait on counted lgkmcnt
-        static_assert(true, "");
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             const int chk = ((ks * 4 + fq) ^ fsw) * 16;
@@ -143,54 +140,22 @@ __global__ __launch_bounds__(256, 2) void gemm_128x128_kernel(KArgs p) {
 
 }  // namespace
 
-// Plan for problems the big-tile kernels cannot fill (small M): tile height (128 rows, 2 blocks per CU = 512 slots; or 64 rows, 3 per
-// CU = 768 slots) x deterministic split-K over blockIdx.y.  Cost model (us), measured on these kernels: ~1.06 / ~0.65 us per k-tile
-// and round of co-resident 128- / 64-row blocks; a split adds the fp32 slab written once and read once (~5 TB/s) and the reduce
-// launch.  M = 2304 x N = 1024 (144 blocks) is faster UNSPLIT (17 vs 26 us); M = 288 (K = 3072) wants the split.
-// g_gemm_splitk: 0 = never split, 1 = plan, >= 2 = forced (experiments: low byte = splits, bit 8 = 64-row tiles).
-struct SmallPlan { int tile64, splits; double cost; };
-static SmallPlan plan_small(int M, int N, int K, bool allow_split, bool allow64) {
-    const int nk = K / BK;
-    SmallPlan best{0, 1, 1e30};
-    if (g_gemm_splitk >= 2) {
-        SmallPlan f{(g_gemm_splitk >> 8) & 1, (g_gemm_splitk & 0xff) > 16 ? 16 : (g_gemm_splitk & 0xff), 0.0};      // forced plans: at most 16 slices, as the planner's own
-        if (f.tile64 && !allow64) f.tile64 = 0;
-        if (!allow_split || f.splits > nk) f.splits = 1;
-        const int kps = (nk + f.splits - 1) / f.splits;
-        f.splits = (nk + kps - 1) / kps;                       // every split owns at least one k-tile
-        return f;
+// The launch knobs: ofx_tune(2 | 5 | 11 | 15 | 16 | 18, v) (GemmKnobs, gemm_plan.h).  No other file reads them: the plan carries what they decide.
+static GemmKnobs g_knobs;
+int ofx_gemm_tune(int knob, int value) {
+    switch (knob) {
+        case 2: g_knobs.kernel = value; return OFX_OK;
+        case 5: g_knobs.splitk = value; return OFX_OK;
+        case 11: g_knobs.w2_persist = value; return OFX_OK;
+        case 15: g_knobs.x3_kernel = value; return OFX_OK;
+        case 16: g_knobs.x3_persist = value != 0; return OFX_OK;
+        case 18: if (value != 0 && value != 1) { ofx_set_error("ofx_tune(18): %d is not 0 or 1", value); return OFX_EINVAL; } g_knobs.epi_direct = value; return OFX_OK;
+        default: ofx_set_error("ofx_tune: unknown knob %d", knob); return OFX_EINVAL;
     }
-    for (int t64 = 0; t64 <= (allow64 ? 1 : 0); ++t64) {
-        const long blocks = (long)((M + (t64 ? 63 : 127)) / (t64 ? 64 : 128)) * (N / 128);
-        const long slots = t64 ? 768 : 512;
-        const double per = t64 ? 0.65 : 1.06;
-        for (int sp = 1; sp <= 16; ++sp) {
-            if (sp > 1 && !(allow_split && g_gemm_splitk != 0 && blocks < 256 && nk >= 16 && sp <= nk / 4)) break;
-            const int kps = (nk + sp - 1) / sp;
-            if ((nk + kps - 1) / kps != sp) continue;
-            double t = (double)((blocks * sp + slots - 1) / slots) * kps * per + (t64 ? 1.0 : 0.0);
-            if (sp > 1) t += 2.0 * sp * M * N * 4.0 / 5.0e6 + 3.0;
-            if (t < best.cost) best = SmallPlan{t64, sp, t};
-        }
-    }
-    return best;
 }
-// Slab size for ANY plan the launcher may pick for this shape: it plans with or without 64-row tiles depending on the kernel knobs
-// and the grid (can64 in ofx_launch_gemm), so the slab covers the larger slice count of the two tile heights (forced plans: <= 16).
-size_t ofx_gemm_splitk_bytes(int M, int N, int K) {
-    const int a = plan_small(M, N, K, true, true).splits, b = plan_small(M, N, K, true, false).splits;
-    const int sp = a > b ? a : b;
-    return sp > 1 ? (size_t)sp * M * N * 4 : 0;
-}
+size_t ofx_gemm_splitk_bytes(int M, int N, int K) { return gemm_splitk_slab_bytes(M, N, K, g_knobs); }
 
-
-int g_epi_direct = 1;     // ofx_tune(18, v): 1 (default) gemm_w2f8_kernel's operand-type outputs leave straight from the accumulator layout (epilogue_direct), 0 = through LDS
-int g_x3_persist = 1;     // ofx_tune(16, v): 1 (default) gemm_x3_kernel launches one block per CU walking its tiles (when it has more tiles than CUs), 0 = one block per tile
-int g_x3_kernel = 1;      // three-product GEMMs (k_mult == 3: A rows [hi | lo | hi], W rows [hi | hi | lo]): 1 = the operand-tiles-loaded-once 256x128 kernel
-                          // (gemm_x3.hip) from 192 tiles on, 2 = always, 0 = the K-concatenated single-product kernels; ofx_tune(15, v)
-int g_w2_persist = -1;    // dual-weight kernel: persistent grid size (blocks walk tiles b, b + grid, ...): -1 = one block per CU of the device, 0 = one block per tile, ofx_tune(11, v)
-int g_gemm_kernel = GEMM_AUTO;    // ofx_tune(2, v): a GemmKind (gemm_common.h) forces that kernel
-
+// Four steps: validate, describe the problem (GemmShape), plan (gemm_plan: every decision), carry the plan out.
 int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
     OFX_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, OFX_ESHAPE, "gemm: empty problem M=%d N=%d K=%d", g.M, g.N, g.K);
     OFX_REQUIRE(g.N % BN == 0, OFX_ESHAPE, "gemm: N=%d must be a multiple of %d (pad the weight at pack time)", g.N, BN);
@@ -205,11 +170,6 @@ int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
     OFX_REQUIRE(op_dtype == OFX_BF16 || op_dtype == OFX_F16, OFX_EINVAL, "gemm: operand dtype must be bf16 or f16");
     if (g.defer_splits) *g.defer_splits = 1;
     if (g.ln_done) *g.ln_done = false;
-    KArgs k;
-    k.A = (const char*)g.A; k.W = (const char*)g.W; k.C = (char*)g.C; k.bias = g.bias; k.resid = g.resid; k.aux_out = g.aux_out; k.m_dev = g.m_dev; k.splits = 1; k.slab = nullptr; k.m_slab = g.M; k.kt_per_split = 0;
-    k.ka_tiles = ka / BK;
-    k.M = g.M; k.N = g.N; k.K = g.K; k.lda = g.lda; k.ldc = g.ldc; k.ldr = g.ldr; k.act = g.act; k.out_kind = g.out_kind; k.drop = g.drop; k.n_valid = g.N;
-    k.xb_out = (char*)g.xb_out; k.stat_part = g.stat_part; k.row_stat = g.row_stat; k.col_sum = g.col_sum; k.stat_ld = g.stat_ld > 0 ? g.stat_ld : 1; k.xlo = (char*)g.xlo;
     const bool producer = g.xb_out || g.stat_part || g.xlo;
     OFX_REQUIRE(!producer || (g.xb_out && g.stat_part && g.xlo && g.C == g.xb_out && g.out_kind == 1 && g.ldc == g.N && g.N % 64 == 0), OFX_EINVAL,
                 "gemm: a LayerNorm-fold producer takes xb_out, stat_part and xlo together, with C == xb_out in the operand type");
@@ -218,6 +178,36 @@ int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
                 "gemm: LayerNorm folding does not combine with the training epilogue features");
     OFX_REQUIRE(!(g.row_stat || producer) || !g.resid, OFX_EINVAL, "gemm: LayerNorm folding takes no residual (a producer's stream is (xb_out, xlo))");
     OFX_REQUIRE(!producer || g.act == OFX_ACT_NONE, OFX_EINVAL, "gemm: a LayerNorm-fold producer has no activation");
+
+    GemmShape sh;
+    sh.M = g.M; sh.N = g.N; sh.K = g.K; sh.lda = g.lda; sh.a_wrap = g.a_wrap; sh.k_mult = g.k_mult;
+    sh.f16 = op_dtype == OFX_F16; sh.has_w8 = g.W8 && g.w8_scale; sh.has_m_dev = g.m_dev != nullptr;
+    sh.can_split = g.slab && !producer && !g.row_stat; sh.defer = g.defer_splits != nullptr;
+    sh.ln_fusable = g.ln_gamma && g.out_kind == 0 && g.act == OFX_ACT_NONE && !g.aux_out && !g.drop.thresh;
+    sh.out_kind = g.out_kind; sh.resid = g.resid != nullptr; sh.aux = g.aux_out != nullptr; sh.xlo = g.xlo != nullptr;
+    const GemmPlan pl = gemm_plan(sh, g_knobs, device_cu_count());
+    if (pl.splits > 1) OFX_REQUIRE(g.slab_bytes >= (size_t)pl.splits * g.M * g.N * 4, OFX_EWORKSPACE, "gemm: split-K slab too small");
+
+    // record label: logical shape (K without the split-weight / three-product concatenation), the K multiplier and the GemmKind
+    if (g_ofx_prof_on) ofx_prof_set_tag(g.M, g.N, pl.k_logical, pl.kind, pl.kmul, pl.bytes);
+    ProfScope prof(PROF_GEMM, s, pl.flops, true);      // events ride on the launches (OFX_PLAUNCH)
+    KArgs k;
+    k.A = (const char*)g.A; k.W = (const char*)g.W; k.C = (char*)g.C; k.bias = g.bias; k.resid = g.resid; k.aux_out = g.aux_out; k.m_dev = g.m_dev;
+    k.M = g.M; k.N = g.N; k.K = g.K; k.lda = g.lda; k.ldc = g.ldc; k.ldr = g.ldr; k.act = g.act; k.out_kind = g.out_kind; k.drop = g.drop; k.n_valid = g.N;
+    k.ka_tiles = ka / BK;
+    k.xb_out = (char*)g.xb_out; k.stat_part = g.stat_part; k.row_stat = g.row_stat; k.col_sum = g.col_sum; k.stat_ld = g.stat_ld > 0 ? g.stat_ld : 1; k.xlo = (char*)g.xlo;
+    k.tiles_m = pl.tiles_m; k.tiles_n = pl.tiles_n; k.nwg = pl.nwg; k.group_m = pl.group_m; k.epi_direct = pl.epi_direct;
+    k.splits = pl.splits; k.kt_per_split = pl.kt_per_split; k.slab = (float*)g.slab; k.m_slab = g.M;
+    if (gemm_kind_big_tile(pl.kind)) {
+        if (pl.kind == GEMM_W2F8) { k.W8 = (const char*)g.W8; k.w8_scale = (const char*)g.w8_scale; TRY(ofx_gemm_launch_w2f8(&k, pl, s)); }
+        else if (pl.kind == GEMM_X3) TRY(ofx_gemm_launch_x3(&k, pl, op_dtype, s));
+        else if (pl.kind == GEMM_W2) TRY(ofx_gemm_launch_w2(&k, pl, op_dtype, s));
+        else if (pl.kind == GEMM_PP) TRY(ofx_gemm_launch_pp(&k, pl, op_dtype, s));
+        else TRY(ofx_gemm_launch_big(&k, pl, op_dtype, s));
+        OFX_LAUNCH_CHECK();
+        return OFX_OK;
+    }
+    // the 128x128 / 64x128 kernel (64-row tiles, three blocks per CU: grids that would leave CUs idle with 128-row tiles), with or without split-K
     static DeviceOnce attr_set;
     TRY(attr_set.run([]() -> int {
         OFX_HIP(hipFuncSetAttribute((const void*)gemm_128x128_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES));
@@ -226,95 +216,23 @@ int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
         OFX_HIP(hipFuncSetAttribute((const void*)gemm_128x128_kernel<f16_t, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM64_LDS_BYTES));
         return OFX_OK;
     }));
-    // big tiles when they still fill the chip, else the 128^2 kernel
-    int kind = g_gemm_kernel == GEMM_W2 ? GEMM_AUTO : g_gemm_kernel;      // GEMM_W2 only forces the kernel of split-weight GEMMs; every other GEMM keeps the automatic choice
-    if (g.a_wrap) {        // split weights: the dual-weight 256x256 kernel when its grid fills the chip, else the 128x128 kernel with a wrapping A index
-        const long t2 = (long)((g.M + 255) / 256) * (g.N / 256);
-        kind = (g.K == 2 * g.a_wrap && g.a_wrap % 32 == 0 && g.a_wrap >= 64 && g.N % 256 == 0 && (t2 >= 256 || g_gemm_kernel == GEMM_W2) && g_gemm_kernel != GEMM_128) ? GEMM_W2 : GEMM_128;
-        // the correction product on the fp8 matrix instruction
-        if (kind == GEMM_W2 && g.W8 && g.w8_scale && op_dtype == OFX_F16 && g.a_wrap % 128 == 0) kind = GEMM_W2F8;
-    } else if (kind == GEMM_AUTO) {   // measured crossover points (tools/gemm_bench.py, profiles/r01_gemm_variants.txt)
-        const long t2 = (long)((g.M + 255) / 256) * (g.N / 256), t3 = (long)((g.M + 255) / 256) * (g.N / 128);
-        if (g.N % 256 == 0 && t2 >= 1024) kind = g.K <= 1024 ? GEMM_PP : GEMM_256;   // 256x256, one block per CU (short K: the ping-pong kernel)
-        else if (g.N % 128 == 0 && t3 >= 512) kind = GEMM_256x128;                  // short K / mid-size M: 256x128, two blocks per CU
-        else kind = GEMM_128;
-    }
-    if (g.k_mult == 3 && !g.a_wrap && g_x3_kernel && (g_gemm_kernel == GEMM_AUTO || g_gemm_kernel == GEMM_W2) && g.K % 96 == 0 && g.N % 128 == 0 && g.lda >= g.K &&
-        (g_x3_kernel >= 2 || (long)((g.M + 255) / 256) * (g.N / 128) >= 192))
-        kind = GEMM_X3;            // the three products from ONE copy of each operand tile
-    if ((kind == GEMM_256 || kind == GEMM_PP) && g.N % 256) kind = GEMM_128;
-    if (kind == GEMM_64 && g.N % 128) kind = GEMM_128;
-    // record label: logical shape (K without the split-weight / three-product concatenation), the K multiplier and the GemmKind
-    if (g_ofx_prof_on) {
-        const int km = g.a_wrap ? g.K / g.a_wrap : (g.k_mult > 0 ? g.k_mult : 1);
-        // algorithmic HBM bytes of this launch: A once (its k index wraps over a_wrap columns for split weights), the weight rows as
-        // stored, and per output element what the configured epilogue moves: fp32 4 (+4 residual read), operand type 2 (in-place
-        // (hi, lo) stream: 4 read + 4 written), [hi | lo | hi] 6, +4 pre-activation tape copy
-        const double ab = kind == GEMM_X3 ? 2.0 * g.M * (g.K / 3) * 2 : 2.0 * g.M * (g.a_wrap ? g.a_wrap : g.K), wb = kind == GEMM_W2F8 ? 3.0 * g.N * g.a_wrap : (kind == GEMM_X3 ? 2.0 * g.N * (g.K / 3) * 2 : 2.0 * g.N * g.K);      // GEMM_W2F8 reads the hi rows (2 B) + the fp8 lo rows (1 B)
-        double ob = g.out_kind == 0 ? 4.0 : (g.out_kind == 2 ? 6.0 : 2.0);
-        if (g.xlo) ob = 8.0;
-        else if (g.resid) ob += 4.0;
-        if (g.aux_out) ob += 4.0;
-        ofx_prof_set_tag(g.M, g.N, g.K / km, kind, km, ab + wb + ob * g.M * g.N);
-    }
-    // executed FLOPs in f16-rate equivalents: the fp8 correction product of GEMM_W2F8 runs at twice the f16 rate (1.5 products, not 2)
-    ProfScope prof(PROF_GEMM, s, 2.0 * g.M * g.N * g.K * (kind == GEMM_W2F8 ? 0.75 : 1.0), true);      // events ride on the launches (OFX_PLAUNCH)
-    if (gemm_kind_big_tile(kind)) {
-        k.group_m = kind == GEMM_256x128 ? 4 : 8;
-        int rc;
-        if (kind == GEMM_W2F8) {
-            k.W8 = (const char*)g.W8; k.w8_scale = (const char*)g.w8_scale; rc = ofx_gemm_launch_w2f8(&k, g.M, g.N, s);
-        }
-        else if (kind == GEMM_X3) rc = ofx_gemm_launch_x3(&k, op_dtype, g.M, g.N, s);
-        else if (kind == GEMM_W2) rc = ofx_gemm_launch_w2(&k, op_dtype, g.M, g.N, s);
-        else if (kind == GEMM_PP) rc = ofx_gemm_launch_pp(&k, op_dtype, g.M, g.N, s);
-        else rc = ofx_gemm_launch_big(&k, kind, op_dtype, g.M, g.N, s);
-        if (rc != OFX_OK) return rc;
-    } else {
-        k.tiles_n = g.N / BN; k.tiles_m = (g.M + BM - 1) / BM; k.nwg = k.tiles_m * k.tiles_n;
-        // row panels per L2 group: (group_m + 64/group_m) panels of 128 x K operands should fit ~3 MiB of the XCD's L2
-        int gm = (int)((3u << 20) / ((size_t)BM * g.K * 2) / 2);
-        gm = gm < 1 ? 1 : (gm > 8 ? 8 : gm);
-        k.group_m = gm;
-        const bool can_split = g.slab && !producer && !g.row_stat;
-        const bool can64 = (kind == GEMM_64) || (kind == GEMM_128 && g_gemm_kernel == GEMM_AUTO && g.M > 64 && (long)k.tiles_m * k.tiles_n <= 384);
-        SmallPlan pl = plan_small(g.M, g.N, g.K, can_split, can64);
-        if (kind == GEMM_64) pl.tile64 = 1;
-        const int splits = pl.splits;
-        k.splits = splits; k.slab = (float*)g.slab; k.m_slab = g.M;
-        k.kt_per_split = splits > 1 ? (g.K / BK + splits - 1) / splits : 0;
-        if (splits > 1) OFX_REQUIRE(g.slab_bytes >= (size_t)splits * g.M * g.N * 4, OFX_EWORKSPACE, "gemm: split-K slab too small");
-        // second pass of a split-K plan: left to the consumer (defer_splits), fused with the following LayerNorm (ln_gamma), or the plain reduce
-        auto second_pass = [&]() -> int {
-            if (g.defer_splits) { *g.defer_splits = splits; return OFX_OK; }
-            if (g.ln_gamma && g.out_kind == 0 && g.act == OFX_ACT_NONE && !g.aux_out && !g.drop.thresh && (g.N == 512 || g.N == 768 || g.N == 1024 || g.N == 1536)) {
-                SplitKLnArgs a{(const float*)g.slab, (size_t)g.M * g.N, splits, g.bias, g.resid, g.ldr, (float*)g.C, g.ldc,
-                               g.ln_gamma, g.ln_beta, g.ln_out, g.ln_ld, g.ln_kind, g.ln_eps, g.M, g.N, g.m_dev};
-                TRY(ofx_launch_splitk_reduce_ln(a, op_dtype, s, true));
-                if (g.ln_done) *g.ln_done = true;
-                return OFX_OK;
-            }
-            size_t tot = (size_t)g.M * (g.N / 4);
-            int rg = (int)((tot + 255) / 256); if (rg > 2048) rg = 2048;
-            if (op_dtype == OFX_F16) OFX_PLAUNCH(true, splitk_reduce_kernel<f16_t>, dim3(rg), dim3(256), 0, s, k);
-            else OFX_PLAUNCH(true, splitk_reduce_kernel<bf16_t>, dim3(rg), dim3(256), 0, s, k);
-            return OFX_OK;
-        };
-        if (pl.tile64) {        // 64-row tiles, three blocks per CU: grids that would leave CUs idle with 128-row tiles (with or without split-K)
-            k.tiles_m = (g.M + 63) / 64; k.nwg = k.tiles_m * k.tiles_n; k.group_m = 2 * gm;
-            const dim3 grid64(k.nwg, splits);
-            const bool one64 = splits <= 1 || g.defer_splits;      // the launch that carries the profile record's stop event
-            if (op_dtype == OFX_F16) OFX_PLAUNCH(one64, (gemm_128x128_kernel<f16_t, 2>), grid64, dim3(256), GEMM64_LDS_BYTES, s, k);
-            else OFX_PLAUNCH(one64, (gemm_128x128_kernel<bf16_t, 2>), grid64, dim3(256), GEMM64_LDS_BYTES, s, k);
-            if (splits > 1) TRY(second_pass());
-            OFX_LAUNCH_CHECK();
-            return OFX_OK;
-        }
-        const dim3 grid(k.nwg, splits > 1 ? splits : 1);
-        const bool one = splits <= 1 || g.defer_splits;
-        if (op_dtype == OFX_F16) OFX_PLAUNCH(one, gemm_128x128_kernel<f16_t>, grid, dim3(256), GEMM_LDS_BYTES, s, k);
-        else OFX_PLAUNCH(one, gemm_128x128_kernel<bf16_t>, grid, dim3(256), GEMM_LDS_BYTES, s, k);
-        if (splits > 1) TRY(second_pass());
+    const dim3 grid(pl.grid_x, pl.grid_y);
+    const bool one = pl.second_pass == GEMM_PASS_NONE || pl.second_pass == GEMM_PASS_DEFERRED;      // the launch that carries the profile record's stop event
+    if (pl.tile_m == 64) {
+        if (op_dtype == OFX_F16) OFX_PLAUNCH(one, (gemm_128x128_kernel<f16_t, 2>), grid, dim3(256), GEMM64_LDS_BYTES, s, k);
+        else OFX_PLAUNCH(one, (gemm_128x128_kernel<bf16_t, 2>), grid, dim3(256), GEMM64_LDS_BYTES, s, k);
+    } else if (op_dtype == OFX_F16) OFX_PLAUNCH(one, gemm_128x128_kernel<f16_t>, grid, dim3(256), GEMM_LDS_BYTES, s, k);
+    else OFX_PLAUNCH(one, gemm_128x128_kernel<bf16_t>, grid, dim3(256), GEMM_LDS_BYTES, s, k);
+    // second pass of a split-K plan: left to the consumer (defer_splits), fused with the following LayerNorm (ln_gamma), or the plain reduce
+    if (pl.second_pass == GEMM_PASS_DEFERRED) *g.defer_splits = pl.splits;
+    else if (pl.second_pass == GEMM_PASS_REDUCE_LN) {
+        SplitKLnArgs a{(const float*)g.slab, (size_t)g.M * g.N, pl.splits, g.bias, g.resid, g.ldr, (float*)g.C, g.ldc,
+                       g.ln_gamma, g.ln_beta, g.ln_out, g.ln_ld, g.ln_kind, g.ln_eps, g.M, g.N, g.m_dev};
+        TRY(ofx_launch_splitk_reduce_ln(a, op_dtype, s, true));
+        if (g.ln_done) *g.ln_done = true;
+    } else if (pl.second_pass == GEMM_PASS_REDUCE) {
+        if (op_dtype == OFX_F16) OFX_PLAUNCH(true, splitk_reduce_kernel<f16_t>, dim3(pl.reduce_grid), dim3(256), 0, s, k);
+        else OFX_PLAUNCH(true, splitk_reduce_kernel<bf16_t>, dim3(pl.reduce_grid), dim3(256), 0, s, k);
     }
     OFX_LAUNCH_CHECK();
     return OFX_OK;

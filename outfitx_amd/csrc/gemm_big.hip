@@ -117,20 +117,19 @@ __global__ __launch_bounds__(64 * WR * WC, 2) void gemm_big_kernel(KArgs p) {
 }
 
 template <typename T, int WR, int WC, int NST>
-static int launch_big(KArgs& k, int M, int N, hipStream_t s) {
+static int launch_big(const KArgs& k, const GemmPlan& plan, hipStream_t s) {
     constexpr int TM = WR * 128, TN = WC * 64, NW = WR * WC;
     constexpr int LDSB = NST * (TM + TN) * BK * 2 + NW * EPI2_BYTES_PER_WAVE;
     static DeviceOnce attr;
     TRY(set_max_dynamic_lds(attr, gemm_big_kernel<T, WR, WC, NST>, LDSB));
-    k.tiles_n = N / TN; k.tiles_m = (M + TM - 1) / TM; k.nwg = k.tiles_m * k.tiles_n;
-    OFX_PLAUNCH(true, (gemm_big_kernel<T, WR, WC, NST>), dim3(k.nwg), dim3(64 * NW), LDSB, s, k);
+    OFX_PLAUNCH(true, (gemm_big_kernel<T, WR, WC, NST>), dim3(plan.grid_x), dim3(64 * NW), LDSB, s, k);
     return OFX_OK;
 }
 
 }  // namespace
 
-int ofx_gemm_launch_big(void* kargs, int kind, int op_dtype, int M, int N, hipStream_t s) {
-    KArgs& k = *(KArgs*)kargs;
-    if (kind == GEMM_256) return op_dtype == OFX_F16 ? launch_big<f16_t, 2, 4, 2>(k, M, N, s) : launch_big<bf16_t, 2, 4, 2>(k, M, N, s);
-    return op_dtype == OFX_F16 ? launch_big<f16_t, 2, 2, 1>(k, M, N, s) : launch_big<bf16_t, 2, 2, 1>(k, M, N, s);
+int ofx_gemm_launch_big(void* kargs, const GemmPlan& plan, int op_dtype, hipStream_t s) {
+    const KArgs& k = *(const KArgs*)kargs;
+    if (plan.kind == GEMM_256) return op_dtype == OFX_F16 ? launch_big<f16_t, 2, 4, 2>(k, plan, s) : launch_big<bf16_t, 2, 4, 2>(k, plan, s);
+    return op_dtype == OFX_F16 ? launch_big<f16_t, 2, 2, 1>(k, plan, s) : launch_big<bf16_t, 2, 2, 1>(k, plan, s);
 }

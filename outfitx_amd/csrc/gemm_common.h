@@ -1,38 +1,22 @@
 // Shared pieces of the GEMM translation units (gemm.hip: 128x128 kernel + dispatcher; gemm_big.hip: 256x256 / 256x128 tiles;
 // gemm_pp.hip: ping-pong 256x256; gemm_w2.hip: dual-weight 256x256; gemm_w2f8.hip: the same with the fp8 correction product;
 // gemm_x3.hip: three-product 256x128; gemm_tn.hip: weight-gradient TN kernel) and of fused_qkv_attn.hip, which borrows the tile
-// constants and the block remap: the kernel kinds, kernel arguments, the tile walk (gemm_walk.h), the two-wave-group main loop
-// (gemm_pingpong.h: slot protocol, BK = 32 lane constants, persistent walk, dual-weight step), the live-row clamp, the LDS-DMA
-// helpers and the fused epilogue.  There is ONE epilogue value chain (epi_value, epi_residual) and one rounding / [hi | lo | hi] store
-// (store4 / store8, ofx_common.h); the kernels reach it by several routes - epilogue2's fp32 and operand-type branches, epilogue_direct
-// (accumulator layout), splitk_reduce_kernel - which differ only in where the values come from and how they leave: loads and prefetch
-// depth, LDS staging and swizzle, 16- or 32-byte row segments, buffer stores.  The 128x128 / 64x128 kernel's `epilogue`, whose fold
-// role is a run-time choice, keeps the same chain written out (the reason stands above it).  Everything here has internal linkage
-// (anonymous namespace / templates); the files are split only so that they compile in parallel.
+// constants and the block remap: kernel arguments, the tile walk (gemm_walk.h), the two-wave-group main loop (gemm_pingpong.h: slot
+// protocol, BK = 32 lane constants, persistent walk, dual-weight step), the live-row clamp, the LDS-DMA helpers and the fused epilogue.
+// The launch decision - kernel kinds, tiles, grids, split-K plans, the profile label - is host arithmetic and lives in gemm_plan.h;
+// the launchers below take its finished GemmPlan.  There is ONE epilogue value chain (epi_value, epi_residual) and one rounding /
+// [hi | lo | hi] store (store4 / store8, ofx_common.h); the kernels reach it by several routes - epilogue2's fp32 and operand-type
+// branches, epilogue_direct (accumulator layout), splitk_reduce_kernel - which differ only in where the values come from and how they
+// leave: loads and prefetch depth, LDS staging and swizzle, 16- or 32-byte row segments, buffer stores.  The 128x128 / 64x128 kernel's
+// `epilogue`, whose fold role is a run-time choice, keeps the same chain written out (the reason stands above it).  Everything here has
+// internal linkage (anonymous namespace / templates); the files are split only so that they compile in parallel.
 #pragma once
 #include <type_traits>
 
 #include "gemm_pingpong.h"
+#include "gemm_plan.h"
 #include "gemm_walk.h"
 #include "ofx_common.h"
-
-// The NT GEMM kernels by number.  The same numbers are the values of ofx_tune(2, v) (g_gemm_kernel: 0 = the automatic choice; 6 forces
-// only the kernel of split-weight GEMMs) and the `kind` of the profile records (include/ofx.h), where 7 - no dispatcher kind - labels
-// the fused QKV projection + attention launch of fused_qkv_attn.hip.
-//   kind   tile      kernel                 notes
-//   1      128x128   gemm_128x128_kernel    4 waves; carries the split-K plans and, planned or forced, the 64-row variant
-//   2      256x256   gemm_big_kernel        8 waves, two LDS stages
-//   3      256x128   gemm_big_kernel        4 waves, register-resident k-tile, two blocks per CU
-//   4      256x256   gemm_pp_kernel         ping-pong wave groups (short K)
-//   5      64x128    gemm_128x128_kernel    the 64-row variant, forced (ofx_tune only)
-//   6      256x256   gemm_w2_kernel         dual weight [hi | lo] against one copy of A
-//   8      256x256   gemm_w2f8_kernel       kind 6 with the correction product on the fp8 matrix instruction (never forced: chosen from 6)
-//   9      256x128   gemm_x3_kernel         three products with the operand tiles loaded once (never forced: ofx_tune(15, v))
-enum GemmKind { GEMM_AUTO = 0, GEMM_128 = 1, GEMM_256 = 2, GEMM_256x128 = 3, GEMM_PP = 4, GEMM_64 = 5, GEMM_W2 = 6, GEMM_W2F8 = 8, GEMM_X3 = 9 };
-// the big-tile kernels live in their own translation units behind the ofx_gemm_launch_* functions at the end of this file
-inline bool gemm_kind_big_tile(int kind) {
-    return kind == GEMM_256 || kind == GEMM_256x128 || kind == GEMM_PP || kind == GEMM_W2 || kind == GEMM_W2F8 || kind == GEMM_X3;
-}
 
 namespace {
 
@@ -476,9 +460,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(KArgs p) {
 
 }  // namespace
 
-// launchers implemented by the other translation units (KArgs travels as an opaque pointer: each unit sees the same definition)
-int ofx_gemm_launch_big(void* kargs, int kind, int op_dtype, int M, int N, hipStream_t s);
-int ofx_gemm_launch_pp(void* kargs, int op_dtype, int M, int N, hipStream_t s);
-int ofx_gemm_launch_w2(void* kargs, int op_dtype, int M, int N, hipStream_t s);
-int ofx_gemm_launch_w2f8(void* kargs, int M, int N, hipStream_t s);
-int ofx_gemm_launch_x3(void* kargs, int op_dtype, int M, int N, hipStream_t s);
+// launchers implemented by the other translation units (KArgs travels as an opaque pointer: each unit sees the same definition).
+// ofx_launch_gemm has filled KArgs from the plan; a launcher owns what is tied to its kernel template - the LDS size, the attribute
+// call, the launch over plan.grid_x blocks.
+int ofx_gemm_launch_big(void* kargs, const GemmPlan& plan, int op_dtype, hipStream_t s);
+int ofx_gemm_launch_pp(void* kargs, const GemmPlan& plan, int op_dtype, hipStream_t s);
+int ofx_gemm_launch_w2(void* kargs, const GemmPlan& plan, int op_dtype, hipStream_t s);
+int ofx_gemm_launch_w2f8(void* kargs, const GemmPlan& plan, hipStream_t s);
+int ofx_gemm_launch_x3(void* kargs, const GemmPlan& plan, int op_dtype, hipStream_t s);

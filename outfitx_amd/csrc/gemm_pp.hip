@@ -135,18 +135,17 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(KArgs p) {
 
 
 template <typename T>
-static int launch_pp(KArgs& k, int M, int N, hipStream_t s) {
+static int launch_pp(const KArgs& k, const GemmPlan& plan, hipStream_t s) {
     constexpr int LDSB = 2 * (256 + 256) * BK * 2 + 8 * EPI2_BYTES_PER_WAVE;
     static DeviceOnce attr;
     TRY(set_max_dynamic_lds(attr, gemm_pp_kernel<T>, LDSB));
-    k.tiles_n = N / 256; k.tiles_m = (M + 255) / 256; k.nwg = k.tiles_m * k.tiles_n;
-    OFX_PLAUNCH(true, (gemm_pp_kernel<T>), dim3(k.nwg), dim3(512), LDSB, s, k);
+    OFX_PLAUNCH(true, (gemm_pp_kernel<T>), dim3(plan.grid_x), dim3(512), LDSB, s, k);
     return OFX_OK;
 }
 
 }  // namespace
 
-int ofx_gemm_launch_pp(void* kargs, int op_dtype, int M, int N, hipStream_t s) {
-    KArgs& k = *(KArgs*)kargs;
-    return op_dtype == OFX_F16 ? launch_pp<f16_t>(k, M, N, s) : launch_pp<bf16_t>(k, M, N, s);
+int ofx_gemm_launch_pp(void* kargs, const GemmPlan& plan, int op_dtype, hipStream_t s) {
+    const KArgs& k = *(const KArgs*)kargs;
+    return op_dtype == OFX_F16 ? launch_pp<f16_t>(k, plan, s) : launch_pp<bf16_t>(k, plan, s);
 }

@@ -159,25 +159,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_kernel(TnArgs p) {
 
 }  // namespace
 
-// ---- TN GEMM (wgrad): split plan + launcher
-int ofx_gemm_tn_splits(int M, int N, int K) {
-    // cost model (us): waves of blocks x k-tiles per split x ~1.6 us per 256x256x64 k-tile, plus the slab written once and
-    // read once at ~4 TB/s.  K is the static upper bound of the live row count, so the plan is shape-only (graph-safe).
-    const long tiles = (long)((M + 255) / 256) * (N / 256);
-    const int nkt = (K + 63) / 64;
-    int best = 1;
-    double best_t = 1e30;
-    for (int s = 1; s <= 16 && s <= nkt; ++s) {
-        const double waves = (double)((tiles * s + 255) / 256);
-        const double t = waves * ((nkt + s - 1) / s) * 1.6 + 4.0 + (s > 1 ? 2.0 * s * M * N * 4.0 / 4.0e6 + 3.0 : 0.0);
-        if (t < best_t) { best_t = t; best = s; }
-    }
-    return best;
-}
-size_t ofx_gemm_tn_slab_bytes(int M, int N, int K) {
-    const int s = ofx_gemm_tn_splits(M, N, K);
-    return s > 1 ? (size_t)s * M * N * 4 : 0;
-}
+// ---- TN GEMM (wgrad): launcher (split plan: gemm_tn_splits, gemm_plan.h)
+size_t ofx_gemm_tn_slab_bytes(int M, int N, int K) { return gemm_tn_slab_bytes(M, N, K); }
 int ofx_launch_gemm_tn(const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, int K, const int* k_dev,
                        void* slab, size_t slab_bytes, int op_dtype, hipStream_t s, int m_valid, int n_valid, int accumulate) {
     if (m_valid <= 0) m_valid = M;
@@ -191,7 +174,7 @@ int ofx_launch_gemm_tn(const void* A, int lda, const void* B, int ldb, float* C,
     TnArgs t;
     t.A = (const char*)A; t.B = (const char*)B; t.C = C; t.slab = (float*)slab; t.k_dev = k_dev;
     t.M = M; t.N = N; t.K = K; t.lda = lda; t.ldb = ldb; t.ldc = ldc; t.m_valid = m_valid; t.n_valid = n_valid; t.accumulate = accumulate;
-    t.splits = slab ? ofx_gemm_tn_splits(M, N, K) : 1;
+    t.splits = slab ? gemm_tn_splits(M, N, K) : 1;
     if (t.splits > 1) OFX_REQUIRE(slab_bytes >= (size_t)t.splits * M * N * 4, OFX_EWORKSPACE, "gemm_tn: split-K slab too small");
     t.tiles_m = M / 256; t.tiles_n = N / 256; t.nwg = t.tiles_m * t.tiles_n * t.splits; t.group_m = 4;
     constexpr int LDSB = 2 * 4 * 64 * 256 + 8 * EPI2_BYTES_PER_WAVE;

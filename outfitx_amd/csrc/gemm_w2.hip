@@ -13,7 +13,6 @@
 // steps nk and nk + 1 fetch the next tile's first two steps under the current epilogue (see the kernel body).
 #include "gemm_common.h"
 
-extern int g_w2_persist;
 namespace {
 
 template <typename T>
@@ -138,19 +137,17 @@ __global__ __launch_bounds__(512, 2) void gemm_w2_kernel(KArgs p) {
 }
 
 template <typename T>
-static int launch_w2(KArgs& k, int M, int N, hipStream_t s) {
+static int launch_w2(const KArgs& k, const GemmPlan& plan, hipStream_t s) {
     constexpr int LDSB = 3 * 3 * 256 * 32 * 2;          // 144 KiB
     static DeviceOnce attr;
     TRY(set_max_dynamic_lds(attr, gemm_w2_kernel<T>, LDSB));
-    k.tiles_n = N / 256; k.tiles_m = (M + 255) / 256; k.nwg = k.tiles_m * k.tiles_n;
-    const int grid = ofx_persistent_grid(k.nwg, g_w2_persist, k.m_dev != nullptr);
-    OFX_PLAUNCH(true, (gemm_w2_kernel<T>), dim3(grid), dim3(512), LDSB, s, k);
+    OFX_PLAUNCH(true, (gemm_w2_kernel<T>), dim3(plan.grid_x), dim3(512), LDSB, s, k);
     return OFX_OK;
 }
 
 }  // namespace
 
-int ofx_gemm_launch_w2(void* kargs, int op_dtype, int M, int N, hipStream_t s) {
-    KArgs& k = *(KArgs*)kargs;
-    return op_dtype == OFX_F16 ? launch_w2<f16_t>(k, M, N, s) : launch_w2<bf16_t>(k, M, N, s);
+int ofx_gemm_launch_w2(void* kargs, const GemmPlan& plan, int op_dtype, hipStream_t s) {
+    const KArgs& k = *(const KArgs*)kargs;
+    return op_dtype == OFX_F16 ? launch_w2<f16_t>(k, plan, s) : launch_w2<bf16_t>(k, plan, s);
 }

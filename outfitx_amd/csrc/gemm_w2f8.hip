@@ -46,7 +46,6 @@
 // tile's last fp8 slot and the next tile's refill.
 #include "gemm_common.h"
 
-extern int g_w2_persist, g_epi_direct;
 namespace {
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
@@ -314,15 +313,12 @@ __global__ __launch_bounds__(256) void pack_lo8_kernel(const f16_t* src, unsigne
 
 }  // namespace
 
-int ofx_gemm_launch_w2f8(void* kargs, int M, int N, hipStream_t s) {
-    KArgs& k = *(KArgs*)kargs;
+int ofx_gemm_launch_w2f8(void* kargs, const GemmPlan& plan, hipStream_t s) {
+    const KArgs& k = *(const KArgs*)kargs;
     constexpr int LDSB = 4 * 2 * 256 * 32 * 2 + 256 * 128;              // 128 KiB of stages + the 32 KiB fp8 weight buffer = 160 KiB
     static DeviceOnce attr;
     TRY(set_max_dynamic_lds(attr, gemm_w2f8_kernel, LDSB));
-    k.tiles_n = N / 256; k.tiles_m = (M + 255) / 256; k.nwg = k.tiles_m * k.tiles_n;
-    k.epi_direct = g_epi_direct;
-    const int grid = ofx_persistent_grid(k.nwg, g_w2_persist, k.m_dev != nullptr);
-    OFX_PLAUNCH(true, gemm_w2f8_kernel, dim3(grid), dim3(512), LDSB, s, k);
+    OFX_PLAUNCH(true, gemm_w2f8_kernel, dim3(plan.grid_x), dim3(512), LDSB, s, k);
     return OFX_OK;
 }
 

@@ -14,7 +14,6 @@
 // (bload16 / make_rsrc, gemm_common.h: rows past M read zeros).
 #include "gemm_common.h"
 
-extern int g_w2_persist, g_x3_persist;
 namespace {
 
 template <typename T>
@@ -124,20 +123,17 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_kernel(KArgs p) {
 }
 
 template <typename T>
-static int launch_x3(KArgs& k, int M, int N, hipStream_t s) {
+static int launch_x3(const KArgs& k, const GemmPlan& plan, hipStream_t s) {
     constexpr int LDSB = 3 * (2 * 256 + 2 * 128) * 32 * 2;          // 144 KiB
     static DeviceOnce attr;
     TRY(set_max_dynamic_lds(attr, gemm_x3_kernel<T>, LDSB));
-    k.tiles_n = N / 128; k.tiles_m = (M + 255) / 256; k.nwg = k.tiles_m * k.tiles_n;
-    // ofx_tune(16, 0): one block per tile (short-lived blocks: a side stream's GEMM then frees its CUs tile by tile)
-    const int grid = ofx_persistent_grid(k.nwg, g_x3_persist == 1 ? g_w2_persist : 0, k.m_dev != nullptr);
-    OFX_PLAUNCH(true, (gemm_x3_kernel<T>), dim3(grid), dim3(512), LDSB, s, k);
+    OFX_PLAUNCH(true, (gemm_x3_kernel<T>), dim3(plan.grid_x), dim3(512), LDSB, s, k);
     return OFX_OK;
 }
 
 }  // namespace
 
-int ofx_gemm_launch_x3(void* kargs, int op_dtype, int M, int N, hipStream_t s) {
-    KArgs& k = *(KArgs*)kargs;
-    return op_dtype == OFX_F16 ? launch_x3<f16_t>(k, M, N, s) : launch_x3<bf16_t>(k, M, N, s);
+int ofx_gemm_launch_x3(void* kargs, const GemmPlan& plan, int op_dtype, hipStream_t s) {
+    const KArgs& k = *(const KArgs*)kargs;
+    return op_dtype == OFX_F16 ? launch_x3<f16_t>(k, plan, s) : launch_x3<bf16_t>(k, plan, s);
 }

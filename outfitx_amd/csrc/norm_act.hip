@@ -105,7 +105,7 @@ __global__ __launch_bounds__(64 * NW) void splitk_reduce_ln_kernel(SplitKLnArgs 
 }  // namespace
 
 int ofx_launch_splitk_reduce_ln(const SplitKLnArgs& a, int op_dtype, hipStream_t s, bool in_gemm_scope) {
-    OFX_REQUIRE(a.D == 512 || a.D == 768 || a.D == 1024 || a.D == 1536, OFX_ESHAPE, "splitk_reduce_ln: D=%d not in {512,768,1024,1536}", a.D);
+    OFX_REQUIRE(splitk_reduce_ln_width_ok(a.D), OFX_ESHAPE, "splitk_reduce_ln: D=%d not in {512,768,1024,1536}", a.D);
     OFX_REQUIRE(a.rows > 0 && a.splits >= 1 && a.ldx % 4 == 0 && a.ldx >= a.D && (!a.resid || (a.ldr % 4 == 0 && a.ldr >= a.D)), OFX_ESHAPE, "splitk_reduce_ln: bad shape");
     OFX_REQUIRE(a.ldy % 4 == 0 && a.ldy >= (a.out_kind == 2 ? 3 * a.D : a.D), OFX_ESHAPE, "splitk_reduce_ln: bad ldy=%d", a.ldy);
     const int grid = a.rows > 8192 ? 8192 : a.rows;

@@ -7,6 +7,7 @@
 #include <stdio.h>
 
 #include "../../include/ofx.h"
+#include "gemm_plan.h"      // host-only: the GEMM launch decision, and splitk_reduce_ln_width_ok for ofx_launch_splitk_reduce_ln
 
 typedef __bf16 bf16_t;
 typedef _Float16 f16_t;
@@ -228,10 +229,6 @@ int set_max_dynamic_lds(DeviceOnce& once, K kernel, int bytes) {
 
 // CU count of the CURRENT device, cached per device ordinal (256 if the query fails).
 int device_cu_count();
-// Grid of a kernel whose blocks can walk tiles b, b + grid, ... over nwg tiles.  persist: -1 = one block per CU of the current
-// device, 0 = one block per tile, n = n blocks.  A device-side row count (has_m_dev) always takes one block per tile: tiles past
-// the live rows leave at once.  Never more blocks than tiles.
-int ofx_persistent_grid(int nwg, int persist, bool has_m_dev);
 
 struct Bump {                                       // carve a caller-provided workspace
     char* base; size_t cap, off = 0; bool ok = true;
@@ -312,7 +309,8 @@ struct GemmArgs {
     // fp8 correction product (gemm_w2f8.hip): with a_wrap, the e4m3 copy of the rows' lo halves [N, a_wrap] bytes and its per-row scale
     // bytes (ofx_launch_pack_lo8); when the dual-weight 256x256 kernel would run, its fp8 variant runs instead (f16 only, a_wrap % 128 == 0)
     const void* W8 = nullptr; const void* w8_scale = nullptr;
-    int k_mult = 1;     // informational (profile records): K = k_mult x the logical depth (3: three-product K-concatenation; a_wrap implies 2)
+    int k_mult = 1;     // K = k_mult x the logical depth.  3 = three-product K-concatenation (A rows [hi | lo | hi], W rows [hi | hi | lo]): makes the GEMM eligible for
+                        // gemm_x3_kernel (kind 9, gemm_plan.h) and labels the profile record; other values only label the record (a_wrap implies 2)
     // ---- small batches (split-K plans): let the NEXT kernel do the second pass, one launch less per linear layer.
     // defer_splits: when the plan splits K, the reduce pass is skipped and *defer_splits = number of slabs (fp32 [splits, M, N] at
     // `slab`, bias / activation / residual NOT applied: the consumer sums them); left at 1 when the output was written normally.
@@ -323,7 +321,8 @@ struct GemmArgs {
     bool* ln_done = nullptr;
 };
 int ofx_launch_gemm(const GemmArgs& g, int op_dtype /*OFX_BF16|OFX_F16*/, hipStream_t s);
-size_t ofx_gemm_splitk_bytes(int M, int N, int K);
+size_t ofx_gemm_splitk_bytes(int M, int N, int K);      // under the current knobs
+int ofx_gemm_tune(int knob, int value);      // ofx_tune's knobs 2, 5, 11, 15, 16, 18: the GemmKnobs object of gemm.hip
 
 struct LnArgs {
     const float* x;        // [rows_in, D] fp32
@@ -336,7 +335,6 @@ struct LnArgs {
     float eps;
     float* stats = nullptr;  // optional [rows, 2] (mean, rstd) for the backward pass
 };
-int ofx_gemm_tn_splits(int M, int N, int K);
 size_t ofx_gemm_tn_slab_bytes(int M, int N, int K);
 int ofx_launch_gemm_tn(const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, int K, const int* k_dev,
                        void* slab, size_t slab_bytes, int op_dtype, hipStream_t s, int m_valid = 0, int n_valid = 0, int accumulate = 0);
@@ -348,6 +346,7 @@ struct SplitKLnArgs {       // split-K second pass + LayerNorm in one launch (no
     const float* gamma; const float* beta; void* y; int ldy, out_kind; float eps;
     int rows, D; const int* m_dev;
 };
+// (its widths: splitk_reduce_ln_width_ok, gemm_plan.h - the launcher's check and the GEMM plan's gate of this route are the one predicate)
 int ofx_launch_splitk_reduce_ln(const SplitKLnArgs& a, int op_dtype, hipStream_t s, bool in_gemm_scope = false);   // in_gemm_scope: the launch closes the GEMM dispatcher's profile record
 int ofx_launch_layernorm_dev(const LnArgs& a, const int* rows_dev, int op_dtype, hipStream_t s);
 // fp8 (e4m3) copy of the lo half of split-weight rows [hi | lo] (f16) + per-row E8M0 scale bytes, in gemm_w2f8.hip's layouts
@@ -461,6 +460,5 @@ int ofx_launch_l2_topk_grouped(const float* Q, const float* P, int nq, int np, i
 int ofx_launch_topk_merge(const int64_t* idx_in, const float* dist_in, int parts, int nq, int k, int64_t* idx, float* dist,
                           hipStream_t s);
 
-// ---- ofx_tune knobs defined outside api.hip (gemm.hip, scoring.hip)
-extern int g_topk_filter, g_epi_direct;
-extern int g_gemm_kernel, g_gemm_splitk, g_w2_persist, g_x3_kernel, g_x3_persist;
+// ---- ofx_tune knobs defined outside api.hip (scoring.hip; the GEMM launch knobs go through ofx_gemm_tune)
+extern int g_topk_filter;

@@ -117,7 +117,7 @@ def test_gemm_split_weights_persistent_grid_is_bit_identical_to_one_block_per_ti
 
 
 def _recorded_kinds(lib):
-    """Kernel kinds (GemmKind, csrc/gemm_common.h) of the GEMM launches since ofx_profile_enable(1)."""
+    """Kernel kinds (GemmKind, csrc/gemm_plan.h) of the GEMM launches since ofx_profile_enable(1)."""
     recs = (L.ProfRecord * 16)()
     n = lib.ofx_profile_records(recs, 16)
     ms, fl, cnt = (C.c_double * 4)(), (C.c_double * 4)(), (C.c_longlong * 4)()
