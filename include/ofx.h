@@ -409,7 +409,8 @@ int ofx_profile_records(ofx_prof_record* out, int cap);
 /* Process-wide tuning knobs (benchmarks / tests only).  Unknown knobs return OFX_EINVAL.
  * knob 2: GEMM kernel, 0 (default) = the automatic choice, 1 = 128x128, 2 = 256x256, 3 = 256x128, 4 = 256x256 ping-pong, 5 = 64x128,
  *         6 = the dual-weight 256x256 kernel for split weights (every other GEMM keeps the automatic choice);
- * knob 5: split-K of small GEMMs, 1 (default) = planned, 0 = never, >= 2 = forced (low byte = splits, bit 8 = 64-row tiles);
+ * knob 5: split-K of small GEMMs, 1 (default) = planned, 0 = never, >= 2 = forced (low byte = splits, bit 8 = 64-row tiles; a forced value whose
+ *         low byte is 0 names no slices and is OFX_EINVAL);
  * knob 6: accepts only 2, the one tower form (a no-op kept for callers that set it): the CLIP towers' LayerNorms are folded into the
  *         neighbouring GEMM epilogues and their residual stream is an operand-type (hi, lo) pair updated in place; 0 and 1 (fp32 stream,
  *         materialised LayerNorms) are retired and return OFX_EINVAL;

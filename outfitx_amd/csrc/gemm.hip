@@ -145,7 +145,9 @@ static GemmKnobs g_knobs;
 int ofx_gemm_tune(int knob, int value) {
     switch (knob) {
         case 2: g_knobs.kernel = value; return OFX_OK;
-        case 5: g_knobs.splitk = value; return OFX_OK;
+        case 5:      // a forced plan (>= 2) names its slice count in the low byte: none would divide by zero in gemm_plan_small
+            if (value >= 2 && (value & 0xff) == 0) { ofx_set_error("ofx_tune(5): %d forces a split-K plan of 0 slices (low byte = slices, 1-16)", value); return OFX_EINVAL; }
+            g_knobs.splitk = value; return OFX_OK;
         case 11: g_knobs.w2_persist = value; return OFX_OK;
         case 15: g_knobs.x3_kernel = value; return OFX_OK;
         case 16: g_knobs.x3_persist = value != 0; return OFX_OK;

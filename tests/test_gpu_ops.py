@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import gemm_exact_cases as X
 from conftest import rel_err
 from oracle import np_oracle as O
 
@@ -54,16 +55,8 @@ def test_gemm_plain(dt, M, N, K):
 
 
 def _split_w(Wf, dt):
-    """fp32 [N, K] -> ([N, 2K] operand-type [hi | lo] via ofx_convert mode 3, float64 value hi + lo)."""
-    N, K = Wf.shape
-    src = dev(Wf)
-    td = torch.bfloat16 if dt == "bf16" else torch.float16
-    W2 = torch.empty(N, 2 * K, dtype=td, device="cuda")
-    L.check(L.load().ofx_convert(src.data_ptr(), W2.data_ptr(), N, K, 3, DT[dt], stream()))
-    hi = src.to(td)
-    lo = (src - hi.float()).to(td)
-    assert torch.equal(W2[:, :K], hi) and torch.equal(W2[:, K:], lo)
-    return W2, (hi.double() + lo.double()).cpu().numpy()
+    """fp32 [N, K] -> ([N, 2K] operand-type [hi | lo] via ofx_convert mode 3, float64 value hi + lo); shared with the exact tests."""
+    return X._split_w(L, Wf, dt)
 
 
 @pytest.mark.parametrize("force", [0, 6])
@@ -285,27 +278,10 @@ def test_gemm_three_products_from_operand_tiles_loaded_once(dt, M, N, K, ep):
     assert rel_err(outs[0], outs[1]) < 2 * tol
 
 
-def _e4m3_decode(b):
-    """uint8 ndarray (OCP e4m3fn bit patterns) -> float64 values."""
-    b = b.astype(np.int64)
-    s, e, m = b >> 7, (b >> 3) & 15, b & 7
-    v = np.where(e == 0, m * 2.0 ** -9, (1.0 + m / 8.0) * 2.0 ** (e - 7.0))
-    return np.where(s == 1, -v, v)
-
-
 def _pack_lo8(W2, N, K):
-    """ofx_pack_lo8 on the device; returns (W8 bytes tensor, scale bytes tensor, lo values as the kernel will see them [N, K] float64
-    in natural k order = e4m3(byte) 2^-sw, per-row sw)."""
-    W8 = torch.zeros(N, K, dtype=torch.uint8, device="cuda")
-    sc = torch.zeros(N, dtype=torch.uint8, device="cuda")
-    L.check(L.load().ofx_pack_lo8(W2.data_ptr(), W8.data_ptr(), sc.data_ptr(), N, K, stream()))
-    torch.cuda.synchronize()
-    b = W8.cpu().numpy().reshape(N, K // 128, 4, 4, 8)                 # [n][block][g][s][j] <- k = 32 s + 8 g + j
-    nat = _e4m3_decode(b).transpose(0, 1, 3, 2, 4).reshape(N, K)       # [n][block][s][g][j] -> natural k
-    scb = sc.cpu().numpy().reshape(N // 128, 16, 8)                    # [(n >> 7)][n & 15][(n >> 4) & 7]
-    n = np.arange(N)
-    sw = 127 - scb[n >> 7, n & 15, (n >> 4) & 7].astype(np.int64)
-    return W8, sc, nat * 2.0 ** (-sw[:, None].astype(np.float64)), sw
+    """ofx_pack_lo8 on the device -> (W8 bytes, scale bytes, lo as the kernel will see it [N, K] float64 in natural k order, per-row sw);
+    decoded by gemm_exact_cases._e4m3_decode, shared with the exact tests."""
+    return X._pack_lo8(L, W2, N, K)
 
 
 @pytest.mark.parametrize("N,K", [(256, 128), (768, 3072), (3072, 768)])
