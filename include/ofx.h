@@ -144,6 +144,16 @@ int ofx_vit_b32_fwd(ofx_handle* h, const float* pixels, int N, float* emb, int e
 int ofx_clip_text_fwd(ofx_handle* h, const int64_t* ids, const int64_t* attn_mask, const int* lengths_host,
                       int N, int T, float* emb, int emb_ld, int emb_col, int normalize, void* ws,
                       size_t ws_bytes, ofx_stream stream);
+/* The same with the texts' common first position computed once.  shared_first != 0 is the CALLER'S word that (a) ids[i, 0] is the same
+ * token for every text (CLIP's BOS), (b) attn_mask is NULL or non-zero in column 0 of every text.  The tower is causal, so position 0 attends
+ * to itself only and is then the same row for every text in every layer: the three-product scheme (txt_x3) computes it once, on
+ * 1 + N (Tc - 1) rows instead of N Tc (Tc = computed tokens per text) - the same bits as ofx_clip_text_fwd wherever the full-row GEMMs do
+ * not plan split-K (batches beyond a few texts; then the fp32 summation order depends on the row count as it does between two batch sizes).
+ * The flag is ignored - the call IS ofx_clip_text_fwd - when shared_first == 0, Tc < 2, the text scheme is not the three-product one, or
+ * ofx_tune(21, 0) is set.  Same workspace size (ofx_workspace_bytes(OFX_OP_TEXT)).  Added within ABI version 6: nothing existing changed. */
+int ofx_clip_text_fwd_shared(ofx_handle* h, const int64_t* ids, const int64_t* attn_mask, const int* lengths_host,
+                             int N, int T, float* emb, int emb_ld, int emb_col, int normalize, int shared_first, void* ws,
+                             size_t ws_bytes, ofx_stream stream);
 
 /* Row H: torch.cdist(y[B,1,D], cand[B,C,D]).squeeze(1).argmin(-1) (fill_in_the_blank_trainer.py:50-56).
  * idx int64 [B] = the first minimum; dist fp32 [B,C] optional.  D a multiple of 4 (else OFX_EINVAL); rows are read as 16-byte vectors.
@@ -429,7 +439,8 @@ int ofx_profile_records(ofx_prof_record* out, int cap);
  * knob 18: 1 (default) the split-weight GEMM's f16 outputs (qkv, fc1) are stored straight from the accumulator layout, 0 = through the LDS
  *          transpose of rounds 1-3; any other value is OFX_EINVAL.  Bit-identical results.
  * knob 20: validation only, default 0: 1 = a three-product ViT (vit_x3) keeps q | k | v in fp32 and runs the fp32 attention kernel instead of the MFMA attention
- *          on operand-rounded q | k | v (several times slower; tools/parity_selfcheck.py uses it for its reference run). */
+ *          on operand-rounded q | k | v (several times slower; tools/parity_selfcheck.py uses it for its reference run).
+ * knob 21: 1 (default) ofx_clip_text_fwd_shared honours its shared_first flag, 0 = it runs the full rows (A/B runs and tests). */
 int ofx_tune(int knob, int value);
 /* A counter that every ofx_tune call bumps, and whether per-launch profiling events are being recorded: the host mirror replays a
  * stream-captured forward (outfitx_amd/graphs.py) only while the counter still has the value it had at capture time and no recording

@@ -137,6 +137,7 @@ SIGNATURES = {
     "ofx_cir_prefix": (_i, [_vp, _vp, _i, _vp, _vp]),
     "ofx_vit_b32_fwd": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp]),
     "ofx_clip_text_fwd": (_i, [_vp, _vp, _vp, C.POINTER(_i), _i, _i, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "ofx_clip_text_fwd_shared": (_i, [_vp, _vp, _vp, C.POINTER(_i), _i, _i, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "ofx_fitb_argmin": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "ofx_fitb_argmin_indexed": (_i, [_vp, _i, C.c_longlong, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "ofx_l2_topk": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _sz, _vp]),

@@ -636,7 +636,8 @@ static int clip_layer(const ClipLayer& L, const ClipWs& w, int rows, int nseq, i
 // writing [hi | lo | hi] rows, weights packed [hi | hi | lo] (the outfit transformer's bf16x3 scheme in the towers' operand type).
 // q | k | v leave the projection rounded once to the operand type for the MFMA attention, whose output is again (hi, lo).
 static int clip_layer_x3(const ClipLayer& L, const ClipWs& w, int rows, int nseq, int S, int W, int MLP, int heads, int act,
-                         float eps, int causal, const int64_t* key_mask, int mask_ld, int dt, const int* pool_idx, hipStream_t s, bool mfma_attn = false) {
+                         float eps, int causal, const int64_t* key_mask, int mask_ld, int dt, const int* pool_idx, hipStream_t s, bool mfma_attn = false,
+                         int shared_first = 0) {
     LnArgs ln{w.X, nullptr, L.g1, L.be1, w.H, rows, W, 3 * W, OFX_OUT_SPLIT3, eps};
     TRY(ofx_launch_layernorm(ln, dt, s));
     GemmArgs g1{}; g1.A = w.H; g1.C = w.QKV; g1.M = rows; g1.N = 3 * W;
@@ -648,11 +649,13 @@ static int clip_layer_x3(const ClipLayer& L, const ClipWs& w, int rows, int nseq
     // (the ViT in its three-product mode keeps the MFMA attention: 2,048 images x 12 heads of 50 tokens in fp32 VALU arithmetic would
     // cost more than the layer's GEMMs, and the attention core's operand rounding is the smallest term of its budget, 6e-5)
     const bool f32_attn = S <= 64 && !mfma_attn;
+    // shared_first (text tower): `rows` = 1 + nseq * (S - 1) in the shared-first-row map; only the attention knows (everything else is row-wise)
+    OFX_REQUIRE(!shared_first || f32_attn, OFX_EINVAL, "clip_layer_x3: a shared first row needs the fp32 set attention");
     g1.ldc = 3 * W; g1.act = OFX_ACT_NONE; g1.out_kind = f32_attn ? OFX_OUT_F32 : OFX_OUT_OP;
     TRY(ofx_launch_gemm(g1, dt, s));
     if (f32_attn) {
         SetAttnArgs sa{w.QKV, w.H, nullptr, nseq, heads, W, 3 * W, OFX_OUT_SPLIT3, S, 0, 0.125f};
-        sa.fixed_len = S; sa.causal = causal; sa.key_mask = key_mask; sa.mask_ld = mask_ld;
+        sa.fixed_len = S; sa.causal = causal; sa.key_mask = key_mask; sa.mask_ld = mask_ld; sa.shared_first = shared_first;
         TRY(ofx_launch_set_attention(sa, dt, s));
     } else {
         AttnArgs at{w.QKV, w.H, key_mask, nseq, S, heads, 3 * W, 3 * W, W, 2 * W, mask_ld, causal, 0.125f};
@@ -685,10 +688,12 @@ static int clip_layer_x3(const ClipLayer& L, const ClipWs& w, int rows, int nseq
 // statistics, in w.XB / w.XLO / w.S.
 static int clip_layers(const std::vector<ClipLayer>& Ls, const ClipWs& w, int rows, int nseq, int S, int W, int MLP,
                        int heads, int act, float eps, int causal, const int64_t* key_mask, int mask_ld, int dt,
-                       const int* pool_idx, hipStream_t s, bool pool_first, bool x3) {
+                       const int* pool_idx, hipStream_t s, bool pool_first, bool x3, int shared_first = 0) {
+    OFX_REQUIRE(!shared_first || x3, OFX_EINVAL, "clip_layers: a shared first row exists in the three-product path only");
     if (x3) {
         for (size_t l = 0; l < Ls.size(); ++l)
-            TRY(clip_layer_x3(Ls[l], w, rows, nseq, S, W, MLP, heads, act, eps, causal, key_mask, mask_ld, dt, l + 1 == Ls.size() ? pool_idx : nullptr, s, !causal && !key_mask && !g_x3_vit_f32_attn));
+            TRY(clip_layer_x3(Ls[l], w, rows, nseq, S, W, MLP, heads, act, eps, causal, key_mask, mask_ld, dt, l + 1 == Ls.size() ? pool_idx : nullptr, s, !causal && !key_mask && !g_x3_vit_f32_attn,
+                              shared_first));
         return OFX_OK;
     }
     for (size_t l = 0; l < Ls.size(); ++l)
@@ -769,9 +774,16 @@ extern "C" int ofx_vit_b32_fwd_u8(ofx_handle* h, const uint8_t* src, const long 
     return vit_core(h, nullptr, &raw, N, emb, emb_ld, emb_col, normalize, (char*)ws + pre, ws_bytes - pre, stream);
 }
 
-extern "C" int ofx_clip_text_fwd(ofx_handle* h, const int64_t* ids, const int64_t* attn_mask, const int* lengths_host,
-                                 int N, int T, float* emb, int emb_ld, int emb_col, int normalize, void* ws,
-                                 size_t ws_bytes, ofx_stream stream) {
+int g_text_shared_first = 1;      // ofx_tune(21, v): 1 (default) ofx_clip_text_fwd_shared computes the texts' common first-position row once, 0 = it runs the full rows
+
+// shared_first: the caller vouches that every text starts with the same token and no text masks position 0.  The text tower is causal, so
+// position 0 sees itself only and carries the same bits for every text in every layer: the three-product path then computes it once.  Row 0
+// is that row, position t >= 1 of text i is row 1 + i * (Tc - 1) + (t - 1), rows = 1 + N * (Tc - 1) instead of N * Tc; the LayerNorms, GEMMs
+// and gathers are row-wise and only see fewer rows, the embedding, the EOS index and the attention know the map.  Same bits as the full rows
+// wherever the GEMMs' summation order does not depend on M (no split-K plan on the full rows: every batch beyond a few texts).
+static int clip_text_core(ofx_handle* h, const int64_t* ids, const int64_t* attn_mask, const int* lengths_host,
+                          int N, int T, float* emb, int emb_ld, int emb_col, int normalize, int shared_first, void* ws,
+                          size_t ws_bytes, ofx_stream stream) {
     OFX_REQUIRE(h && h->txt_ready, OFX_ESTATE, "clip_text_fwd: text weights not packed");
     OFX_REQUIRE(ids && emb && ws && N > 0 && T > 0, OFX_EINVAL, "clip_text_fwd: bad argument");
     const ofx_model_desc& d = h->d;
@@ -787,13 +799,15 @@ extern "C" int ofx_clip_text_fwd(ofx_handle* h, const int64_t* ids, const int64_
     ClipWs w;
     const size_t need = txt_bytes(h, N, Tc, &w, ws, ws_bytes);
     OFX_REQUIRE(need <= ws_bytes, OFX_EWORKSPACE, "clip_text_fwd: workspace %zu < %zu bytes", ws_bytes, need);
-    const int W = d.txt_width, dt = h->tw_dtype, rows = N * Tc;
-    TRY(ofx_launch_text_embed(ids, h->t_tok, h->t_pos, w.X, N, T, Tc, W, d.txt_vocab, s));
-    TRY(ofx_launch_text_eos_index(ids, w.idx, N, T, Tc, d.txt_eos_id, s));      // EOS rows
     const bool x3 = h->txt_x3 != 0, x3p = x3 || h->proj_x3;
+    // (the single-product / MFMA-attention path keeps the full rows; one token per text has no other rows to share with)
+    const int sf = shared_first && g_text_shared_first && x3 && Tc >= 2 ? 1 : 0;
+    const int W = d.txt_width, dt = h->tw_dtype, rows = sf ? 1 + N * (Tc - 1) : N * Tc;        // fewer rows in the same workspace
+    TRY(ofx_launch_text_embed(ids, h->t_tok, h->t_pos, w.X, N, T, Tc, W, d.txt_vocab, sf, s));
+    TRY(ofx_launch_text_eos_index(ids, w.idx, N, T, Tc, d.txt_eos_id, sf, s));      // EOS rows
     const int pk = x3p ? 3 : 1;
     if (!x3) TRY(ofx_launch_row_stats_cast(w.X, w.XB, w.XLO, w.S, rows, W, d.ln_eps, dt, s));      // layer 0's (hi, lo) stream + LayerNorm-1 statistics
-    TRY(clip_layers(h->tl, w, rows, N, Tc, W, d.txt_mlp, d.txt_heads, d.txt_act, d.ln_eps, 1, attn_mask, T, dt, w.idx, s, false, x3));
+    TRY(clip_layers(h->tl, w, rows, N, Tc, W, d.txt_mlp, d.txt_heads, d.txt_act, d.ln_eps, 1, attn_mask, T, dt, w.idx, s, false, x3, sf));
     LnArgs ln{w.XP, nullptr, h->t_fin_g, h->t_fin_b, w.PL, N, W, pk * W, x3p ? OFX_OUT_SPLIT3 : OFX_OUT_OP, d.ln_eps};
     TRY(ofx_launch_layernorm(ln, dt, s));
     GemmArgs gj{}; gj.A = w.PL; gj.C = w.E; gj.M = N; gj.N = d.proj_dim; gj.ldc = d.proj_dim;
@@ -801,6 +815,17 @@ extern "C" int ofx_clip_text_fwd(ofx_handle* h, const int64_t* ids, const int64_
     gj.act = OFX_ACT_NONE; gj.out_kind = OFX_OUT_F32; gj.slab = w.slab; gj.slab_bytes = w.slab_bytes;
     TRY(ofx_launch_gemm(gj, dt, s));
     return ofx_launch_l2norm_store(w.E, emb, N, d.proj_dim, emb_ld, emb_col, normalize, s);
+}
+
+extern "C" int ofx_clip_text_fwd(ofx_handle* h, const int64_t* ids, const int64_t* attn_mask, const int* lengths_host,
+                                 int N, int T, float* emb, int emb_ld, int emb_col, int normalize, void* ws,
+                                 size_t ws_bytes, ofx_stream stream) {
+    return clip_text_core(h, ids, attn_mask, lengths_host, N, T, emb, emb_ld, emb_col, normalize, 0, ws, ws_bytes, stream);
+}
+extern "C" int ofx_clip_text_fwd_shared(ofx_handle* h, const int64_t* ids, const int64_t* attn_mask, const int* lengths_host,
+                                        int N, int T, float* emb, int emb_ld, int emb_col, int normalize, int shared_first, void* ws,
+                                        size_t ws_bytes, ofx_stream stream) {
+    return clip_text_core(h, ids, attn_mask, lengths_host, N, T, emb, emb_ld, emb_col, normalize, shared_first, ws, ws_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------- scoring
@@ -1239,6 +1264,7 @@ extern "C" int ofx_tune(int knob, int value) {
         case 10: g_set_fuse = value; return OFX_OK;
         case 17: g_topk_filter = value != 0; return OFX_OK;
         case 20: g_x3_vit_f32_attn = value != 0; return OFX_OK;
+        case 21: g_text_shared_first = value != 0; return OFX_OK;
         default: ofx_set_error("ofx_tune: unknown knob %d", knob); return OFX_EINVAL;
     }
 }

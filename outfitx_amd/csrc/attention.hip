@@ -109,6 +109,10 @@ struct SetK {
     // causal AND key-padding mask (key_mask [nseq, mask_ld] int64, 0 = ignored)
     int fixed_S, causal, mask_ld;
     const int64_t* key_mask;
+    // ... with a shared first row (SetAttnArgs::shared_first): position j of sequence b is row (j ? b * (fixed_S - 1) + j : 0); blocks
+    // b < nseq compute queries 1 .. fixed_S - 1 (keys and values j = 0 .. fixed_S - 1 in that order, as without sharing: same sums),
+    // blocks b == nseq compute query 0 of row 0 - one live key under the causal mask - as a sequence of one row
+    int shared_first;
     // fp32 q | k | v still in split-K slabs: element = sum_s qkv[s * plane + ...] + bias[col] (the GEMM's second pass, done here)
     int splits; size_t plane; const float* bias;
 };
@@ -129,10 +133,14 @@ __global__ __launch_bounds__(64) void set_attention_kernel(SetK a) {
     __shared__ __attribute__((aligned(16))) float sc[SMAX * (SMAX + 4)];
     const int lane = threadIdx.x;
     const int b = blockIdx.x / a.n_head, h = blockIdx.x % a.n_head;
-    const int r0 = a.cu ? a.cu[b] : b * a.fixed_S;
-    int S = a.cu ? a.cu[b + 1] - r0 : a.fixed_S;
+    const bool sh = a.shared_first != 0, sh_q0 = sh && b == a.nseq;      // sh_q0: the block of the shared row's own query
+    const int r0 = a.cu ? a.cu[b] : (sh ? (sh_q0 ? 0 : b * (a.fixed_S - 1)) : b * a.fixed_S);
+    int S = a.cu ? a.cu[b + 1] - r0 : (sh_q0 ? 1 : a.fixed_S);
     S = S < SMAX ? S : SMAX;
     const int nq = a.only_row0 ? 1 : S;
+    const int q0 = sh && !sh_q0 ? 1 : 0;              // first query this block computes
+    const int mb = sh_q0 ? 0 : b;                     // key-mask row (the shared row's key 0 is live in every sequence: sequence 0's entry)
+    auto row_of = [&](int j) { return sh && j == 0 ? 0 : r0 + j; };
     const int D = a.D;
     const bool two = WIDE && lane < HD - 64;        // this lane owns column 64 + lane as well
     float vreg[SMAX];
@@ -180,8 +188,8 @@ __global__ __launch_bounds__(64) void set_attention_kernel(SetK a) {
         // wants).  The kernel is bound by its vector-memory instruction count, not by bytes (S = 8: 12 loads + 3 stores per wave instead
         // of 24 + 24)
         auto f32_row = [&](int j, int c4) {
-            const float* rp = (const float*)a.qkv + (size_t)(r0 + j) * 3 * D + h * HD + c4;
-            if (j < nq) *(f32x4*)(qs + j * STR + c4) = *(const f32x4*)rp;
+            const float* rp = (const float*)a.qkv + (size_t)row_of(j) * 3 * D + h * HD + c4;
+            if (j >= q0 && j < nq) *(f32x4*)(qs + j * STR + c4) = *(const f32x4*)rp;
             *(f32x4*)(ks + j * STR + c4) = *(const f32x4*)(rp + D);
         };
         if constexpr (!WIDE) {
@@ -194,10 +202,10 @@ __global__ __launch_bounds__(64) void set_attention_kernel(SetK a) {
             for (int f = lane; f < S * C4; f += 64) f32_row(f / C4, (f % C4) * 4);
         }
 #pragma unroll
-        for (int j = 0; j < SMAX; ++j) vreg[j] = j < S ? ((const float*)a.qkv)[(size_t)(r0 + j) * 3 * D + 2 * D + h * HD + lane] : 0.f;
+        for (int j = 0; j < SMAX; ++j) vreg[j] = j < S ? ((const float*)a.qkv)[(size_t)row_of(j) * 3 * D + 2 * D + h * HD + lane] : 0.f;
         if constexpr (WIDE) {
 #pragma unroll
-            for (int j = 0; j < SMAX; ++j) vreg2[j] = (j < S && two) ? ((const float*)a.qkv)[(size_t)(r0 + j) * 3 * D + 2 * D + h * HD + 64 + lane] : 0.f;
+            for (int j = 0; j < SMAX; ++j) vreg2[j] = (j < S && two) ? ((const float*)a.qkv)[(size_t)row_of(j) * 3 * D + 2 * D + h * HD + 64 + lane] : 0.f;
         }
     } else {
 #pragma unroll
@@ -220,8 +228,8 @@ __global__ __launch_bounds__(64) void set_attention_kernel(SetK a) {
         }
     }
     __syncthreads();
-    for (int p = lane; p < nq * S; p += 64) {
-        const int i = p / S, j = p % S;
+    for (int p = lane; p < (nq - q0) * S; p += 64) {
+        const int i = q0 + p / S, j = p % S;
         const f32x4* qp = (const f32x4*)(qs + i * STR);
         const f32x4* kp = (const f32x4*)(ks + j * STR);
         float d = 0.f;
@@ -231,11 +239,11 @@ __global__ __launch_bounds__(64) void set_attention_kernel(SetK a) {
             d += x[0] * y[0] + x[1] * y[1] + x[2] * y[2] + x[3] * y[3];
         }
         bool dead = a.causal && j > i;
-        if (!dead && a.key_mask) dead = a.key_mask[(size_t)b * a.mask_ld + j] == 0;
+        if (!dead && a.key_mask) dead = a.key_mask[(size_t)mb * a.mask_ld + j] == 0;
         sc[i * (SMAX + 4) + j] = dead ? -INFINITY : d * a.scale;
     }
     __syncthreads();
-    if (lane < nq) {
+    if (lane >= q0 && lane < nq) {
         float* row = sc + lane * (SMAX + 4);
         float m = -INFINITY;
         for (int j = 0; j < S; ++j) m = fmaxf(m, row[j]);
@@ -248,17 +256,17 @@ __global__ __launch_bounds__(64) void set_attention_kernel(SetK a) {
     }
     __syncthreads();
     if (a.out_kind == 0) {
-        for (int i = 0; i < nq; ++i) {
+        for (int i = q0; i < nq; ++i) {
             const float* row = sc + i * (SMAX + 4);
             float acc = 0.f;
 #pragma unroll
             for (int j = 0; j < SMAX; ++j) acc += (j < S ? row[j] : 0.f) * vreg[j];
-            ((float*)a.out)[(size_t)(r0 + i) * a.ldo + h * HD + lane] = acc;
+            ((float*)a.out)[(size_t)row_of(i) * a.ldo + h * HD + lane] = acc;
             if constexpr (WIDE) {
                 float acc2 = 0.f;
 #pragma unroll
                 for (int j = 0; j < SMAX; ++j) acc2 += (j < S ? row[j] : 0.f) * vreg2[j];
-                if (two) ((float*)a.out)[(size_t)(r0 + i) * a.ldo + h * HD + 64 + lane] = acc2;
+                if (two) ((float*)a.out)[(size_t)row_of(i) * a.ldo + h * HD + 64 + lane] = acc2;
             }
         }
         return;
@@ -266,7 +274,7 @@ __global__ __launch_bounds__(64) void set_attention_kernel(SetK a) {
     // operand-type outputs: the fp32 rows go through the (now free) q staging rows and leave as 16-byte stores - 8 lanes per 64-column
     // slice, 8 rows per instruction, one instruction per copy (hi | lo | hi) instead of one 2-byte store per lane, row and copy
     // (96 columns: 12 chunks of 8 per row, walked flat)
-    for (int i = 0; i < nq; ++i) {
+    for (int i = q0; i < nq; ++i) {
         const float* row = sc + i * (SMAX + 4);
         float acc = 0.f;
 #pragma unroll
@@ -282,16 +290,16 @@ __global__ __launch_bounds__(64) void set_attention_kernel(SetK a) {
     __syncthreads();
     auto store_row = [&](int i, int c8) {
         const f32x4 x0 = *(const f32x4*)(qs + i * STR + c8), x1 = *(const f32x4*)(qs + i * STR + c8 + 4);
-        store8<T>(a.out, (size_t)(r0 + i) * a.ldo + h * HD + c8, x0, x1, a.out_kind, D);
+        store8<T>(a.out, (size_t)row_of(i) * a.ldo + h * HD + c8, x0, x1, a.out_kind, D);
     };
     if constexpr (!WIDE) {
         const int c8 = (lane & 7) * 8, r8 = lane >> 3;
         for (int i0 = 0; i0 < nq; i0 += 8) {
             const int i = i0 + r8;
-            if (i < nq) store_row(i, c8);
+            if (i >= q0 && i < nq) store_row(i, c8);
         }
     } else {
-        for (int f = lane; f < nq * C8; f += 64) store_row(f / C8, (f % C8) * 8);
+        for (int f = lane + q0 * C8; f < nq * C8; f += 64) store_row(f / C8, (f % C8) * 8);
     }
 }
 
@@ -553,9 +561,12 @@ int ofx_launch_set_attention(const SetAttnArgs& g, int op_dtype, hipStream_t s) 
     k.qkv = g.qkv; k.out = (char*)g.out; k.cu = g.cu_seqlens; k.nseq = g.nseq; k.n_head = g.n_head; k.D = g.D; k.ldo = g.ldo;
     k.out_kind = g.out_kind; k.only_row0 = g.only_row0; k.scale = g.scale; k.drop = g.drop;
     k.fixed_S = g.fixed_len; k.causal = g.causal; k.mask_ld = g.mask_ld; k.key_mask = g.key_mask;
+    OFX_REQUIRE(!g.shared_first || (!g.cu_seqlens && g.causal && g.fixed_len >= 2 && !g.only_row0 && !g.qkv_op && g.splits <= 1 && !g.drop.thresh), OFX_EINVAL,
+                "set_attention: a shared first row needs the fixed-length causal mode on fp32 q|k|v, >= 2 rows per sequence, all queries, no slabs, no dropout");
+    k.shared_first = g.shared_first ? 1 : 0;
     OFX_REQUIRE(g.splits <= 1 || (!g.qkv_op && g.bias && g.plane > 0 && g.max_len <= 32), OFX_EINVAL, "set_attention: slab input needs fp32 q|k|v, the bias, the slab stride and sets of <= 32 rows");
     k.splits = g.splits > 1 ? g.splits : 1; k.plane = g.plane; k.bias = g.bias;
-    const int grid = g.nseq * g.n_head;
+    const int grid = (g.nseq + (g.shared_first ? 1 : 0)) * g.n_head;
     ProfScope prof(PROF_ATTN, s);
 #define SA(T, N) do { if (wide) { if (g.qkv_op) hipLaunchKernelGGL((set_attention_kernel<T, N, T, 96>), dim3(grid), dim3(64), 0, s, k); \
                                       else hipLaunchKernelGGL((set_attention_kernel<T, N, float, 96>), dim3(grid), dim3(64), 0, s, k); } \

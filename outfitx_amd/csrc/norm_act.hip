@@ -250,13 +250,22 @@ __global__ __launch_bounds__(256) void vit_embed_ln_kernel(const float* patch_ou
     }
 }
 
-// CLIP text embedding: x[i*Tc + t] = tok_emb[ids[i*T + t]] + pos_emb[t], t < Tc   (fp32, D = 512)
+// The text tower's row of (text i, position t).  Full rows: i * Tc + t.  Shared first row (every text starts with the same token and sees
+// position 0, which under the causal mask attends to itself only - one row carries all N of them): row 0 is position 0 of every text,
+// position t >= 1 of text i is row 1 + i * (Tc - 1) + (t - 1); rows = 1 + N * (Tc - 1).
+__device__ __forceinline__ int text_row(int i, int t, int Tc, int shared_first) {
+    if (!shared_first) return i * Tc + t;
+    return t == 0 ? 0 : 1 + i * (Tc - 1) + (t - 1);
+}
+
+// CLIP text embedding: x[text_row(i, t)] = tok_emb[ids[i*T + t]] + pos_emb[t], t < Tc   (fp32, D = 512)
 __global__ __launch_bounds__(256) void text_embed_kernel(const int64_t* ids, const float* tok, const float* pos, float* x,
-                                                        int N, int T, int Tc, int D, int vocab) {
+                                                        int N, int T, int Tc, int D, int vocab, int shared_first) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int rows = N * Tc;
+    const int rows = shared_first ? 1 + N * (Tc - 1) : N * Tc;
     for (int r = blockIdx.x * 4 + w; r < rows; r += gridDim.x * 4) {
-        const int i = r / Tc, t = r % Tc;
+        int i = r / Tc, t = r % Tc;
+        if (shared_first) { i = r ? (r - 1) / (Tc - 1) : 0; t = r ? 1 + (r - 1) % (Tc - 1) : 0; }
         long long id = ids[(size_t)i * T + t];
         id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
         const f32x4* tp = (const f32x4*)(tok + (size_t)id * D);
@@ -265,9 +274,9 @@ __global__ __launch_bounds__(256) void text_embed_kernel(const int64_t* ids, con
     }
 }
 
-// pooled row index per text: i*Tc + min(eos_pos, Tc-1); eos_pos = argmax(ids) (legacy eos_id==2)
+// pooled row index per text: text_row(i, min(eos_pos, Tc-1)); eos_pos = argmax(ids) (legacy eos_id==2)
 // or first position == eos_id (0 if none) — HF CLIPTextModel pooling rule.
-__global__ void text_eos_index_kernel(const int64_t* ids, int* row_idx, int N, int T, int Tc, int eos_id) {
+__global__ void text_eos_index_kernel(const int64_t* ids, int* row_idx, int N, int T, int Tc, int eos_id, int shared_first) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
     const int64_t* p = ids + (size_t)i * T;
@@ -278,7 +287,7 @@ __global__ void text_eos_index_kernel(const int64_t* ids, int* row_idx, int N, i
     } else {
         for (int t = 0; t < T; ++t) if (p[t] == eos_id) { pos = t; break; }
     }
-    row_idx[i] = i * Tc + (pos < Tc ? pos : Tc - 1);
+    row_idx[i] = text_row(i, pos < Tc ? pos : Tc - 1, Tc, shared_first);
 }
 
 __global__ void iota_rows_kernel(int* idx, int n, int stride) {
@@ -532,13 +541,16 @@ int ofx_launch_vit_embed_ln(const float* patch_out, const float* cls, const floa
     return OFX_OK;
 }
 int ofx_launch_text_embed(const int64_t* ids, const float* tok, const float* pos, float* x, int N, int T, int Tc, int D,
-                          int vocab, hipStream_t s) {
-    hipLaunchKernelGGL(text_embed_kernel, dim3(rows_grid(N * Tc)), dim3(256), 0, s, ids, tok, pos, x, N, T, Tc, D, vocab);
+                          int vocab, int shared_first, hipStream_t s) {
+    OFX_REQUIRE(!shared_first || Tc >= 2, OFX_ESHAPE, "text_embed: a shared first row needs Tc >= 2 (Tc=%d)", Tc);
+    hipLaunchKernelGGL(text_embed_kernel, dim3(rows_grid(shared_first ? 1 + N * (Tc - 1) : N * Tc)), dim3(256), 0, s, ids, tok, pos, x, N, T, Tc, D, vocab,
+                       shared_first);
     OFX_LAUNCH_CHECK();
     return OFX_OK;
 }
-int ofx_launch_text_eos_index(const int64_t* ids, int* row_idx, int N, int T, int Tc, int eos_id, hipStream_t s) {
-    hipLaunchKernelGGL(text_eos_index_kernel, dim3((N + 255) / 256), dim3(256), 0, s, ids, row_idx, N, T, Tc, eos_id);
+int ofx_launch_text_eos_index(const int64_t* ids, int* row_idx, int N, int T, int Tc, int eos_id, int shared_first, hipStream_t s) {
+    OFX_REQUIRE(!shared_first || Tc >= 2, OFX_ESHAPE, "text_eos_index: a shared first row needs Tc >= 2 (Tc=%d)", Tc);
+    hipLaunchKernelGGL(text_eos_index_kernel, dim3((N + 255) / 256), dim3(256), 0, s, ids, row_idx, N, T, Tc, eos_id, shared_first);
     OFX_LAUNCH_CHECK();
     return OFX_OK;
 }

@@ -357,8 +357,8 @@ int ofx_launch_patchify(const float* px, void* out, int N, int img, int patch, i
 int ofx_launch_vit_embed_ln(const float* patch_out, const float* cls, const float* pos, const float* g, const float* b,
                             float* x, int N, int S, int D, float eps, hipStream_t s, void* xb, float* stat, int op_dtype, void* xlo);
 int ofx_launch_text_embed(const int64_t* ids, const float* tok, const float* pos, float* x, int N, int T, int Tc, int D,
-                          int vocab, hipStream_t s);
-int ofx_launch_text_eos_index(const int64_t* ids, int* row_idx, int N, int T, int Tc, int eos_id, hipStream_t s);
+                          int vocab, int shared_first, hipStream_t s);
+int ofx_launch_text_eos_index(const int64_t* ids, int* row_idx, int N, int T, int Tc, int eos_id, int shared_first, hipStream_t s);
 int ofx_launch_iota_rows(int* idx, int n, int stride, hipStream_t s);
 int ofx_launch_l2norm_store(const float* src, float* dst, int rows, int D, int ld, int col, int normalize, hipStream_t s);
 int ofx_launch_set_build(const float* x, const uint8_t* mask, const float* prefix, int prefix_stride, int* cu, float* X,
@@ -412,6 +412,10 @@ struct SetAttnArgs {
     // fixed-length mode (cu_seqlens == nullptr): every sequence has fixed_len <= 32 rows; optional causal AND key-padding mask
     int fixed_len = 0, causal = 0, mask_ld = 0;
     const int64_t* key_mask = nullptr;
+    // fixed-length causal mode with a shared first row (the text tower's row map, norm_act.hip text_row): row 0 is position 0 of every
+    // sequence, sequence b's positions 1 .. fixed_len - 1 are rows 1 + b * (fixed_len - 1) ...; nseq * n_head blocks compute the queries
+    // 1 .. fixed_len - 1 of their sequence against key / value 0 from row 0 and their own rows, n_head more blocks compute query 0
+    int shared_first = 0;
     // fp32 qkv still in split-K slabs (GemmArgs::defer_splits): qkv = slab 0, element = sum_s qkv[s * plane + ...] + bias[col]
     int splits = 1; size_t plane = 0; const float* bias = nullptr;
 };

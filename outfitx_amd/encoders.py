@@ -24,7 +24,7 @@ from torch import nn
 
 from . import _lib as L
 from .configs import ItemEncoderConfig
-from .engine import Engine
+from .engine import Engine, TextLengths, shared_first_row
 
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
@@ -398,13 +398,15 @@ class CLIPTextEncoder(_TowerBase):
         ids, att = self._tokenize(flatten_seq_to_one_dim(texts), tokenizer_kargs)
         return ids, att, len(texts)
 
-    def _lengths(self, ids: torch.Tensor):
-        """EOS position + 1 per text when the ids live on the host (no device sync otherwise)."""
+    def _lengths(self, ids: torch.Tensor, att=False):
+        """EOS position + 1 per text when the ids live on the host (no device sync otherwise).  With `att` (the batch's attention mask, or
+        None when it has none) the shared-first-row predicate of (ids, att) rides along (engine.TextLengths); without it the lengths
+        carry shared_first = False, the full rows."""
         if ids.device.type != "cpu":
             return None
         eos = self.model.config.eos_token_id
         pos = ids.argmax(-1) if eos == 2 else (ids == eos).int().argmax(-1)
-        return (pos + 1).tolist()
+        return TextLengths((pos + 1).tolist(), att is not False and shared_first_row(ids, att))
 
     def _dedup(self, ids: torch.Tensor, att: Optional[torch.Tensor]):
         """dedup_texts (the item texts are 132 category strings): host-side unique over the token rows ->
@@ -463,14 +465,14 @@ class CLIPTextEncoder(_TowerBase):
                 sel = torch.as_tensor(miss, dtype=torch.long)
                 m_ids = ids.index_select(0, sel).contiguous()
                 m_att = None if att is None else att.index_select(0, sel).contiguous()
-                plan["lengths"] = self._lengths(m_ids)
+                plan["lengths"] = self._lengths(m_ids, m_att)
                 plan["ids"], plan["att"] = self._engine("text").stage_tokens(m_ids, m_att)
             return None, None, None, b, plan
         dd = self._dedup(ids, att)
         if dd is not None:
             ids, att, inverse = dd
             inverse = inverse.to(self.device, non_blocking=True)
-        lengths = self._lengths(ids)
+        lengths = self._lengths(ids, att)
         ids_d, att_d = self._engine("text").stage_tokens(ids, att)
         return ids_d, att_d, lengths, b, inverse
 

@@ -27,6 +27,29 @@ def _f32c(t: torch.Tensor, device) -> torch.Tensor:
     return t
 
 
+def shared_first_row(ids: torch.Tensor, att: Optional[torch.Tensor]) -> bool:
+    """Whether the text tower may compute position 0 once for all texts of ids [N, T] (ofx_clip_text_fwd_shared's precondition): the ids are
+    on the host (the test costs no device sync), every text starts with the same token (CLIP's BOS) and no text masks position 0.  The
+    tower is causal, so position 0 then is the same row for every text in every layer.  Tc >= 2 and the three-product scheme, the other
+    two conditions of the mode, are Engine.text's to check."""
+    if ids.device.type != "cpu" or ids.dim() != 2 or ids.shape[0] < 1 or ids.shape[1] < 2:
+        return False
+    if not bool((ids[:, 0] == ids[0, 0]).all()):
+        return False
+    if att is not None and (att.device.type != "cpu" or att.shape != ids.shape or not bool((att[:, 0] != 0).all())):
+        return False
+    return True
+
+
+class TextLengths(list):
+    """Tokens to compute per text (EOS position + 1) as CLIPTextEncoder computes them from host ids, with shared_first_row of those ids:
+    the ids travel to the device before Engine.text sees them, the host-side facts about them travel here."""
+
+    def __init__(self, lengths, shared_first: bool = False):
+        super().__init__(lengths)
+        self.shared_first = bool(shared_first)
+
+
 class SetInput(NamedTuple):
     """A staged set input (Engine.stage_set).  `args` are the seven set-input arguments in ofx_cir_train_fwd's order - x, pad_mask,
     table, ld, n_table, item_index, cu_items -: the dense form fills the first two, the indexed form the other five."""
@@ -358,16 +381,20 @@ class Engine:
 
     def text(self, ids: torch.Tensor, att: Optional[torch.Tensor], out: torch.Tensor, col: int, normalize: bool,
              lengths: Optional[Sequence[int]] = None) -> None:
-        """ids/att [N,T] int64 -> out[:, col:col+512].  lengths: host ints (EOS position + 1) or None."""
+        """ids/att [N,T] int64 -> out[:, col:col+512].  lengths: host ints (EOS position + 1) or None; a TextLengths carries the
+        shared-first-row predicate of the host ids it was computed from (the ids themselves may already be on the device), host ids
+        passed here are examined directly, anything else computes the full rows."""
+        shared = lengths.shared_first if isinstance(lengths, TextLengths) else shared_first_row(ids, att)
         ids_d, att_d = self.stage_tokens(ids, att)
         N, T = ids_d.shape
         Tc = T if lengths is None else max(1, min(T, max(int(v) for v in lengths)))
         arr = None if lengths is None else (C.c_int * N)(*[int(v) for v in lengths])
         nb = self.ws_bytes(L.OP_TEXT, N, Tc)
         ws = self.workspace(nb)
+        shared = bool(shared) and Tc >= 2 and bool(self.desc.txt_x3)      # (the library checks the last two again, and its ofx_tune(21) knob)
         with torch.cuda.device(self.device):
-            L.check(self.lib.ofx_clip_text_fwd(self.h, _ptr(ids_d), _ptr(att_d), arr, N, T, _ptr(out), out.stride(0), col,
-                                               int(normalize), _ptr(ws), ws.numel(), _stream(self.device)), "ofx_clip_text_fwd")
+            L.check(self.lib.ofx_clip_text_fwd_shared(self.h, _ptr(ids_d), _ptr(att_d), arr, N, T, _ptr(out), out.stride(0), col,
+                                                      int(normalize), int(shared), _ptr(ws), ws.numel(), _stream(self.device)), "ofx_clip_text_fwd_shared")
         self._keep_ids = (ids_d, att_d)
 
     # ---------------------------------------------------------------- scoring

@@ -11,7 +11,8 @@ Constraints, all the usual ones of a captured graph:
   * shapes, dtypes and the ADDRESSES of every input are frozen: feed a new batch by copying it into the captured tensors (`CapturedCall.inputs`);
     pinned host tensors that the call copies to the device (token ids / masks) are re-read at every replay, so overwrite them in place;
   * host-side decisions are frozen too: for texts that is the longest token row of the captured batch (the tower computes that many positions):
-    a replayed batch must not hold a longer one;
+    a replayed batch must not hold a longer one; and whether position 0 is computed once for all texts (they share their first token, unmasked):
+    a replayed batch must still do so (CapturedCall.check raises otherwise);
   * the returned tensors are owned by the graph and overwritten by the next replay: clone what must survive;
   * inference only (no autograd), parameters must not be re-packed (an optimizer step invalidates the capture).
 """
@@ -20,6 +21,8 @@ from __future__ import annotations
 from typing import Any, Callable, Optional
 
 import torch
+
+from .engine import TextLengths, shared_first_row
 
 
 class CapturedCall:
@@ -85,11 +88,17 @@ def capture_cp_forward(model, outfit_mask: torch.Tensor, images: torch.Tensor, t
     if ids.device.type == "cpu":                   # host ids: the tower computes max(EOS position) + 1 token positions, decided on the host at capture time
         flat = ids.reshape(-1, ids.shape[-1])
         cc.captured_tokens = max(1, min(flat.shape[1], max(enc._lengths(flat))))
+        att = texts.get("attention_mask")
+        flat_att = None if att is None else att.reshape(-1, att.shape[-1])
+        # ... and whether it computes position 0 once for all texts (same first token everywhere, no mask on it: engine.shared_first_row)
+        cc.captured_shared_first = shared_first_row(flat, flat_att)
 
         def check():
             now = max(enc._lengths(flat))          # the pinned tensor is re-read at every replay: what it holds NOW must fit what was captured
             if now > cc.captured_tokens:
                 raise ValueError(f"replay: a token row of {now} positions, but the graph was captured for {cc.captured_tokens}: capture again (a longer row would be silently truncated)")
+            if cc.captured_shared_first and not shared_first_row(flat, flat_att):
+                raise ValueError("replay: the graph was captured for texts that share their first position (one first token, unmasked), and the token tensors no longer do: capture again")
         cc.check = check
     return cc
 
@@ -101,7 +110,8 @@ class ForwardReplay:
 
     key = address / shape / dtype of the image tensor (the graph reads the caller's own tensor: no 1.2 GB copy per call; a caller that
     passes another tensor at another address starts another entry), shapes of the token tensors and the outfit mask, the number of token
-    positions the text tower computes (host ids: longest row; device ids: all T), the operand schemes, stream options, the library's
+    positions the text tower computes (host ids: longest row; device ids: all T), whether it computes position 0 once (host ids that share
+    their first token, unmasked), the operand schemes, stream options, the library's
     ofx_tune generation.  Token ids / attention mask / outfit mask are COPIED into entry-owned device tensors on the caller's stream
     before each replay (1 MB; pinned or device sources asynchronously, pageable ones synchronously - exactly how the launch-by-launch
     call stages them), so the graph itself never reads caller-owned host memory.  An entry dies when any parameter changes (data_ptr / version
@@ -153,7 +163,10 @@ class ForwardReplay:
         tokens = T
         if ids.device.type == "cpu":
             tokens = max(1, min(T, max(enc.text_enc._lengths(ids.reshape(-1, T)))))
-        key = (images.data_ptr(), tuple(images.shape), images.dtype, tuple(ids.shape), att is not None, tokens, tuple(outfit_mask.shape),
+        # host ids: does the text tower compute position 0 once for all texts?  Re-read from the caller's tensors at every call, like the
+        # longest row: a batch that stops qualifying gets another key, never the shared-row graph
+        shared = shared_first_row(ids.reshape(-1, T), None if att is None else att.reshape(-1, T))
+        key = (images.data_ptr(), tuple(images.shape), images.dtype, tuple(ids.shape), att is not None, tokens, shared, tuple(outfit_mask.shape),
                model.precision, model.tower_fed_precision, enc.image_enc.tower_precision, enc.text_enc.tower_precision, enc.overlap_towers, enc.side_stream_priority,
                enc.image_enc.vit_streams, lib.ofx_config_generation(), torch.cuda.current_stream(images.device).cuda_stream)
         sig = tuple((p.data_ptr(), p._version) for p in model.parameters())
@@ -174,7 +187,7 @@ class ForwardReplay:
                 return eager()
             out = eager()                                  # this call's result; the capture below serves the following ones
             self.stats["eager"] += 1
-            e = self._capture(model, outfit_mask, images, ids, att, tokens, sig)
+            e = self._capture(model, outfit_mask, images, ids, att, tokens, shared, sig)
             if e is None:
                 if len(self.failed) < 256:
                     self.failed.add(key)
@@ -192,7 +205,7 @@ class ForwardReplay:
         self.stats["replays"] += 1
         return e["out"].clone()
 
-    def _capture(self, model, outfit_mask, images, ids, att, tokens, sig):
+    def _capture(self, model, outfit_mask, images, ids, att, tokens, shared, sig):
         dev = images.device
         n_rows, T = ids.numel() // ids.shape[-1], ids.shape[-1]
         ids_d = torch.empty(n_rows, T, dtype=torch.int64, device=dev); ids_d.copy_(ids.reshape(n_rows, T))
@@ -200,7 +213,8 @@ class ForwardReplay:
         if att is not None:
             att_d = torch.empty(n_rows, T, dtype=torch.int64, device=dev); att_d.copy_(att.reshape(n_rows, T))
         mask_d = outfit_mask.to(dev).clone()
-        lengths = None if ids.device.type != "cpu" else [tokens] * n_rows     # only their maximum (positions computed) is a host-side decision
+        # only their maximum (positions computed) and the shared first position are host-side decisions
+        lengths = None if ids.device.type != "cpu" else TextLengths([tokens] * n_rows, shared)
         prepared = (ids_d, att_d, lengths, ids.shape[0], None)
 
         def fn():
