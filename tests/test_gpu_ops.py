@@ -439,7 +439,8 @@ def test_gemm_split_k_is_deterministic_and_exact(M, N, K, kind):
                                               (256, 768, 1, None, True), (768, 256, 4352, 2305, True), (256, 256, 640, 0, True)])
 def test_gemm_tn_weight_gradient_kernel(dt, M, N, K, kdev, split):
     """C = A^T B with the contraction over ROWS (transposed LDS reads): asymmetric operands, K not a multiple of 64,
-    device-side live row count (rows past it are garbage / NaN and must not contribute), with and without split-K."""
+    device-side live row count (rows past it are garbage / NaN and must not contribute), with and without split-K.
+    Bit-exact coverage of every path of the kernel: tests/test_gpu_gemm_tn_exact.py."""
     lib = L.load()
     g = np.random.default_rng(M + N + K)
     Kp = (K + 63) // 64 * 64
