@@ -55,7 +55,7 @@ typedef struct ofx_model_desc {
     int d_model, n_head, d_ffn, n_layers, max_items; /* 1024, 16, 2024, 6, 16 */
     int outfit_act;                                   /* OFX_ACT_MISH */
     int outfit_precision;                             /* ofx_precision */
-    /* CLIP ViT-B/32 vision tower — HF CLIPVisionConfig as loaded by clip_image_encoder.py:20-22 */
+    /* CLIP vision tower (ViT-B/32 by default; any patch / image with (image/patch)^2 + 1 <= 256 tokens, e.g. B/16 at 224) — HF CLIPVisionConfig as loaded by clip_image_encoder.py:20-22 */
     int vit_width, vit_layers, vit_heads, vit_mlp, vit_patch, vit_image, vit_act; /* 768,12,12,3072,32,224 */
     /* CLIP text tower — HF CLIPTextConfig as loaded by clip_text_encoder.py:19-21 */
     int txt_width, txt_layers, txt_heads, txt_mlp, txt_vocab, txt_max_pos, txt_act, txt_eos_id; /* 512,12,8,2048,49408,77 */
@@ -133,8 +133,9 @@ int ofx_cir_head(ofx_handle* h, const float* row0, int B, float* emb, void* ws, 
 int ofx_cir_prefix(ofx_handle* h, const float* target_text_emb, int B, float* prefix_out, ofx_stream stream);
 
 /* Row F: HF CLIPVisionModelWithProjection(pixel_values).image_embeds (clip_image_encoder.py:74-76)
- * + optional F.normalize (base_image_encoder.py:46-47).  pixels [N,3,224,224] fp32 (already
- * resized/normalised by the host processor); emb [N, emb_ld] fp32, written at column emb_col.   */
+ * + optional F.normalize (base_image_encoder.py:46-47).  pixels [N,3,vit_image,vit_image] fp32 (already
+ * resized/normalised by the host processor; the descriptor's vit_patch / vit_image set the grid: B/32 at 224 is 50 tokens, B/16 at
+ * 224 is 197, at most 256 tokens - the entry point keeps its name); emb [N, emb_ld] fp32, written at column emb_col.   */
 int ofx_vit_b32_fwd(ofx_handle* h, const float* pixels, int N, float* emb, int emb_ld, int emb_col,
                     int normalize, void* ws, size_t ws_bytes, ofx_stream stream);
 /* Row G: HF CLIPTextModelWithProjection(input_ids, attention_mask).text_embeds
@@ -575,7 +576,8 @@ int ofx_vit_embed_ln(const float* patch_out, const float* cls, const float* pos,
 int ofx_gather_hilo(const void* hi, const void* lo, const int* idx, float* dst, int rows, int W, int op_dtype, ofx_stream stream);
 int ofx_layernorm(const float* x, const int* row_idx, const float* gamma, const float* beta, void* y, int rows,
                   int D, int ldy, int out_kind, int op_dtype, float eps, ofx_stream stream);
-/* MFMA attention over fixed-length sequences of 1 .. 64 rows (the CLIP towers): qkv [nseq * seq_len, ld] operand type, q at column 0, k at
+/* MFMA attention over fixed-length sequences of 1 .. 256 rows (the CLIP towers; up to 64 rows one wavefront holds the whole sequence, 65 ..
+ * 256 rows - ViT-B/16: 197 - take a workgroup per (sequence, head) with the same roundings; seq_len > 256: OFX_ESHAPE): qkv [nseq * seq_len, ld] operand type, q at column 0, k at
  * k_off, v at v_off, head h at + 64 h; out [nseq * seq_len, ldo] operand type = softmax(q k^T * scale + mask) v, columns n_head * 64 .. ldo - 1
  * not written.  key_mask: optional int64 [nseq, mask_ld], 0 = key ignored; causal: key j > query i ignored.  ld, k_off, v_off multiples of 8,
  * ldo of 4 (OFX_ESHAPE); qkv 16-byte and out 8-byte aligned (OFX_EINVAL).

@@ -34,6 +34,9 @@ class ItemEncoderConfig:
         attr, name, width = _ENCODERS[self.type]
         setattr(self, attr, name)
         self.dim_per_modality: int = width
+        # type 'clip' only, set after construction like clip_model_name: `cfg.clip_vision_config = {"patch_size": 16}` - a dict of HF
+        # CLIPVisionConfig fields that fixes the image tower's architecture (ViT-B/16: 197 tokens) without a checkpoint on disk; when it
+        # is absent the architecture is read from the checkpoint clip_model_name names (encoders.CLIPImageEncoder).
 
 
 @dataclass

@@ -644,8 +644,8 @@ static int clip_layer_x3(const ClipLayer& L, const ClipWs& w, int rows, int nseq
     use_gemm(g1, L.qkv, W);
     // q | k | v stay fp32 and the attention runs in fp32 arithmetic (the outfit transformer's set kernel with HF's causal AND
     // key-padding mask, up to 64 rows per sequence): rounding q, k, v, P to the operand type alone leaves 3.5e-4 at the text embedding
-    // (tests/studies/operand_scheme_cpu.py); the single-tile MFMA kernel stays as the fallback beyond 64 rows (never reached:
-    // ofx_clip_text_fwd caps the computed tokens at 64)
+    // (tests/studies/operand_scheme_cpu.py); the MFMA attention stays as the fallback beyond 64 rows (never reached by the text tower:
+    // ofx_clip_text_fwd caps the computed tokens at 64; a three-product ViT-B/16, 197 rows, asks for it by mfma_attn anyway)
     // (the ViT in its three-product mode keeps the MFMA attention: 2,048 images x 12 heads of 50 tokens in fp32 VALU arithmetic would
     // cost more than the layer's GEMMs, and the attention core's operand rounding is the smallest term of its budget, 6e-5)
     const bool f32_attn = S <= 64 && !mfma_attn;

@@ -4,6 +4,7 @@
 //     CLIP ViT-B/32 (S = 50, 12 heads) and CLIP text (S <= 64, causal ∧ key-padding, 8 heads);
 //     replaces HF CLIPAttention's softmax(QK^T/8 + mask)V (reached from clip_image_encoder.py:74-76,
 //     clip_text_encoder.py:56-58).  The wavefront's algorithm and lane maps: attn_wave.h.
+//     (1b) attention_mfma_long: 65 <= S <= 256 (CLIP ViT-B/16: S = 197), a workgroup per (sequence, head), the same wave core and roundings.
 // (2) set_attention: fp32 VALU attention over an outfit's 1 + n items (S <= 32, 16 heads);
 //     replaces nn.MultiheadAttention's SDPA inside nn.TransformerEncoderLayer
 //     (src/models/outfit_x.py:137-140,165-168) with -inf on padded keys realised by pad-free
@@ -95,6 +96,90 @@ __global__ __launch_bounds__(256, 3) void attention_mfma_kernel(AttnK a) {      
     v8 pf[NT][KS];
     attn_softmax_p<T, NT, true>(pf, st, a.scale, nu, a.drop, pair);      // varlen training: dropout on P, row = pair
     attn_pv_store<T, NT>(vl, pf, nu, live, (T*)a.out, row_first, a.ldo, head * 64, a.only_row0 ? 1 : S, a.split3_w);      // dead waves store nothing
+}
+
+// (1b) attention_mfma_long: 65 <= S <= 256 rows (ViT-B/16: 197), fixed-length mode.  One workgroup of 4 waves per (sequence, head).  K and
+// V of the whole sequence are staged once as two LDS row images (ATTN_V_ROW bytes per row, rows >= S zero); wave w then takes the
+// 16-query tiles u = w, w + 4, ...: Q fragments from global, the K fragment of key tile t as one 16-byte read of image row 16t + r16
+// (at the 160-byte pitch the four 16-lane groups of ds_read_b128 each land on 16 distinct 4-bank slots: conflict-free), V through
+// attn_tr_frag.  NT key tiles x 1 query tile of attn_wave.h: the whole score row of a query tile is NT f32x4 in registers, so max
+// and sum run over the whole key row and the roundings are those of attention_mfma_kernel - no online-softmax rescaling.
+// The additive key mask (16 NT floats, the same for every query tile) lives in the row images' pad: the four floats of keys
+// 4g .. 4g + 3 at byte 128 of K row g, one 16-byte broadcast read per key tile - no LDS beyond the two images, so the NT = 16
+// instance (2 x 256 x 160 B = 80 KB) still fits twice into a CU's 160 KiB.
+template <typename T, int NT>   // NT >= ceil(S / 16) in {8, 13, 16}: key tiles; key tiles beyond S are all-zero rows under a -inf mask
+__global__ __launch_bounds__(256, 2) void attention_mfma_long_kernel(AttnK a) {
+    typedef typename OpT<T>::v8 v8;
+    constexpr int KS = attn_ksteps(NT), ROWS = 32 * KS, IMG = ROWS * ATTN_V_ROW;
+    static_assert(4 * NT <= ROWS && ATTN_V_ROW >= 128 + 16, "the key mask sits in the pad of the first 4 NT K rows");
+    __shared__ __attribute__((aligned(16))) char smem[2 * IMG];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int seq = blockIdx.x / a.n_head, head = blockIdx.x % a.n_head;
+    const int S = a.S, row_first = seq * S;
+    const T* base = (const T*)a.qkv + (size_t)row_first * a.ld + head * 64;
+    const int r16 = lane & 15, q4 = lane >> 4;
+    OFX_LDS char* kl = (OFX_LDS char*)smem;
+    OFX_LDS char* vl = kl + IMG;
+
+    // ---- K, V -> LDS, zero rows beyond S (0 * garbage must stay 0; a zero K row scores 0 + -inf)
+#pragma unroll
+    for (int it = 0; it < ROWS / 32; ++it) {
+        const int key = it * 32 + (tid >> 3);
+        v8 kv, vv;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) kv[e] = vv[e] = (T)0.0f;
+        if (key < S) {
+            const T* rp = base + (size_t)key * a.ld + (tid & 7) * 8;
+            kv = *(const v8*)(rp + a.k_off);
+            vv = *(const v8*)(rp + a.v_off);
+        }
+        *(OFX_LDS v8*)(kl + key * ATTN_V_ROW + (tid & 7) * 16) = kv;
+        *(OFX_LDS v8*)(vl + key * ATTN_V_ROW + (tid & 7) * 16) = vv;
+    }
+    // ---- additive key mask, 0 or -inf, independent of the query: key = tid -> pad of K row key / 4
+    if (tid < 16 * NT) {
+        bool dead = tid >= S;
+        if (!dead && a.key_mask) dead = a.key_mask[(size_t)seq * a.mask_ld + tid] == 0;
+        *(OFX_LDS float*)(kl + (tid >> 2) * ATTN_V_ROW + 128 + (tid & 3) * 4) = dead ? -INFINITY : 0.f;
+    }
+    __syncthreads();
+
+    // only_row0: query row 0 alone is wanted -> query tile 0, wave 0
+    const int nqt = a.only_row0 ? 1 : (S + 15) / 16;
+    for (int u = wave; u < nqt; u += 4) {          // wave-uniform: EXEC stays all ones for the transposed reads
+        v8 qf[1][2];
+        {
+            int row = 16 * u + r16;
+            row = row < S ? row : S - 1;
+            const T* rp = base + (size_t)row * a.ld + q4 * 8;
+            qf[0][0] = *(const v8*)rp;
+            qf[0][1] = *(const v8*)(rp + 32);
+        }
+        f32x4 st[NT][1];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            v8 kf[1][2];
+            OFX_LDS char* kr = kl + (16 * t + r16) * ATTN_V_ROW + q4 * 16;
+            kf[0][0] = *(OFX_LDS v8*)kr;
+            kf[0][1] = *(OFX_LDS v8*)(kr + 64);
+            const f32x4 ng = *(OFX_LDS f32x4*)(kl + (4 * t + q4) * ATTN_V_ROW + 128);
+            const float neg[1][4] = {{ng[0], ng[1], ng[2], ng[3]}};
+            f32x4 s1[1][1];
+            attn_scores<T, 1, 1>(s1, kf, qf, neg, 1);
+            st[t][0] = s1[0][0];
+            if (t % 4 == 3) __builtin_amdgcn_sched_barrier(0);      // at most 4 key tiles' fragment reads in flight: without it NT = 16 spills
+        }
+        if (a.causal) {                  // wave-uniform
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (16 * t + 4 * q4 + r > 16 * u + r16) st[t][0][r] = -INFINITY;
+        }
+        v8 pf[1][KS];
+        attn_softmax_p<T, NT, false, 1>(pf, st, a.scale, 1);
+        attn_pv_store<T, NT, 1>(vl, pf, 1, true, (T*)a.out, row_first + 16 * u, a.ldo, head * 64, a.only_row0 ? 1 : min(S - 16 * u, 16), a.split3_w);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -529,7 +614,8 @@ __global__ __launch_bounds__(256) void set_attention_bwd_mfma_kernel(AttnBwdK a)
 }  // namespace
 
 int ofx_launch_attention_mfma(const AttnArgs& g, int op_dtype, hipStream_t s) {
-    OFX_REQUIRE(g.seq_len >= 1 && g.seq_len <= 64, OFX_ESHAPE, "attention: seq_len=%d must be in [1,64]", g.seq_len);
+    OFX_REQUIRE(g.seq_len >= 1 && g.seq_len <= 256, OFX_ESHAPE, "attention: seq_len=%d must be in [1,256]", g.seq_len);
+    OFX_REQUIRE(g.seq_len <= 64 || !g.cu_seqlens, OFX_ESHAPE, "attention: varlen sequences of up to %d rows exceed 64 (only the fixed-length mode goes to 256)", g.seq_len);
     OFX_REQUIRE(g.nseq > 0 && g.n_head > 0, OFX_ESHAPE, "attention: nseq=%d n_head=%d", g.nseq, g.n_head);
     OFX_REQUIRE(g.seq_len <= 32 || !g.drop.thresh, OFX_ESHAPE, "attention: dropout columns are keyed query * 32 + key");
     OFX_REQUIRE(g.ld % 8 == 0 && g.ldo % 4 == 0 && g.k_off % 8 == 0 && g.v_off % 8 == 0, OFX_ESHAPE, "attention: strides must keep 16-byte alignment");
@@ -539,8 +625,18 @@ int ofx_launch_attention_mfma(const AttnArgs& g, int op_dtype, hipStream_t s) {
     k.n_head = g.n_head; k.ld = g.ld; k.ldo = g.ldo; k.k_off = g.k_off; k.v_off = g.v_off; k.mask_ld = g.mask_ld;
     k.causal = g.causal; k.scale = g.scale; k.cu = g.cu_seqlens; k.only_row0 = g.only_row0; k.drop = g.drop; k.split3_w = g.split3_w;
     OFX_REQUIRE(g.split3_w == 0 || (g.split3_w % 8 == 0 && g.ldo >= 3 * g.split3_w), OFX_ESHAPE, "attention: split3 output needs ldo >= 3 W");
-    const int grid = (g.nseq * g.n_head + 3) / 4;
     ProfScope prof(PROF_ATTN, s);
+    if (g.seq_len > 64) {           // one workgroup per (sequence, head), key tiles: 8 (<= 128 rows), 13 (<= 208: the B/16 grids), 16
+        OFX_REQUIRE((long long)g.nseq * g.n_head <= INT_MAX && (long long)g.nseq * g.seq_len <= INT_MAX, OFX_ESHAPE, "attention: nseq=%d is too large", g.nseq);
+        const int pairs = g.nseq * g.n_head;
+#define ATL(T, N) hipLaunchKernelGGL((attention_mfma_long_kernel<T, N>), dim3(pairs), dim3(256), 0, s, k)
+        if (op_dtype == OFX_F16) { if (g.seq_len <= 128) ATL(f16_t, 8); else if (g.seq_len <= 208) ATL(f16_t, 13); else ATL(f16_t, 16); }
+        else { if (g.seq_len <= 128) ATL(bf16_t, 8); else if (g.seq_len <= 208) ATL(bf16_t, 13); else ATL(bf16_t, 16); }
+#undef ATL
+        OFX_LAUNCH_CHECK();
+        return OFX_OK;
+    }
+    const int grid = (g.nseq * g.n_head + 3) / 4;
 #define AT(T, N) hipLaunchKernelGGL((attention_mfma_kernel<T, N>), dim3(grid), dim3(256), 0, s, k)
     const int nt = g.seq_len <= 16 ? 1 : g.seq_len <= 32 ? 2 : 4;
     if (op_dtype == OFX_F16) { if (nt == 1) AT(f16_t, 1); else if (nt == 2) AT(f16_t, 2); else AT(f16_t, 4); }

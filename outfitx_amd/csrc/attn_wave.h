@@ -19,6 +19,10 @@
 // key-padding and causal masks in attention.hip; 144-byte LDS rows and the key >= S mask in fused_qkv_attn.hip).  Every piece is
 // force-inlined with its caller's constants: nu (live query tiles), the dropout switch and split3_w fold where they are literals.
 // The pieces take the lane from threadIdx.x (one-dimensional blocks of 64-lane waves).
+//
+// The tile grid is rectangular: NT key tiles by NU query tiles, NU = NT (the whole sequence in one wave) unless the caller says
+// otherwise.  attention_mfma_long_kernel (attention.hip, 65 .. 256 rows) runs the same pieces with NU = 1: one 16-query tile against
+// all NT <= 16 key tiles, the whole score row still in registers, so the softmax is the same two-pass one over the whole key row.
 #pragma once
 #include "ofx_common.h"
 
@@ -46,13 +50,13 @@ __device__ __forceinline__ typename OpT<T>::v8 attn_tr_frag(OFX_LDS char* img, i
 }
 
 // S^T[key][query] for the query tiles u < nu; neg[t][r] = 0 or -inf for key 16t + 4q4 + r (-inf + finite = -inf)
-template <typename T, int NT>
-__device__ __forceinline__ void attn_scores(f32x4 (&st)[NT][NT], const typename OpT<T>::v8 (&kf)[NT][2], const typename OpT<T>::v8 (&qf)[NT][2],
+template <typename T, int NT, int NU = NT>
+__device__ __forceinline__ void attn_scores(f32x4 (&st)[NT][NU], const typename OpT<T>::v8 (&kf)[NT][2], const typename OpT<T>::v8 (&qf)[NU][2],
                                             const float (&neg)[NT][4], int nu) {
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
-        for (int u = 0; u < NT; ++u) {
+        for (int u = 0; u < NU; ++u) {
             if (u >= nu) continue;
             f32x4 c = {neg[t][0], neg[t][1], neg[t][2], neg[t][3]};
             c = OpT<T>::mfma16(kf[t][0], qf[u][0], c);
@@ -63,13 +67,13 @@ __device__ __forceinline__ void attn_scores(f32x4 (&st)[NT][NT], const typename 
 // Wavefront softmax of the raw scores, P written back normalised as the B operand pf[u][ks] (st is consumed).  A fully masked
 // query gets probabilities 0.  DROP: dropout on the probabilities (training), element (pair, query * 32 + key) as in the fp32 set
 // kernel, behind the wave-uniform drop.thresh test.
-template <typename T, int NT, bool DROP>
-__device__ __forceinline__ void attn_softmax_p(typename OpT<T>::v8 (&pf)[NT][attn_ksteps(NT)], f32x4 (&st)[NT][NT], float scale, int nu,
+template <typename T, int NT, bool DROP, int NU = NT>
+__device__ __forceinline__ void attn_softmax_p(typename OpT<T>::v8 (&pf)[NU][attn_ksteps(NT)], f32x4 (&st)[NT][NU], float scale, int nu,
                                                const DropArgs& drop = DropArgs(), int pair = 0) {
     const int lane = threadIdx.x & 63, r16 = lane & 15, q4 = lane >> 4;
     const float sc = scale * 1.4426950408889634f;
 #pragma unroll
-    for (int u = 0; u < NT; ++u) {
+    for (int u = 0; u < NU; ++u) {
         if (u >= nu) continue;
         float m = -INFINITY;
 #pragma unroll
@@ -112,19 +116,19 @@ __device__ __forceinline__ void attn_softmax_p(typename OpT<T>::v8 (&pf)[NT][att
 // O^T[d][query] = V^T . P^T from the row image vl (rows >= S zero: 0 * garbage must stay 0), ot[nd][u][r] = O[query 16u + r16][d = 16 q4 + 4 nd + r],
 // then, if store (wave-uniform), queries < n_rows of the tiles u < nu -> out[row_first + query][col0 + d]: two 16-byte stores per lane
 // and query.  split3_w > 0 (wave-uniform): the row is [hi(W) | lo(W) | hi(W)], W = split3_w, lo = the rounding residual.
-template <typename T, int NT>
-__device__ __forceinline__ void attn_pv_store(OFX_LDS char* vl, const typename OpT<T>::v8 (&pf)[NT][attn_ksteps(NT)], int nu, bool store,
+template <typename T, int NT, int NU = NT>
+__device__ __forceinline__ void attn_pv_store(OFX_LDS char* vl, const typename OpT<T>::v8 (&pf)[NU][attn_ksteps(NT)], int nu, bool store,
                                               T* out, int row_first, int ldo, int col0, int n_rows, int split3_w) {
     typedef typename OpT<T>::v8 v8;
     const int lane = threadIdx.x & 63, r16 = lane & 15, q4 = lane >> 4;
-    f32x4 ot[4][NT];
+    f32x4 ot[4][NU];
 #pragma unroll
     for (int nd = 0; nd < 4; ++nd) {
         v8 vf[attn_ksteps(NT)];
 #pragma unroll
         for (int ks = 0; ks < attn_ksteps(NT); ++ks) vf[ks] = attn_tr_frag<T>(vl, 32 * ks, 16 * (r16 & 3) + 4 * nd);
 #pragma unroll
-        for (int u = 0; u < NT; ++u) {
+        for (int u = 0; u < NU; ++u) {
             if (u >= nu) continue;
             f32x4 c = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -134,7 +138,7 @@ __device__ __forceinline__ void attn_pv_store(OFX_LDS char* vl, const typename O
     }
     if (!store) return;
 #pragma unroll
-    for (int u = 0; u < NT; ++u) {
+    for (int u = 0; u < NU; ++u) {
         if (u >= nu) continue;
         const int query = 16 * u + r16;
         if (query < n_rows) {

@@ -91,7 +91,7 @@ inline const char* ofx_configure(ofx_handle& h, const ofx_model_desc& d) {
     if (!head64 && !head96) return "d_model must be n_head*64 with d_model in 512/768/1024, or n_head*96 with d_model 1536";
     if (d.vit_width != d.vit_heads * 64 || d.txt_width != d.txt_heads * 64) return "tower head_dim must be 64";
     if (d.vit_width % 256 || d.txt_width % 256 || d.proj_dim % 128 || d.vit_mlp % 128 || d.txt_mlp % 128) return "tower dims must be multiples of 128/256";
-    if (d.vit_image % d.vit_patch || (d.vit_image / d.vit_patch) * (d.vit_image / d.vit_patch) + 1 > 64) return "ViT sequence (patches+1) must be <= 64";
+    if (d.vit_image % d.vit_patch || (d.vit_image / d.vit_patch) * (d.vit_image / d.vit_patch) + 1 > 256) return "ViT sequence (patches+1) must be <= 256";
     if (d.max_items < 0 || d.max_items > 63) return "max_items must be in [0,63]";
     if (d.tower_precision != OFX_PREC_BF16 && d.tower_precision != OFX_PREC_F16) return "tower_precision must be BF16 or F16";
     if (d.outfit_precision < 0 || d.outfit_precision > 3) return "bad outfit_precision";

@@ -111,13 +111,14 @@ class _VisionTransformerParams(nn.Module):
 
 
 class ClipVisionParams(nn.Module):
-    """Same parameter names as HF CLIPVisionModelWithProjection (ViT-B/32 defaults)."""
+    """Same parameter names as HF CLIPVisionModelWithProjection (ViT-B/32 defaults; patch_size=16 is ViT-B/16)."""
+
+    DEFAULTS = dict(hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12, patch_size=32, image_size=224,
+                    projection_dim=512, hidden_act="quick_gelu", layer_norm_eps=1e-5)
 
     def __init__(self, **over):
         super().__init__()
-        self.config = SimpleNamespace(hidden_size=768, intermediate_size=3072, num_hidden_layers=12,
-                                      num_attention_heads=12, patch_size=32, image_size=224, projection_dim=512,
-                                      hidden_act="quick_gelu", layer_norm_eps=1e-5)
+        self.config = SimpleNamespace(**self.DEFAULTS)
         self.config.__dict__.update(over)
         self.vision_model = _VisionTransformerParams(self.config)
         self.visual_projection = nn.Linear(self.config.hidden_size, self.config.projection_dim, bias=False)
@@ -180,6 +181,63 @@ def _try_load_pretrained(params: nn.Module, hf_class_name: str, name: str) -> bo
         return True
     except Exception:
         return False
+
+
+# What the image tower's kernels take (ofx_configure, csrc/ofx_weights.h; the MFMA attention, csrc/attention.hip)
+VISION_MAX_TOKENS = 256
+VISION_WIDTHS = (512, 768, 1024)
+_VISION_FIELDS = ("hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads", "patch_size", "image_size",
+                  "projection_dim", "hidden_act", "layer_norm_eps")
+
+
+def vision_arch(config, dim_per_modality: Optional[int] = None) -> Dict[str, Any]:
+    """A HF CLIPVisionConfig, or a dict with some of its fields (the rest: ViT-B/32 at 224), -> the ClipVisionParams keywords.  An
+    architecture the kernels do not take raises NotImplementedError naming the limit - nothing falls back to another tower."""
+    get = config.get if isinstance(config, dict) else lambda k, d=None: getattr(config, k, d)
+    if isinstance(config, dict) and set(config) - set(_VISION_FIELDS):
+        raise ValueError(f"vision_config: unknown fields {sorted(set(config) - set(_VISION_FIELDS))}; known: {list(_VISION_FIELDS)}")
+    base = ClipVisionParams.DEFAULTS
+    a = {k: (get(k) if get(k) is not None else base[k]) for k in _VISION_FIELDS}
+    name = f"vision tower (width {a['hidden_size']}, {a['num_attention_heads']} heads, patch {a['patch_size']}, image {a['image_size']})"
+    if a["hidden_size"] != a["num_attention_heads"] * 64:
+        raise NotImplementedError(f"{name}: the attention kernels take heads of 64 columns, not {a['hidden_size']} / {a['num_attention_heads']}")
+    if a["hidden_size"] not in VISION_WIDTHS:
+        raise NotImplementedError(f"{name}: the tower GEMMs are built for widths {VISION_WIDTHS}")
+    if a["image_size"] % a["patch_size"]:
+        raise NotImplementedError(f"{name}: the image size must be a multiple of the patch size")
+    tokens = (a["image_size"] // a["patch_size"]) ** 2 + 1
+    if tokens > VISION_MAX_TOKENS:
+        raise NotImplementedError(f"{name}: {tokens} tokens per image exceed the attention kernel's {VISION_MAX_TOKENS}")
+    if a["intermediate_size"] % 128 or a["projection_dim"] % 128:
+        raise NotImplementedError(f"{name}: MLP width {a['intermediate_size']} and projection {a['projection_dim']} must be multiples of 128")
+    if a["hidden_act"] not in L.ACTS:
+        raise NotImplementedError(f"{name}: activation {a['hidden_act']!r} is not one of {sorted(L.ACTS)}")
+    if dim_per_modality is not None and a["projection_dim"] != dim_per_modality:
+        raise NotImplementedError(f"{name}: projection {a['projection_dim']} is not the item encoder's dim_per_modality {dim_per_modality}")
+    return a
+
+
+def read_vision_config(name: str):
+    """The checkpoint's CLIPVisionConfig from local files (of a CLIP checkpoint: its vision half), or None when it is not there."""
+    try:
+        from transformers import CLIPVisionConfig
+        return CLIPVisionConfig.from_pretrained(name, local_files_only=True)
+    except (ImportError, OSError, ValueError):
+        return None
+
+
+def load_vision_checkpoint(name: str, arch: Optional[Dict[str, Any]] = None) -> Optional["ClipVisionParams"]:
+    """A local HF CLIP vision checkpoint -> a parameter tree of ITS architecture (`arch`: vision_arch's result when the caller has
+    already judged it), strict-loaded; None when no such checkpoint is there.  HF is a FILE READER only.  A checkpoint that is there
+    and does not load raises: its shapes come from its own config, so a mismatch is a damaged or foreign file."""
+    cfg = read_vision_config(name)
+    if cfg is None:
+        return None
+    params = ClipVisionParams(**(arch if arch is not None else {k: getattr(cfg, k) for k in _VISION_FIELDS}))
+    import transformers
+    hf = transformers.CLIPVisionModelWithProjection.from_pretrained(name, local_files_only=True)
+    params.load_state_dict(hf.state_dict(), strict=True)
+    return params
 
 
 # ----------------------------------------------------------------------------- host preprocessing
@@ -246,11 +304,23 @@ class _TowerBase(nn.Module):
 class CLIPImageEncoder(_TowerBase):
     """Reference: image_encoders/clip_image_encoder.py:10-79 (+ BaseImageEncoder.forward)."""
 
-    def __init__(self, model_name_or_path: str = "patrickjohncyh/fashion-clip", freeze: bool = True):
+    def __init__(self, model_name_or_path: str = "patrickjohncyh/fashion-clip", freeze: bool = True,
+                 vision_config: Optional[dict] = None, dim_per_modality: Optional[int] = None):
+        """The architecture is the checkpoint's own (its CLIPVisionConfig, read from local files): ViT-B/32, ViT-B/16, any tower of heads
+        of 64 with at most 256 tokens per image.  vision_config: a dict of CLIPVisionConfig fields that sets the architecture instead
+        (offline use, tests; unnamed fields are ViT-B/32's) - weights then come from load_state_dict.  An architecture the kernels do
+        not take raises NotImplementedError; only a checkpoint that is not there leaves a randomly initialised tower and a warning."""
         super().__init__()
-        self.model = ClipVisionParams()
-        self.pretrained = _try_load_pretrained(self.model, "CLIPVisionModelWithProjection", model_name_or_path)
-        if not self.pretrained:
+        if vision_config is not None:
+            self.model = ClipVisionParams(**vision_arch(dict(vision_config), dim_per_modality))
+            self.pretrained = False
+        else:
+            cfg = read_vision_config(model_name_or_path)
+            arch = vision_arch(cfg if cfg is not None else {}, dim_per_modality)
+            loaded = load_vision_checkpoint(model_name_or_path, arch) if cfg is not None else None
+            self.model = loaded if loaded is not None else ClipVisionParams(**arch)
+            self.pretrained = loaded is not None
+        if not self.pretrained and vision_config is None:
             warnings.warn(f"CLIP vision checkpoint '{model_name_or_path}' not available offline: random-initialised "
                           "(load weights with load_state_dict)", stacklevel=2)
         self.model.eval()
@@ -530,7 +600,10 @@ class ItemEncoder(nn.Module):
             raise NotImplementedError(
                 f"ItemEncoderConfig(type='{cfg.type}') is outside the MI355X scoring path; build the model with "
                 "OutfitXConfig(item_encoder=ItemEncoderConfig(type='clip')), or - for precomputed embeddings only - OutfitX(cfg, item_towers=False)")
-        self.image_enc = CLIPImageEncoder(model_name_or_path=cfg.clip_model_name)
+        # clip_vision_config: like clip_model_name an attribute set on the config after construction - a dict of CLIPVisionConfig fields
+        # ({"patch_size": 16}: ViT-B/16) that sets the image tower's architecture without a checkpoint on disk
+        self.image_enc = CLIPImageEncoder(model_name_or_path=cfg.clip_model_name, vision_config=getattr(cfg, "clip_vision_config", None),
+                                          dim_per_modality=cfg.dim_per_modality)
         self.text_enc = CLIPTextEncoder(model_name_or_path=cfg.clip_model_name)
         # side-stream text tower: its small kernels fill the tile-quantisation tails of the big ViT GEMMs.  Neutral with round 1's
         # 1.3 ms single-product text tower; with the three-product one (5 ms) 31.85 vs 32.85 ms per cfg2 step (bench.py --overlap-towers)

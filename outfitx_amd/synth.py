@@ -85,13 +85,13 @@ def _clip_layer_shapes(prefix: str, width: int, mlp: int, n_layers: int) -> Dict
     return s
 
 
-def vision_shapes(n_layers: int = VIT_LAYERS) -> Dict[str, Tuple[int, ...]]:
-    """Key → shape of HF CLIPVisionModelWithProjection (ViT-B/32), keys relative to `….image_enc.model.`"""
+def vision_shapes(n_layers: int = VIT_LAYERS, patch: int = VIT_PATCH, image: int = VIT_IMG) -> Dict[str, Tuple[int, ...]]:
+    """Key → shape of HF CLIPVisionModelWithProjection (ViT-B/32; patch=16 is ViT-B/16, 197 positions), keys relative to `….image_enc.model.`"""
     v = "vision_model."
     s: Dict[str, Tuple[int, ...]] = {
         v + "embeddings.class_embedding": (VIT_WIDTH,),
-        v + "embeddings.patch_embedding.weight": (VIT_WIDTH, 3, VIT_PATCH, VIT_PATCH),
-        v + "embeddings.position_embedding.weight": (VIT_POS, VIT_WIDTH),
+        v + "embeddings.patch_embedding.weight": (VIT_WIDTH, 3, patch, patch),
+        v + "embeddings.position_embedding.weight": ((image // patch) ** 2 + 1, VIT_WIDTH),
         v + "pre_layrnorm.weight": (VIT_WIDTH,),
         v + "pre_layrnorm.bias": (VIT_WIDTH,),
     }
@@ -151,8 +151,8 @@ def outfit_transformer_weights(seed: int, d_model: int = D_MODEL, n_layers: int 
     return make_weights(seed, outfit_transformer_shapes(d_model, n_layers))
 
 
-def vision_weights(seed: int, prefix: str = "", n_layers: int = VIT_LAYERS) -> Dict[str, np.ndarray]:
-    return make_weights(seed, vision_shapes(n_layers), prefix)
+def vision_weights(seed: int, prefix: str = "", n_layers: int = VIT_LAYERS, patch: int = VIT_PATCH, image: int = VIT_IMG) -> Dict[str, np.ndarray]:
+    return make_weights(seed, vision_shapes(n_layers, patch, image), prefix)
 
 
 def text_weights(seed: int, prefix: str = "", n_layers: int = TXT_LAYERS) -> Dict[str, np.ndarray]:

@@ -5,7 +5,9 @@
   cfg4  CIR: 1000 queries vs 100k-item pool, k=50 (unsharded, and one 12.5k shard = 1/8 of the 8-GPU layout)
   cfgw  the wide model beside the default one, same run, alternating: CP forward at cfg1's 32 and cfg3's 1024 outfits, d_model 1024 (16 x 64) and
         1536 (16 x 96, the reference's default SigLIP width, built without towers), bf16x3; median of 30 device-event-timed steps each + the ratio
-Prints one JSON line per config.   python tools/bench_configs.py [cfg1] [cfg1x] [cfg3] [cfg4] [cfgw]   (default: all; cfg1 = 32 outfits only, cfg1x = its 256 / 1024-outfit variants; rocprofv3 passes name one)"""
+  cfgb16 the ViT-B/16 image tower (197 tokens) beside ViT-B/32 (50), 256 images each, alternating steps in one run, default scheme: ms, images/s, the ratio, and
+        from ofx_profile the attention's share of the B/16 tower (only when named: python tools/bench_configs.py cfgb16)
+Prints one JSON line per config.   python tools/bench_configs.py [cfg1] [cfg1x] [cfg3] [cfg4] [cfgw] [cfgb16]   (default: all but cfgb16; cfg1 = 32 outfits only, cfg1x = its 256 / 1024-outfit variants; rocprofv3 passes name one)"""
 import json, os, sys, time, warnings
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -62,7 +64,48 @@ def wide_rows(steps=30, warm=5):
                           "ms_d1024": round(med[1024], 4), "ms_d1536": round(med[1536], 4), "ratio_1536_over_1024": round(med[1536] / med[1024], 3)}), flush=True)
 
 
+def b16_rows(steps=20, warm=3, n_img=256):
+    """ViT-B/16 (197 tokens, the MFMA attention over 65 .. 256 rows) beside ViT-B/32 (50 tokens): the image towers alone, 256 images each, default
+    scheme, steps alternating between the two; then one profiled B/16 step: the attention's share of the tower's launch time."""
+    import ctypes as C
+    from outfitx_amd import _lib as L
+    from outfitx_amd.encoders import CLIPImageEncoder
+    px = cu(synth.pixel_values(1236, n_img)).view(n_img, 1, 3, 224, 224)
+    calls = {}
+    for patch in (32, 16):
+        enc = CLIPImageEncoder(vision_config={"patch_size": patch})
+        enc.load_state_dict({"model." + k: torch.from_numpy(v) for k, v in synth.vision_weights(7, patch=patch).items()}, strict=True)
+        enc = enc.to(dev).eval()
+        calls[patch] = (lambda enc=enc: enc(px))
+    for _ in range(warm):
+        for f in calls.values(): f()
+    torch.cuda.synchronize()
+    ev = {p: [] for p in calls}
+    for _ in range(steps):
+        for p, f in calls.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); f(); b.record()
+            ev[p].append((a, b))
+    torch.cuda.synchronize()
+    med = {p: float(np.median([a.elapsed_time(b) for a, b in ev[p]])) for p in ev}
+    lib = L.load()
+    lib.ofx_profile_enable(15)
+    calls[16](); torch.cuda.synchronize()
+    ms, fl, cnt = (C.c_double * 4)(), (C.c_double * 4)(), (C.c_longlong * 4)()
+    L.check(lib.ofx_profile_read(ms, fl, cnt), "ofx_profile_read")
+    lib.ofx_profile_enable(0)
+    print(json.dumps({"config": "cfgb16", "what": f"image tower alone, {n_img} images, {L.DEFAULT_TOWER_PRECISION}, ViT-B/32 (50 tokens) vs ViT-B/16 (197 tokens), median of {steps} alternating steps",
+                      "ms_b32": round(med[32], 3), "ms_b16": round(med[16], 3), "images_per_s_b32": round(n_img / med[32] * 1e3, 1), "images_per_s_b16": round(n_img / med[16] * 1e3, 1),
+                      "ratio_b16_over_b32": round(med[16] / med[32], 3), "rows_ratio": round(197 / 50, 2),
+                      "b16_profiled_ms": {"gemm": round(ms[0], 3), "norm": round(ms[1], 3), "attention": round(ms[2], 3), "other": round(ms[3], 3)},
+                      "b16_attention_launches": int(cnt[2]), "b16_attention_share": round(ms[2] / sum(ms), 4)}), flush=True)
+
+
 only = set(a for a in sys.argv[1:] if a.startswith("cfg"))
+if only == {"cfgb16"}:
+    with torch.no_grad():
+        b16_rows()
+    sys.exit(0)
 if only == {"cfgw"}:
     with torch.no_grad():
         wide_rows()
