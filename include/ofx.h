@@ -648,7 +648,13 @@ int ofx_set_attention_bwd(const void* qkv, const float* d_o, void* dqkv, const i
 /* Fused QKV projection + scaled-dot-product attention of a CLIP ViT layer (HF CLIPAttention's q/k/v_proj + softmax(q k^T * scale) v,
  * reached from clip_image_encoder.py:74-76), q | k | v staged in LDS only: X [nseq * seq_len, ldx] operand type, Wqkv [3 width, width]
  * (q | k | v rows), bias [3 width]; optional LayerNorm-fold consumer inputs row_stat [rows, 2] (mean, rstd) + col_sum [3 width];
- * out [nseq * seq_len, ldo] operand type (heads concatenated).  seq_len in [33, 64], width = n_head * 64, no mask.  X and out must not alias. */
+ * out [nseq * seq_len, ldo] operand type (heads concatenated).  seq_len in [33, 64] except 35, 36 and 42 (a block's last image would read
+ * key rows past the 16 zeroed pad rows behind its 256-row tile), width = n_head * 64, n_head >= 2, ldx and ldo >= width and multiples of 8
+ * (else OFX_ESHAPE); NULL X, Wqkv, bias or out, nseq <= 0, or row_stat without col_sum: OFX_EINVAL; a refused call launches nothing.  No
+ * mask.  Columns width .. ldo - 1 of out are not written; rows at or past nseq * seq_len of X and row_stat are not read (tile rows past the
+ * end are clamped onto the last row).  X and out must not alias.  q | k | v are ONE rounding of the fp32 projection to the operand type and
+ * the attention is attention_mfma_kernel's wave core: on operands whose fp32 sums are exact the output equals ofx_gemm* -> ofx_attention
+ * value for value (tests/test_gpu_fused_qkv_exact.py). */
 int ofx_fused_qkv_attention(const void* X, const void* Wqkv, const float* bias, const float* row_stat, const float* col_sum, void* out,
                             int nseq, int seq_len, int width, int n_head, int ldx, int ldo, float scale, int op_dtype, ofx_stream stream);
 /* The same against split weights: Wqkv2 [3 width, 2 width], row n = [hi(width) | lo(width)] (ofx_convert mode 3): q | k | v = X . (hi + lo)^T,

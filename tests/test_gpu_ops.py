@@ -621,7 +621,8 @@ def test_fused_qkv_projection_attention(fold, dt, n, S, H):
     """The fused QKV-projection + attention kernel (q | k | v staged in LDS only) against (a) the unfused pair ofx_gemm ->
     ofx_attention on the same operands - the same arithmetic in the same order by construction: both kernels run the one
     wave-level attention core of csrc/attn_wave.h, so equal to the rounding of q | k | v - and (b) float64 arithmetic on the operand-rounded inputs.  Image counts below, at and above one block's group (5 at S = 50,
-    ragged tail), sequence lengths at both ends of the supported range, with and without the LayerNorm-fold epilogue."""
+    ragged tail), sequence lengths at both ends of the supported range, with and without the LayerNorm-fold epilogue.
+    Exactness (value equality with the unfused pair, per (image, head) block, the fold branch): tests/test_gpu_fused_qkv_exact.py."""
     g = np.random.default_rng(n * 7 + S + H + fold)
     W = H * 64
     rows = n * S
@@ -671,7 +672,8 @@ def test_fused_qkv_attention_rejects_sequence_lengths_that_overrun_its_pad_rows(
 def test_fused_qkv_projection_attention_split_weights(fold, dt, n, S, H):
     """Dual-weight variant of the fused kernel (the default tower scheme's ViT layers): q | k | v = X . (hi + lo)^T on the
     gemm_w2 main loop, then the same LDS-staged attention.  Against float64 arithmetic on the operand-rounded X and the exact
-    hi + lo weights, and against the unfused pair ofx_gemm_w2 -> ofx_attention on the same operands."""
+    hi + lo weights, and against the unfused pair ofx_gemm_w2 -> ofx_attention on the same operands.
+    Exactness (value equality with the unfused pair, per (image, head) block, the fold branch): tests/test_gpu_fused_qkv_exact.py."""
     g = np.random.default_rng(n * 11 + S + H + fold)
     W = H * 64
     rows = n * S
