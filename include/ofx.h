@@ -441,7 +441,10 @@ int ofx_profile_records(ofx_prof_record* out, int cap);
  *          transpose of rounds 1-3; any other value is OFX_EINVAL.  Bit-identical results.
  * knob 20: validation only, default 0: 1 = a three-product ViT (vit_x3) keeps q | k | v in fp32 and runs the fp32 attention kernel instead of the MFMA attention
  *          on operand-rounded q | k | v (several times slower; tools/parity_selfcheck.py uses it for its reference run).
- * knob 21: 1 (default) ofx_clip_text_fwd_shared honours its shared_first flag, 0 = it runs the full rows (A/B runs and tests). */
+ * knob 21: 1 (default) ofx_clip_text_fwd_shared honours its shared_first flag, 0 = it runs the full rows (A/B runs and tests).
+ * knob 22: 1 (default) ViT layers with split q | k | v weights and their fp8 copy run the fused QKV-projection + attention kernel's fp8-correction
+ *          variant wherever the qkv GEMM would run as gemm_w2f8_kernel (f16 operands, >= 256 tiles of 256 x 256), 0 = the GEMM -> HBM ->
+ *          attention-kernel pair.  Bit-identical results.  Independent of knob 9, whose bits keep their meaning. */
 int ofx_tune(int knob, int value);
 /* A counter that every ofx_tune call bumps, and whether per-launch profiling events are being recorded: the host mirror replays a
  * stream-captured forward (outfitx_amd/graphs.py) only while the counter still has the value it had at capture time and no recording
@@ -661,6 +664,15 @@ int ofx_fused_qkv_attention(const void* X, const void* Wqkv, const float* bias, 
  * two MFMA products per weight on one copy of the activations (the default tower scheme 'f16w2x'). */
 int ofx_fused_qkv_attention_w2(const void* X, const void* Wqkv2, const float* bias, const float* row_stat, const float* col_sum, void* out,
                                int nseq, int seq_len, int width, int n_head, int ldx, int ldo, float scale, int op_dtype, ofx_stream stream);
+/* The same with the correction product X . lo^T on the block-scaled fp8 matrix instruction, as ofx_gemm_w2f8 computes it: W8 [3 width, width]
+ * bytes and scale8 [3 width] = ofx_pack_lo8 of Wqkv2; f16 operands only.  Every accumulator sees the instruction sequence of gemm_w2f8_kernel,
+ * so q | k | v - and the output - equal ofx_gemm_w2f8(_fold) (256 x 256 kernel) -> ofx_attention bit for bit on ANY operands
+ * (tests/test_gpu_fused_qkv_w2f8.py).  The blocks walk their tiles as the dual-weight GEMMs do: knob 11 sets the grid.  Refused as above, and:
+ * width not a multiple of 128 (or weights of 2 GiB and more): OFX_ESHAPE; NULL W8 or scale8: OFX_EINVAL.  Rows at or
+ * past nseq * seq_len of X are not read (they count as zeros).  Added within ABI version 6: nothing existing changed. */
+int ofx_fused_qkv_attention_w2f8(const void* X, const void* Wqkv2, const void* W8, const void* scale8, const float* bias, const float* row_stat,
+                                 const float* col_sum, void* out, int nseq, int seq_len, int width, int n_head, int ldx, int ldo, float scale,
+                                 ofx_stream stream);
 /* fp32-arithmetic attention over fixed-length sequences of <= 64 rows (the three-product CLIP text tower): qkv fp32 [nseq * seq_len, 3 D]
  * (q | k | v), HF's causal AND key-padding mask (key_mask [nseq, mask_ld] int64, 0 = ignored, may be NULL); out as ofx_set_attention.
  * A fully masked query row has probabilities 0: its output row is exactly 0, in all three copies of a split3 row (the library's own rule, as

@@ -562,6 +562,9 @@ int g_fuse_qkv = 1;     // ofx_tune(9, v): bit 0 (default on) = ViT layers with 
                         // (q | k | v stay in LDS); bit 1 (default OFF) = so do layers with split (hi, lo) weights, through its dual-weight variant: level with the
                         // persistent GEMM + attention-kernel pair in time, same error distribution, but on the 100-seed sweep it re-rolls two borderline small-logit weight draws from 8.0e-4 /
                         // 8.9e-4 to 1.05e-3 / 1.12e-3, so the default scheme keeps the dual-weight GEMM + attention-kernel pair
+int g_fuse_qkv_w2f8 = 1;     // ofx_tune(22, v): 1 (default) = ViT layers with split q | k | v weights and their fp8 pair run the fused kernel's fp8-correction variant wherever the
+                            // plan would run the qkv GEMM as gemm_w2f8_kernel (>= 256 tiles): the same instruction sequence per accumulator, hence the same bits as the pair;
+                            // 0 = the GEMM + attention-kernel pair.  A knob of its own: knob 9 keeps its two bits
 int g_x3_vit_f32_attn = 0;   // ofx_tune(20, v), experiment: 1 = the three-product ViT keeps q | k | v in fp32 and runs the fp32 set attention (as the text tower does) instead of
                             // the MFMA attention on operand-rounded q | k | v - what the attention core's operand rounding costs under peaked attention
 int g_prune_q = 1;      // ofx_tune(8, v): 1 = the ViT's last layer computes queries for the CLS rows only
@@ -574,13 +577,20 @@ static int clip_layer(const ClipLayer& L, const ClipWs& w, int rows, int nseq, i
                       float eps, int causal, const int64_t* key_mask, int mask_ld, int dt, const int* pool_idx, hipStream_t s, bool pool_first) {
     // fused QKV projection + attention (non-pooled ViT layers: one 33..64-token tile per sequence, no mask): q | k | v never reach HBM;
     // split q | k | v weights: its dual-weight variant (ofx_tune(9, 3)), else the dual-weight GEMM + the attention kernel
-    const bool fused = (g_fuse_qkv & (L.qkv.form == W_SPLIT ? 2 : 1)) && !pool_idx && !causal && !key_mask && S >= 33 && S <= 64 && (256 / S - 1) * S + 64 - 256 <= 16;   // (the kernel's key-row overshoot fits its 16 pad rows)
-    if (fused) {
-        TRY(ofx_launch_fused_qkv_attn(w.XB, L.qkv.w, L.qkv.bias, w.S, L.qkv.col_sum, w.H, nseq, S, W, heads, W, W, 0.125f, dt, s, L.qkv.form == W_SPLIT));
+    const bool fits = !pool_idx && !causal && !key_mask && S >= 33 && S <= 64 && (256 / S - 1) * S + 64 - 256 <= 16;   // (the kernel's key-row overshoot fits its 16 pad rows)
+    const bool fused = (g_fuse_qkv & (L.qkv.form == W_SPLIT ? 2 : 1)) && fits;
+    GemmArgs g1{}; g1.A = w.XB; g1.C = w.QKV; g1.row_stat = w.S; g1.M = rows; g1.N = 3 * W;
+    g1.ldc = 3 * W; g1.act = OFX_ACT_NONE; g1.out_kind = OFX_OUT_OP;
+    use_gemm(g1, L.qkv, W);
+    // split weights with their fp8 pair, where the plan would run this call's qkv GEMM as gemm_w2f8_kernel: the fused kernel's variant with the
+    // same correction product - q | k | v, and with them the layer's output, keep the bits of the GEMM + attention pair
+    const bool fused8 = !fused && g_fuse_qkv_w2f8 && fits && L.qkv.form == W_SPLIT && L.qkv.f8.w8 && L.qkv.f8.s8 && dt == OFX_F16 && W % 128 == 0 &&
+                        ofx_gemm_plan_kind(g1, dt) == GEMM_W2F8;
+    if (fused8) {
+        TRY(ofx_launch_fused_qkv_attn(w.XB, L.qkv.w, L.qkv.bias, w.S, L.qkv.col_sum, w.H, nseq, S, W, heads, W, W, 0.125f, dt, s, FUSED_QKV_W2F8, L.qkv.f8.w8, L.qkv.f8.s8));
+    } else if (fused) {
+        TRY(ofx_launch_fused_qkv_attn(w.XB, L.qkv.w, L.qkv.bias, w.S, L.qkv.col_sum, w.H, nseq, S, W, heads, W, W, 0.125f, dt, s, L.qkv.form == W_SPLIT ? FUSED_QKV_W2 : FUSED_QKV_PLAIN));
     } else {
-        GemmArgs g1{}; g1.A = w.XB; g1.C = w.QKV; g1.row_stat = w.S; g1.M = rows; g1.N = 3 * W;
-        g1.ldc = 3 * W; g1.act = OFX_ACT_NONE; g1.out_kind = OFX_OUT_OP;
-        use_gemm(g1, L.qkv, W);
         const bool prune = pool_idx && pool_first && g_prune_q;
         if (prune) {
             // last layer, pooled row = first row of every sequence (ViT CLS): only those rows' queries are ever used.  K | V for all
@@ -1265,6 +1275,7 @@ extern "C" int ofx_tune(int knob, int value) {
         case 17: g_topk_filter = value != 0; return OFX_OK;
         case 20: g_x3_vit_f32_attn = value != 0; return OFX_OK;
         case 21: g_text_shared_first = value != 0; return OFX_OK;
+        case 22: g_fuse_qkv_w2f8 = value != 0; return OFX_OK;
         default: ofx_set_error("ofx_tune: unknown knob %d", knob); return OFX_EINVAL;
     }
 }
@@ -1509,7 +1520,11 @@ extern "C" int ofx_fused_qkv_attention(const void* X, const void* Wqkv, const fl
 }
 extern "C" int ofx_fused_qkv_attention_w2(const void* X, const void* Wqkv2, const float* bias, const float* row_stat, const float* col_sum, void* out,
                                           int nseq, int seq_len, int width, int n_head, int ldx, int ldo, float scale, int op_dtype, ofx_stream stream) {
-    return ofx_launch_fused_qkv_attn(X, Wqkv2, bias, row_stat, col_sum, out, nseq, seq_len, width, n_head, ldx, ldo, scale, op_dtype, (hipStream_t)stream, true);
+    return ofx_launch_fused_qkv_attn(X, Wqkv2, bias, row_stat, col_sum, out, nseq, seq_len, width, n_head, ldx, ldo, scale, op_dtype, (hipStream_t)stream, FUSED_QKV_W2);
+}
+extern "C" int ofx_fused_qkv_attention_w2f8(const void* X, const void* Wqkv2, const void* W8, const void* scale8, const float* bias, const float* row_stat,
+                                            const float* col_sum, void* out, int nseq, int seq_len, int width, int n_head, int ldx, int ldo, float scale, ofx_stream stream) {
+    return ofx_launch_fused_qkv_attn(X, Wqkv2, bias, row_stat, col_sum, out, nseq, seq_len, width, n_head, ldx, ldo, scale, OFX_F16, (hipStream_t)stream, FUSED_QKV_W2F8, W8, scale8);
 }
 extern "C" int ofx_set_attention(const float* qkv, void* out, const int* cu_seqlens, int nseq, int n_head, int D, int ldo,
                                  int out_kind, int max_len, int only_row0, float scale, int op_dtype, ofx_stream stream) {

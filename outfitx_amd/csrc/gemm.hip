@@ -157,6 +157,23 @@ int ofx_gemm_tune(int knob, int value) {
 }
 size_t ofx_gemm_splitk_bytes(int M, int N, int K) { return gemm_splitk_slab_bytes(M, N, K, g_knobs); }
 
+// What gemm_plan reads of a GemmArgs.
+static GemmShape gemm_shape(const GemmArgs& g, int op_dtype) {
+    const bool producer = g.xb_out || g.stat_part || g.xlo;
+    GemmShape sh;
+    sh.M = g.M; sh.N = g.N; sh.K = g.K; sh.lda = g.lda; sh.a_wrap = g.a_wrap; sh.k_mult = g.k_mult;
+    sh.f16 = op_dtype == OFX_F16; sh.has_w8 = g.W8 && g.w8_scale; sh.has_m_dev = g.m_dev != nullptr;
+    sh.can_split = g.slab && !producer && !g.row_stat; sh.defer = g.defer_splits != nullptr;
+    sh.ln_fusable = g.ln_gamma && g.out_kind == 0 && g.act == OFX_ACT_NONE && !g.aux_out && !g.drop.thresh;
+    sh.out_kind = g.out_kind; sh.resid = g.resid != nullptr; sh.aux = g.aux_out != nullptr; sh.xlo = g.xlo != nullptr;
+    return sh;
+}
+// The GemmKind ofx_launch_gemm would run these arguments as, under the current knobs: callers that choose between a GEMM and a kernel
+// that stands in for it (clip_layer: the fused QKV projection + attention with the fp8 correction) ask the plan instead of copying its rules.
+int ofx_gemm_plan_kind(const GemmArgs& g, int op_dtype) { return gemm_plan(gemm_shape(g, op_dtype), g_knobs, device_cu_count()).kind; }
+// Grid of a kernel outside the dispatcher that walks its nwg tiles as the dual-weight GEMMs do: ofx_tune(11, v) applies.
+int ofx_gemm_w2_grid(int nwg) { return gemm_persistent_grid(nwg, g_knobs.w2_persist, false, device_cu_count()); }
+
 // Four steps: validate, describe the problem (GemmShape), plan (gemm_plan: every decision), carry the plan out.
 int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
     OFX_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, OFX_ESHAPE, "gemm: empty problem M=%d N=%d K=%d", g.M, g.N, g.K);
@@ -181,13 +198,7 @@ int ofx_launch_gemm(const GemmArgs& g, int op_dtype, hipStream_t s) {
     OFX_REQUIRE(!(g.row_stat || producer) || !g.resid, OFX_EINVAL, "gemm: LayerNorm folding takes no residual (a producer's stream is (xb_out, xlo))");
     OFX_REQUIRE(!producer || g.act == OFX_ACT_NONE, OFX_EINVAL, "gemm: a LayerNorm-fold producer has no activation");
 
-    GemmShape sh;
-    sh.M = g.M; sh.N = g.N; sh.K = g.K; sh.lda = g.lda; sh.a_wrap = g.a_wrap; sh.k_mult = g.k_mult;
-    sh.f16 = op_dtype == OFX_F16; sh.has_w8 = g.W8 && g.w8_scale; sh.has_m_dev = g.m_dev != nullptr;
-    sh.can_split = g.slab && !producer && !g.row_stat; sh.defer = g.defer_splits != nullptr;
-    sh.ln_fusable = g.ln_gamma && g.out_kind == 0 && g.act == OFX_ACT_NONE && !g.aux_out && !g.drop.thresh;
-    sh.out_kind = g.out_kind; sh.resid = g.resid != nullptr; sh.aux = g.aux_out != nullptr; sh.xlo = g.xlo != nullptr;
-    const GemmPlan pl = gemm_plan(sh, g_knobs, device_cu_count());
+    const GemmPlan pl = gemm_plan(gemm_shape(g, op_dtype), g_knobs, device_cu_count());
     if (pl.splits > 1) OFX_REQUIRE(g.slab_bytes >= (size_t)pl.splits * g.M * g.N * 4, OFX_EWORKSPACE, "gemm: split-K slab too small");
 
     // record label: logical shape (K without the split-weight / three-product concatenation), the K multiplier and the GemmKind

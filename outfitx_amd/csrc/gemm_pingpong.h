@@ -1,5 +1,5 @@
 // The two-wave-group "ping-pong" main loop of the counted-wait 8-wave tile kernels, once (included by gemm_common.h): gemm_w2.hip,
-// gemm_x3.hip, gemm_w2f8.hip and the dual-weight branch of fused_qkv_attn.hip.  The kernels keep what is theirs - stage layout,
+// gemm_x3.hip, gemm_w2f8.hip and the dual-weight branch and the fp8-correction kernel of fused_qkv_attn.hip.  The kernels keep what is theirs - stage layout,
 // piece list, wait counts, products - and pass it in as callables; everything here is force-inlined into them.
 //
 // Waves 0-3 (group 0) and 4-7 (group 1) run the same per-k-step program offset by ONE barrier slot: on every SIMD one wave reads its

@@ -323,6 +323,8 @@ struct GemmArgs {
 int ofx_launch_gemm(const GemmArgs& g, int op_dtype /*OFX_BF16|OFX_F16*/, hipStream_t s);
 size_t ofx_gemm_splitk_bytes(int M, int N, int K);      // under the current knobs
 int ofx_gemm_tune(int knob, int value);      // ofx_tune's knobs 2, 5, 11, 15, 16, 18: the GemmKnobs object of gemm.hip
+int ofx_gemm_plan_kind(const GemmArgs& g, int op_dtype);      // the GemmKind (gemm_plan.h) ofx_launch_gemm would run g as, under the current knobs
+int ofx_gemm_w2_grid(int nwg);               // persistent grid over nwg tiles under ofx_tune(11, v), as the dual-weight GEMMs take it
 
 struct LnArgs {
     const float* x;        // [rows_in, D] fp32
@@ -420,8 +422,12 @@ struct SetAttnArgs {
     int splits = 1; size_t plane = 0; const float* bias = nullptr;
 };
 int ofx_launch_set_attention(const SetAttnArgs& a, int op_dtype, hipStream_t s);
+// form of the q | k | v weights: one product | split rows [hi | lo], two f16 products | split rows + the fp8 copy of the lo half (W8, scale8:
+// ofx_launch_pack_lo8), the correction product on the block-scaled fp8 instruction as in gemm_w2f8_kernel (f16 operands only)
+enum FusedQkvForm { FUSED_QKV_PLAIN = 0, FUSED_QKV_W2 = 1, FUSED_QKV_W2F8 = 2 };
 int ofx_launch_fused_qkv_attn(const void* X, const void* Wqkv, const float* bias, const float* row_stat, const float* col_sum, void* out,
-                              int n_img, int S, int Wm, int heads, int ldx, int ldo, float scale, int op_dtype, hipStream_t s, bool w2 = false);
+                              int n_img, int S, int Wm, int heads, int ldx, int ldo, float scale, int op_dtype, hipStream_t s, FusedQkvForm form = FUSED_QKV_PLAIN,
+                              const void* W8 = nullptr, const void* scale8 = nullptr);
 
 // ---- pack helpers, training backward, losses, optimizer, scoring
 int ofx_launch_multi_copy(const void* table_host, int n, hipStream_t s);
