@@ -297,10 +297,18 @@ class Engine:
         L.check(self.lib.ofx_train_arm_layer_events(self.h, arr, len(events)), "ofx_train_arm_layer_events")
 
     # ---------------------------------------------------------------- towers
+    @staticmethod
+    def _check_out_rows(out: torch.Tensor, n: int, who: str) -> None:
+        """The towers write n rows of out: the library sees a pointer and a stride, so a shorter buffer is refused HERE, before anything is
+        launched (a caller that sized out by another count - images and texts that disagree - would otherwise have rows written past its end)."""
+        if out.dim() != 2 or out.shape[0] < n:
+            raise ValueError(f"{who}: out has shape {tuple(out.shape)}, the tower writes {n} rows")
+
     def vit(self, pixels: torch.Tensor, out: torch.Tensor, col: int, normalize: bool) -> None:
         """pixels [N,3,H,W] fp32 pixel_values -> out[:, col:col+512] (out is [N, ld] fp32 contiguous)."""
         px = _f32c(pixels, self.device)
         N = px.shape[0]
+        self._check_out_rows(out, N, "vit")
         nb = self.ws_bytes(L.OP_VIT, N, 0)
         ws = self.workspace(nb)
         with torch.cuda.device(self.device):
@@ -355,6 +363,7 @@ class Engine:
     def vit_u8(self, images: Sequence, mean: Sequence[float], std: Sequence[float], out: torch.Tensor, col: int, normalize: bool) -> None:
         """uint8 images -> out[:, col:col+512]: the GPU preprocessor feeds the patch-embedding GEMM directly
         (ofx_vit_b32_fwd_u8); same result as clip_preprocess + vit without the fp32 pixel tensor in between."""
+        self._check_out_rows(out, len(images), "vit_u8")
         src, offs, hs, ws_ = self._stage_images(images)
         N = len(hs)
         I = C.POINTER(C.c_int); LL = C.POINTER(C.c_longlong)
@@ -384,6 +393,7 @@ class Engine:
         """ids/att [N,T] int64 -> out[:, col:col+512].  lengths: host ints (EOS position + 1) or None; a TextLengths carries the
         shared-first-row predicate of the host ids it was computed from (the ids themselves may already be on the device), host ids
         passed here are examined directly, anything else computes the full rows."""
+        self._check_out_rows(out, ids.shape[0], "text")
         shared = lengths.shared_first if isinstance(lengths, TextLengths) else shared_first_row(ids, att)
         ids_d, att_d = self.stage_tokens(ids, att)
         N, T = ids_d.shape

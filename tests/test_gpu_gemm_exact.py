@@ -6,8 +6,9 @@ equality with the float64 product of the same arrays: fp32 output, integer bias,
 otherwise).  Cases of one group that share their arrays (the grids of one shape; gemm_x3_kernel and the K-concatenated path) are
 thereby bit-identical to each other as well.  With per-launch records on, the kernel that ran is the one the case names.
 
-What stays with the tolerance tests (test_gpu_ops.py, test_gpu_fold_ops.py, test_gpu_bwd_ops.py): real-valued data, activations, the
-LayerNorm-fold epilogues and operand-type outputs."""
+What this file leaves out - real-valued data, activations, the LayerNorm-fold epilogues and operand-type outputs - is held element by
+element, on every route of the forward epilogue, by test_gpu_gemm_epilogue_exact.py (the training features and the fold producer by
+test_gpu_bwd_ops.py and test_gpu_fold_ops.py)."""
 import ctypes as C
 
 import numpy as np

@@ -194,6 +194,30 @@ def test_item_encoder_cp_with_encoder_and_precompute(model):
         model.item_encoder([[np.zeros((224, 224, 3), np.uint8)], []], texts)
 
 
+def test_towers_refuse_an_output_buffer_shorter_than_their_rows(model):
+    """The towers are handed a pointer and a stride: Engine.text / vit / vit_u8 refuse an `out` with fewer rows than they would write,
+    BEFORE any launch.  ItemEncoder.forward sizes its buffer by the images; with images and texts that disagree (the ValueError case at
+    the end of the test above: 1 image, 6 texts) the text tower, enqueued first on its side stream, used to write 5 rows past the end of a
+    1-row buffer - silently, or as an illegal access reported by whatever ran next, depending on where the allocator had put the block."""
+    ids, att = synth.token_batch(1239, 6, 64, np.array([4, 8, 6, 3, 9, 12]))
+    px = synth.pixel_values(1239, 2)
+    whole = torch.full((8, 1024), -7.0, device="cuda")
+    teng, veng = model.item_encoder.text_enc._engine("text"), model.item_encoder.image_enc._engine("vision")
+    with pytest.raises(ValueError, match="the tower writes 6 rows"):
+        teng.text(torch.from_numpy(ids), torch.from_numpy(att), whole[:1], 512, True, None)
+    with pytest.raises(ValueError, match="the tower writes 2 rows"):
+        veng.vit(cu(px), whole[:1], 0, True)
+    with pytest.raises(ValueError, match="the tower writes 2 rows"):
+        veng.vit_u8([np.zeros((224, 224, 3), np.uint8)] * 2, [0.5] * 3, [0.5] * 3, whole[:1], 0, True)
+    with pytest.raises(ValueError):
+        model.item_encoder([[np.zeros((224, 224, 3), np.uint8)], []], {"input_ids": torch.from_numpy(ids).view(2, 3, 64), "attention_mask": torch.from_numpy(att).view(2, 3, 64)})
+    torch.cuda.synchronize()
+    assert (whole == -7.0).all()                                # nothing was launched
+    teng.text(torch.from_numpy(ids), torch.from_numpy(att), whole[:6], 512, True, None)       # the same call with room for its rows
+    torch.cuda.synchronize()
+    assert (whole[:6, 512:] != -7.0).all() and (whole[6:] == -7.0).all() and (whole[:, :512] == -7.0).all()
+
+
 def test_scoring_vs_reference_golden_bit_exact():
     from outfitx_amd.engine import Engine, fitb_argmin
     g = golden("scoring")
