@@ -401,6 +401,22 @@ size_t ofx_adamw_step_ws_bytes(long long n_arena);
 int ofx_adamw_step(const ofx_opt_segment* segments, int n_segments, float* grad, float* exp_avg, float* exp_avg_sq, long long n_arena,
                    float* step, double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm, double grad_scale,
                    float* grad_norm, int* skipped, void* ws, size_t ws_bytes, ofx_stream stream);
+/* The same boundary behind a dynamic loss scale: torch.amp.GradScaler's unscale_ -> clip_grad_norm_ -> step -> update as one call, for
+ * training with f16 operands (the arena then holds *loss_scale times the gradient, because the loss was multiplied by it before the
+ * backward).  Arguments, workspace, refusals and guarantees of ofx_adamw_step, plus the scaler's state, which lives on the device and is
+ * read AND rewritten: loss_scale (1 float) and growth_tracker (1 int, the unskipped steps since the scale last changed).
+ *   g     = (grad_scale * (float)(1.0 / *loss_scale)) * grad      (one fp32 factor; exact for a power-of-two scale)
+ *   norm, *grad_norm, *skipped, the update and the zeroing: as above on this g - *grad_norm is the UNSCALED norm
+ *   skipped:    *loss_scale *= backoff_factor;  *growth_tracker = 0
+ *   otherwise:  *growth_tracker += 1;  when it equals growth_interval: *loss_scale *= growth_factor (kept as it is if the product is not
+ *               finite), *growth_tracker = 0.  The products are formed in double and stored as float, as torch does.
+ * Additionally refused, before anything is launched: loss_scale / growth_tracker NULL or not 4-byte aligned (OFX_EINVAL); growth_factor
+ * < 1, backoff_factor outside (0, 1] or growth_interval < 1, NaNs included (OFX_EINVAL).  Same workspace size; still two launches, no
+ * atomics, nothing read back. */
+int ofx_adamw_step_scaled(const ofx_opt_segment* segments, int n_segments, float* grad, float* exp_avg, float* exp_avg_sq, long long n_arena,
+                          float* step, double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm, double grad_scale,
+                          float* loss_scale, int* growth_tracker, double growth_factor, double backoff_factor, int growth_interval,
+                          float* grad_norm, int* skipped, void* ws, size_t ws_bytes, ofx_stream stream);
 
 /* ------------------------------------------------------------------ profiling --------------- */
 /* HIP-event timing of every launch, by category {0 GEMM, 1 norm/embed, 2 attention, 3 other}.

@@ -171,6 +171,7 @@ SIGNATURES = {
     "ofx_cir_sample_batch": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, C.c_uint, C.c_uint, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "ofx_adamw_step_ws_bytes": (_sz, [C.c_longlong]),
     "ofx_adamw_step": (_i, [_vp, _i, _vp, _vp, _vp, C.c_longlong, _vp] + [C.c_double] * 7 + [_vp, _vp, _vp, _sz, _vp]),
+    "ofx_adamw_step_scaled": (_i, [_vp, _i, _vp, _vp, _vp, C.c_longlong, _vp] + [C.c_double] * 7 + [_vp, _vp, C.c_double, C.c_double, _i] + [_vp, _vp, _vp, _sz, _vp]),
     "ofx_profile_enable": (None, [_i]),
     "ofx_profile_read": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
     "ofx_profile_records": (_i, [C.POINTER(ProfRecord), _i]),

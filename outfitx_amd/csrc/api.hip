@@ -1261,6 +1261,26 @@ extern "C" int ofx_adamw_step(const ofx_opt_segment* segments, int n_segments, f
     return ofx_launch_adamw_step(segments, n_segments, grad, exp_avg, exp_avg_sq, n_arena, step, lr, beta1, beta2, eps, weight_decay, max_norm,
                                  grad_scale, grad_norm, skipped, ws, (hipStream_t)stream);
 }
+extern "C" int ofx_adamw_step_scaled(const ofx_opt_segment* segments, int n_segments, float* grad, float* exp_avg, float* exp_avg_sq, long long n_arena,
+                                     float* step, double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm,
+                                     double grad_scale, float* loss_scale, int* growth_tracker, double growth_factor, double backoff_factor,
+                                     int growth_interval, float* grad_norm, int* skipped, void* ws, size_t ws_bytes, ofx_stream stream) {
+    OFX_REQUIRE(segments && grad && exp_avg && exp_avg_sq && step && grad_norm && skipped && ws && loss_scale && growth_tracker, OFX_EINVAL,
+                "adamw_step_scaled: NULL argument");
+    OFX_REQUIRE(n_segments >= 1 && n_segments <= 1024, OFX_ESHAPE, "adamw_step_scaled: n_segments = %d; needs 1 <= n_segments <= 1024", n_segments);
+    OFX_REQUIRE(adamw_shape_ok(n_arena), OFX_ESHAPE, "adamw_step_scaled: n_arena = %lld; needs a positive multiple of 64", n_arena);
+    OFX_REQUIRE((((uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)ws) & 15) == 0 && ((uintptr_t)segments & 7) == 0, OFX_EINVAL,
+                "adamw_step_scaled: grad, exp_avg, exp_avg_sq and ws must be 16-byte aligned, segments 8-byte aligned");
+    OFX_REQUIRE((((uintptr_t)loss_scale | (uintptr_t)growth_tracker) & 3) == 0, OFX_EINVAL,
+                "adamw_step_scaled: loss_scale and growth_tracker must be 4-byte aligned");
+    OFX_REQUIRE(growth_factor >= 1.0 && backoff_factor > 0.0 && backoff_factor <= 1.0 && growth_interval >= 1, OFX_EINVAL,      // NaNs fail too
+                "adamw_step_scaled: growth_factor = %g, backoff_factor = %g, growth_interval = %d; needs growth >= 1, 0 < backoff <= 1, interval >= 1",
+                growth_factor, backoff_factor, growth_interval);
+    OFX_REQUIRE(ws_bytes >= ofx_adamw_step_ws(n_arena), OFX_EWORKSPACE, "adamw_step_scaled: workspace %zu < %zu bytes", ws_bytes, ofx_adamw_step_ws(n_arena));
+    return ofx_launch_adamw_step_scaled(segments, n_segments, grad, exp_avg, exp_avg_sq, n_arena, step, lr, beta1, beta2, eps, weight_decay, max_norm,
+                                        grad_scale, loss_scale, growth_tracker, growth_factor, backoff_factor, growth_interval, grad_norm, skipped,
+                                        ws, (hipStream_t)stream);
+}
 
 // ------------------------------------------------------------------------------------- tuning
 extern "C" int ofx_tune(int knob, int value) {

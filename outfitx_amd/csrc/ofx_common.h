@@ -457,6 +457,10 @@ size_t ofx_adamw_step_ws(long long n_arena);
 int ofx_launch_adamw_step(const ofx_opt_segment* segments, int n_segments, float* grad, float* exp_avg, float* exp_avg_sq, long long n_arena,
                           float* step, double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm, double grad_scale,
                           float* grad_norm, int* skipped, void* ws, hipStream_t s);
+int ofx_launch_adamw_step_scaled(const ofx_opt_segment* segments, int n_segments, float* grad, float* exp_avg, float* exp_avg_sq, long long n_arena,
+                                 float* step, double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm,
+                                 double grad_scale, float* loss_scale, int* growth_tracker, double growth_factor, double backoff_factor,
+                                 int growth_interval, float* grad_norm, int* skipped, void* ws, hipStream_t s);
 int ofx_launch_cp_head_bwd(const float* dlogits, const float* w_or_rows, const int* cu, float* dX, void* dXb, float* db, int B, int D, int op_dtype,
                            const DropArgs& head, const DropArgs& below, hipStream_t s, int accumulate = 0);
 int ofx_launch_fitb(const float* y, const float* cand, int B, int C, int D, int64_t* idx, float* dist, hipStream_t s);

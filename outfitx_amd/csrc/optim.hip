@@ -25,6 +25,22 @@
 //      float4s) past a tensor's end only have their gradient zeroed.
 // No floating-point atomics and no atomics at all: two calls from the same state give the same bits.  Nothing is allocated, copied
 // or waited for; both launches go to the caller's stream and can be captured.
+//
+// ofx_adamw_step_scaled: the same boundary behind a dynamic loss scale, torch.amp.GradScaler's unscale_ -> step -> update (what the
+// reference's trainers wrap the sequence above in), still two launches, the same loads and stores per arena float, and no atomics.  The
+// arena holds loss_scale x the gradient; the scale and its growth tracker are device scalars that this call reads AND rewrites:
+//   1. adamw_norm_kernel<true>: every element times c = grad_scale * inv in fp32, inv = (float)(1.0 / (double)*loss_scale), then the
+//      same double sum.  Workgroup 0 also copies *loss_scale and *growth_tracker into the workspace header, next to *step.
+//   2. adamw_update_kernel<true>: thread 0 of EVERY workgroup rebuilds c from the header's copy of the scale; workgroup 0 writes the
+//      new scale and tracker to *loss_scale / *growth_tracker.  That is the hazard the header's step copy exists for: workgroups of
+//      one launch run in no defined order, so a workgroup that read *loss_scale itself could see the value workgroup 0 has already
+//      replaced, and unscale its share of the arena by another factor than the norm was taken with.  Nobody writes the header in
+//      launch 2 and nobody writes *loss_scale in launch 1, so every read is of a value that is final.
+//      The scaler: skipped (non-finite norm) -> scale *= backoff, tracker = 0; else tracker += 1 and, when it equals growth_interval,
+//      scale *= growth (kept if that is not finite, as torch does) and tracker = 0.  Products in double, stored as float.
+// For a power-of-two scale S, (g S) * (grad_scale / S) and g * grad_scale are the same real number: the scaled call on S x the arena
+// returns the bits of the plain call (tests/test_gpu_loss_scale.py).  The plain kernels' code is what it was before the scaled ones
+// were added: each kernel is one template, and its SCALED = false instance never reads the scaler's arguments.
 #include <math.h>
 
 #include "ofx_common.h"
@@ -35,7 +51,7 @@ constexpr int OPT_THREADS = 256;
 constexpr int OPT_UNROLL = 4;
 constexpr long long OPT_WG_FLOATS = (long long)OPT_THREADS * 4 * OPT_UNROLL;      // 4096 floats per workgroup and stride step
 constexpr int OPT_MAX_GRID = 2048;
-constexpr size_t OPT_HDR_BYTES = 256;             // workspace: float step_old, pad | double partial[OPT_MAX_GRID]
+constexpr size_t OPT_HDR_BYTES = 256;             // workspace: float step_old, float scale_old, int tracker_old, pad | double partial[OPT_MAX_GRID]
 
 struct OptConsts {                                 // per-step constants, fp32 images of values computed in double
     float clip, decay, w1, beta2, w2, step_size, bc2_sqrt, eps;
@@ -56,10 +72,24 @@ __device__ __forceinline__ double block_sum_f64(double v, double* sred) {
     return (sred[0] + sred[1]) + (sred[2] + sred[3]);
 }
 
+struct OptHeader { float step_old, scale_old; int tracker_old; };      // the first words of the workspace
+
+// the factor a scaled gradient element is multiplied by, in fp32: grad_scale / loss_scale
+__device__ __forceinline__ float unscale_factor(float grad_scale, float loss_scale) { return grad_scale * (float)(1.0 / (double)loss_scale); }
+
+struct ScalerArgs {                                // ofx_adamw_step_scaled's additions; all zero and never read when !SCALED
+    float* loss_scale;
+    int* growth_tracker;
+    double growth, backoff;
+    int interval;
+};
+
+template <bool SCALED>
 __global__ __launch_bounds__(OPT_THREADS) void adamw_norm_kernel(const float* __restrict__ grad, long long n, float grad_scale,
-                                                                 const float* __restrict__ step, float* step_old, double* partial) {
+                                                                 const float* __restrict__ step, OptHeader* hdr, double* partial, ScalerArgs sa) {
     __shared__ double sred[4];
     const int tid = threadIdx.x;
+    if constexpr (SCALED) grad_scale = unscale_factor(grad_scale, *sa.loss_scale);
     double acc[OPT_UNROLL];
 #pragma unroll
     for (int u = 0; u < OPT_UNROLL; ++u) acc[u] = 0.0;
@@ -81,7 +111,10 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_norm_kernel(const float* __
     const double s = block_sum_f64((acc[0] + acc[1]) + (acc[2] + acc[3]), sred);
     if (tid == 0) {
         partial[blockIdx.x] = s;
-        if (blockIdx.x == 0) *step_old = *step;
+        if (blockIdx.x == 0) {
+            hdr->step_old = *step;
+            if constexpr (SCALED) { hdr->scale_old = *sa.loss_scale; hdr->tracker_old = *sa.growth_tracker; }
+        }
     }
 }
 
@@ -95,13 +128,16 @@ __device__ __forceinline__ double pow_int(double b, long long t) {
     return r;
 }
 
+template <bool SCALED>
 __global__ __launch_bounds__(OPT_THREADS) void adamw_update_kernel(const ofx_opt_segment* __restrict__ seg, int n_seg, float* __restrict__ grad,
                                                                    float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq, long long n,
                                                                    float grad_scale, double lr, double beta1, double beta2, double eps, double wd,
                                                                    double max_norm, int n_partial, const double* __restrict__ partial,
-                                                                   const float* __restrict__ step_old, float* step, float* grad_norm, int* skipped) {
+                                                                   const OptHeader* __restrict__ hdr, float* step, float* grad_norm, int* skipped,
+                                                                   ScalerArgs sa) {
     __shared__ double sred[4];
     __shared__ OptConsts sc;
+    __shared__ float s_unscale;
     const int tid = threadIdx.x;
     double a = 0.0;
     for (int i = tid; i < n_partial; i += OPT_THREADS) a += partial[i];
@@ -109,7 +145,7 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_update_kernel(const ofx_opt
     if (tid == 0) {
         const float norm = (float)sqrt(sumsq);
         const bool ok = isfinite(norm);
-        const float t = *step_old + 1.0f;
+        const float t = hdr->step_old + 1.0f;
         const double bc1 = 1.0 - pow_int(beta1, (long long)t), bc2 = 1.0 - pow_int(beta2, (long long)t);
         sc.skip = !ok;
         sc.clip = (float)fmin(max_norm / ((double)norm + 1e-6), 1.0);
@@ -125,9 +161,27 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_update_kernel(const ofx_opt
             *skipped = ok ? 0 : 1;
             if (ok) *step = t;
         }
+        if constexpr (SCALED) {
+            const float scale = hdr->scale_old;
+            s_unscale = unscale_factor(grad_scale, scale);
+            if (blockIdx.x == 0) {                                         // GradScaler.update(); everyone else reads the header's copy
+                const int grown = hdr->tracker_old + 1;
+                if (!ok) {
+                    *sa.loss_scale = (float)((double)scale * sa.backoff);
+                    *sa.growth_tracker = 0;
+                } else if (grown == sa.interval) {
+                    const float up = (float)((double)scale * sa.growth);
+                    if (isfinite(up)) *sa.loss_scale = up;
+                    *sa.growth_tracker = 0;
+                } else {
+                    *sa.growth_tracker = grown;
+                }
+            }
+        }
     }
     __syncthreads();
     const OptConsts c = sc;
+    if constexpr (SCALED) grad_scale = s_unscale;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 
     if (c.skip) {                                                          // non-finite norm: drop the gradient, touch nothing else
@@ -222,6 +276,22 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_update_kernel(const ofx_opt
 
 int opt_grid(long long n) { return (int)((n + OPT_WG_FLOATS - 1) / OPT_WG_FLOATS < OPT_MAX_GRID ? (n + OPT_WG_FLOATS - 1) / OPT_WG_FLOATS : OPT_MAX_GRID); }
 
+template <bool SCALED>
+int launch_step(const ofx_opt_segment* segments, int n_segments, float* grad, float* exp_avg, float* exp_avg_sq, long long n_arena, float* step,
+                double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm, double grad_scale, const ScalerArgs& sa,
+                float* grad_norm, int* skipped, void* ws, hipStream_t s) {
+    static_assert(sizeof(OptHeader) <= OPT_HDR_BYTES, "the workspace header holds the step, the scale and the tracker");
+    OptHeader* hdr = (OptHeader*)ws;
+    double* partial = (double*)((char*)ws + OPT_HDR_BYTES);
+    const int grid = opt_grid(n_arena);
+    hipLaunchKernelGGL(adamw_norm_kernel<SCALED>, dim3(grid), dim3(OPT_THREADS), 0, s, grad, n_arena, (float)grad_scale, step, hdr, partial, sa);
+    OFX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(adamw_update_kernel<SCALED>, dim3(grid), dim3(OPT_THREADS), 0, s, segments, n_segments, grad, exp_avg, exp_avg_sq, n_arena,
+                       (float)grad_scale, lr, beta1, beta2, eps, weight_decay, max_norm, grid, partial, hdr, step, grad_norm, skipped, sa);
+    OFX_LAUNCH_CHECK();
+    return OFX_OK;
+}
+
 }  // namespace
 
 size_t ofx_adamw_step_ws(long long n_arena) { return OPT_HDR_BYTES + (size_t)opt_grid(n_arena) * sizeof(double); }
@@ -229,13 +299,14 @@ size_t ofx_adamw_step_ws(long long n_arena) { return OPT_HDR_BYTES + (size_t)opt
 int ofx_launch_adamw_step(const ofx_opt_segment* segments, int n_segments, float* grad, float* exp_avg, float* exp_avg_sq, long long n_arena,
                           float* step, double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm, double grad_scale,
                           float* grad_norm, int* skipped, void* ws, hipStream_t s) {
-    float* step_old = (float*)ws;
-    double* partial = (double*)((char*)ws + OPT_HDR_BYTES);
-    const int grid = opt_grid(n_arena);
-    hipLaunchKernelGGL(adamw_norm_kernel, dim3(grid), dim3(OPT_THREADS), 0, s, grad, n_arena, (float)grad_scale, step, step_old, partial);
-    OFX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(adamw_update_kernel, dim3(grid), dim3(OPT_THREADS), 0, s, segments, n_segments, grad, exp_avg, exp_avg_sq, n_arena,
-                       (float)grad_scale, lr, beta1, beta2, eps, weight_decay, max_norm, grid, partial, step_old, step, grad_norm, skipped);
-    OFX_LAUNCH_CHECK();
-    return OFX_OK;
+    return launch_step<false>(segments, n_segments, grad, exp_avg, exp_avg_sq, n_arena, step, lr, beta1, beta2, eps, weight_decay, max_norm, grad_scale,
+                              ScalerArgs{}, grad_norm, skipped, ws, s);
+}
+
+int ofx_launch_adamw_step_scaled(const ofx_opt_segment* segments, int n_segments, float* grad, float* exp_avg, float* exp_avg_sq, long long n_arena,
+                                 float* step, double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm,
+                                 double grad_scale, float* loss_scale, int* growth_tracker, double growth_factor, double backoff_factor,
+                                 int growth_interval, float* grad_norm, int* skipped, void* ws, hipStream_t s) {
+    return launch_step<true>(segments, n_segments, grad, exp_avg, exp_avg_sq, n_arena, step, lr, beta1, beta2, eps, weight_decay, max_norm, grad_scale,
+                             ScalerArgs{loss_scale, growth_tracker, growth_factor, backoff_factor, growth_interval}, grad_norm, skipped, ws, s);
 }

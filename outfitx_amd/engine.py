@@ -710,6 +710,35 @@ def adamw_step(segments: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor
                                    _ptr(grad_norm), _ptr(skipped), _ptr(ws), ws.numel(), _stream(dev)), "ofx_adamw_step")
 
 
+def adamw_step_scaled(segments: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, step: torch.Tensor,
+                      lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, max_norm: float, grad_scale: float,
+                      loss_scale: torch.Tensor, growth_tracker: torch.Tensor, growth_factor: float, backoff_factor: float, growth_interval: int,
+                      grad_norm: torch.Tensor, skipped: torch.Tensor, ws: Optional[torch.Tensor] = None) -> None:
+    """adamw_step on an arena that holds loss_scale x the gradient, with torch.amp.GradScaler's unscale_ before it and its update() after
+    it, still two launches (ofx_adamw_step_scaled; semantics in include/ofx.h).  loss_scale: 1-element fp32, growth_tracker: 1-element
+    int32, both on the arena's device, both read and rewritten; grad_norm receives the UNSCALED norm.  The other arguments are
+    adamw_step's."""
+    lib = L.load()
+    dev = grad.device
+    if dev.type != "cuda":
+        raise L.OfxError("adamw_step_scaled needs HIP tensors; there is no CPU path")
+    for name, t, dt in (("segments", segments, torch.int64), ("grad", grad, torch.float32), ("exp_avg", exp_avg, torch.float32),
+                        ("exp_avg_sq", exp_avg_sq, torch.float32), ("step", step, torch.float32), ("loss_scale", loss_scale, torch.float32),
+                        ("growth_tracker", growth_tracker, torch.int32), ("grad_norm", grad_norm, torch.float32), ("skipped", skipped, torch.int32)):
+        if t.device != dev or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"adamw_step_scaled: {name} must be a contiguous {dt} tensor on {dev}")
+    n = grad.numel()
+    if segments.dim() != 2 or segments.shape[1] != 3 or exp_avg.numel() != n or exp_avg_sq.numel() != n:
+        raise ValueError(f"adamw_step_scaled: segments {tuple(segments.shape)} is not [n, 3], or the arenas differ in length")
+    if ws is None:
+        ws = torch.empty(max(lib.ofx_adamw_step_ws_bytes(n), 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.ofx_adamw_step_scaled(_ptr(segments), segments.shape[0], _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), n, _ptr(step), float(lr),
+                                          float(beta1), float(beta2), float(eps), float(weight_decay), float(max_norm), float(grad_scale),
+                                          _ptr(loss_scale), _ptr(growth_tracker), float(growth_factor), float(backoff_factor), int(growth_interval),
+                                          _ptr(grad_norm), _ptr(skipped), _ptr(ws), ws.numel(), _stream(dev)), "ofx_adamw_step_scaled")
+
+
 def topk_merge(idx_parts: torch.Tensor, dist_parts: torch.Tensor):
     """[parts,nq,k] per-shard candidates (global indices) -> ([nq,k] idx, [nq,k] dist), ascending, ties -> smaller idx."""
     lib = L.load()

@@ -6,6 +6,11 @@ vector_norm -> mul_ -> multi-tensor AdamW -> zero_ (36 bytes per arena float ins
 `FlatAdamW` is a torch.optim.Optimizer, so OneCycleLR drives its lr and beta1 and the optimizer-step hooks fire; its state_dict has
 torch.optim.AdamW's layout in both directions.  A step whose gradient norm is not finite is skipped on the device: the gradient is zeroed,
 parameters, moments and the step count stay as they were, and `skipped` reads 1.  There is no CPU path.
+
+`FlatAdamW(loss_scaling=True)` adds torch.amp.GradScaler's dynamic loss scale for f16 training, state machine included, to that same
+call (ofx_adamw_step_scaled): multiply the loss by the scale before the backward (`scale(loss)`), and step() unscales the arena, clips,
+updates, zeroes and then backs the scale off after a skipped step or grows it after `growth_interval` good ones - all on the device,
+still two launches, nothing read back.
 """
 from __future__ import annotations
 
@@ -30,10 +35,17 @@ class FlatAdamW(torch.optim.Optimizer):
     clipping) and `skipped` (0-d int32).  `grad_scale` (default 1.0) multiplies the gradient before the norm is taken.
 
     step() reads lr and betas from param_groups[0] on every call (OneCycleLR cycles both), launches on the current stream and never
-    synchronises; it also leaves the gradient arena zero, so no zero_grad() is needed after it."""
+    synchronises; it also leaves the gradient arena zero, so no zero_grad() is needed after it.
+
+    loss_scaling=True (off by default; the four arguments after it are torch.amp.GradScaler()'s defaults, which the reference's trainers
+    construct): the arena is taken to hold `loss_scale` x the gradient - `scale(loss).backward()` puts it there - and step() is one
+    ofx_adamw_step_scaled call: unscale, norm (`grad_norm` is the UNSCALED norm), clip, AdamW, zero, and the scaler's update of the device
+    tensors `loss_scale` (0-d fp32) and `growth_tracker` (0-d int32).  state_dict() then carries "scale" and "growth_tracker" beside
+    torch's keys; load_state_dict() takes them when they are there and keeps the current ones when they are not."""
 
     def __init__(self, flat_grads, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01,
-                 max_norm: float = 1.0):
+                 max_norm: float = 1.0, loss_scaling: bool = False, init_scale: float = 65536.0, growth_factor: float = 2.0,
+                 backoff_factor: float = 0.5, growth_interval: int = 2000):
         flat = flat_grads.flat
         if flat.device.type != "cuda":
             raise L.OfxError("FlatAdamW needs the gradient arena on a HIP device; there is no CPU path")
@@ -42,6 +54,9 @@ class FlatAdamW(torch.optim.Optimizer):
                 raise ValueError(f"FlatAdamW: parameter {i} {tuple(p.shape)} must be fp32, contiguous, 16-byte aligned and on {flat.device}")
         if not 1 <= len(flat_grads.params) <= 1024:
             raise ValueError(f"FlatAdamW: {len(flat_grads.params)} parameters; ofx_adamw_step takes 1 to 1024 segments")
+        if loss_scaling and not (init_scale > 0.0 and growth_factor >= 1.0 and 0.0 < backoff_factor <= 1.0 and growth_interval >= 1):
+            raise ValueError(f"FlatAdamW: loss scaling needs init_scale > 0, growth_factor >= 1, 0 < backoff_factor <= 1 and growth_interval >= 1; "
+                             f"got {init_scale}, {growth_factor}, {backoff_factor}, {growth_interval}")
         # torch.optim.AdamW's own defaults, taken from the installed torch on purpose: the param_groups keys of a state_dict are then
         # exactly the ones its load_state_dict / step expect, whichever keys that version has (foreach, fused, capturable, ...)
         defaults = dict(torch.optim.AdamW([torch.zeros(1)], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay).defaults)
@@ -54,6 +69,11 @@ class FlatAdamW(torch.optim.Optimizer):
         self.step_t = torch.zeros((), dtype=torch.float32, device=dev)
         self.grad_norm = torch.zeros((), dtype=torch.float32, device=dev)
         self.skipped = torch.zeros((), dtype=torch.int32, device=dev)
+        self.loss_scaling = bool(loss_scaling)
+        self.growth_factor, self.backoff_factor, self.growth_interval = float(growth_factor), float(backoff_factor), int(growth_interval)
+        if self.loss_scaling:
+            self.loss_scale = torch.full((), float(init_scale), dtype=torch.float32, device=dev)
+            self.growth_tracker = torch.zeros((), dtype=torch.int32, device=dev)
         self.ws = torch.empty(max(engine.adamw_step_ws_bytes(flat.numel()), 16), dtype=torch.uint8, device=dev)
         self._ptrs = [p.data_ptr() for p in flat_grads.params]
         self.segments = segment_table(flat_grads.params, flat_grads.offsets).to(dev)
@@ -88,9 +108,21 @@ class FlatAdamW(torch.optim.Optimizer):
             raise ValueError("FlatAdamW: amsgrad / maximize are not implemented")
         self._refresh_segments()
         b1, b2 = g["betas"]
+        if self.loss_scaling:
+            engine.adamw_step_scaled(self.segments, self.flat_grads.flat, self.exp_avg, self.exp_avg_sq, self.step_t, float(g["lr"]), float(b1),
+                                     float(b2), float(g["eps"]), float(g["weight_decay"]), self.max_norm, self.grad_scale, self.loss_scale,
+                                     self.growth_tracker, self.growth_factor, self.backoff_factor, self.growth_interval, self.grad_norm,
+                                     self.skipped, self.ws)
+            return loss
         engine.adamw_step(self.segments, self.flat_grads.flat, self.exp_avg, self.exp_avg_sq, self.step_t, float(g["lr"]), float(b1), float(b2),
                           float(g["eps"]), float(g["weight_decay"]), self.max_norm, self.grad_scale, self.grad_norm, self.skipped, self.ws)
         return loss
+
+    def scale(self, loss: torch.Tensor) -> torch.Tensor:
+        """GradScaler.scale: loss x the current scale, a device multiply (nothing is read back).  Needs loss_scaling=True."""
+        if not self.loss_scaling:
+            raise ValueError("FlatAdamW.scale: this optimizer was built with loss_scaling=False")
+        return loss * self.loss_scale
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         """Zero the arena and keep every p.grad a view of it (step() already leaves it zero)."""
@@ -101,7 +133,10 @@ class FlatAdamW(torch.optim.Optimizer):
         t = self.step_t.detach().cpu()
         for p in self.flat_grads.params:
             self.state[p]["step"] = t.clone()
-        return super().state_dict()
+        sd = super().state_dict()
+        if self.loss_scaling:                                           # GradScaler.state_dict()'s names for the two
+            sd["scale"], sd["growth_tracker"] = float(self.loss_scale), int(self.growth_tracker)
+        return sd
 
     @torch.no_grad()
     def load_state_dict(self, state_dict) -> None:
@@ -131,3 +166,6 @@ class FlatAdamW(torch.optim.Optimizer):
                     self.state[p][key].zero_()
         self.step_t.fill_(steps.pop() if steps else 0.0)
         self.param_groups[0].update({k: v for k, v in groups[0].items() if k != "params"})
+        if self.loss_scaling and "scale" in state_dict:                 # a state_dict from before loss scaling (or torch's own) has neither
+            self.loss_scale.fill_(float(state_dict["scale"]))
+            self.growth_tracker.fill_(int(state_dict.get("growth_tracker", 0)))

@@ -4,9 +4,11 @@ Counterpart of the reference's `CompatibilityPredictionTrainer.train_epoch` step
 (src/trains/trainers/compatibility_prediction_trainer.py:57-81) and its `build_metrics` all-gather (:372-405), written
 for one process per GPU over RCCL/xGMI rather than DistributedDataParallel:
 
-  forward (tape, bf16 operands) -> FocalLoss(.75, 2, mean) -> / accumulation_steps -> backward (hand-written HIP)
+  forward (tape, bf16 operands) -> FocalLoss(.75, 2, mean) -> / accumulation_steps [-> x loss scale] -> backward (hand-written HIP)
   every `accumulation_steps` micro-batches:  ONE all-reduce of the flat gradient arena (mean over ranks)
-                                             -> clip_grad_norm_(1.0) -> AdamW(lr) -> OneCycleLR step -> zero
+                                             [-> unscale] -> clip_grad_norm_(1.0) -> AdamW(lr) [-> scaler update] -> OneCycleLR step -> zero
+  The bracketed steps are torch.amp.GradScaler's (scale / unscale_ / step / update, what the reference wraps its step in), run with
+  `loss_scaling=True` in the config: for f16 operands, whose backward keeps activation gradients in f16 and would lose the small ones.
   epoch end: all-gather logits / labels / loss -> AUC, accuracy, precision, recall, F1 (same formulas as :406-436).
 
 Differences from DDP by design (MI355X / xGMI, point-to-point links, per-link bound rings):
@@ -57,6 +59,11 @@ class CPTrainConfig:
     final_div_factor: float = 1e4
     fused_optimizer: bool = True      # torch.optim.AdamW(fused=True): one multi-tensor kernel per step
     hip_optimizer: bool = False       # optim.FlatAdamW: clip + AdamW + zero over the arena as one ofx_adamw_step call (HIP devices only)
+    loss_scaling: bool = False        # torch.amp.GradScaler's dynamic loss scale around the step (the reference's trainers; for train_precision="f16")
+    init_scale: float = 65536.0       # torch.amp.GradScaler()'s defaults, these four
+    growth_factor: float = 2.0
+    backoff_factor: float = 0.5
+    growth_interval: int = 2000
 
 
 @dataclass
@@ -73,6 +80,11 @@ class CIRTrainConfig:
     final_div_factor: float = 1e4
     fused_optimizer: bool = True
     hip_optimizer: bool = False       # as CPTrainConfig.hip_optimizer
+    loss_scaling: bool = False        # as CPTrainConfig.loss_scaling, and the four below it
+    init_scale: float = 65536.0
+    growth_factor: float = 2.0
+    backoff_factor: float = 0.5
+    growth_interval: int = 2000
 
 
 class FlatGrads:
@@ -181,8 +193,17 @@ def gather_epoch(local_y: torch.Tensor, local_labels: torch.Tensor, local_loss: 
 
 class FlatGradTrainer:
     """What the CP and the CIR loop share: the flat gradient arena, gradient-sink mode of the HIP model, per-layer gradient slices,
-    the overlapped mean over the ranks, and the accumulation-boundary step (clip -> AdamW -> OneCycleLR -> zero).  `cfg` carries
-    learning_rate, accumulation_steps, n_epochs, max_grad_norm, pct_start, div_factor, final_div_factor, fused_optimizer, hip_optimizer.
+    the overlapped mean over the ranks, and the accumulation-boundary step ([unscale ->] clip -> AdamW [-> scaler update] -> OneCycleLR
+    -> zero).  `cfg` carries learning_rate, accumulation_steps, n_epochs, max_grad_norm, pct_start, div_factor, final_div_factor,
+    fused_optimizer, hip_optimizer, and loss_scaling with init_scale, growth_factor, backoff_factor, growth_interval.
+
+    cfg.loss_scaling: the loss is multiplied by a dynamic scale before every backward and the boundary undoes it, as torch.amp.GradScaler
+    does: a window whose gradient is not finite is skipped and multiplies the scale by backoff_factor, growth_interval windows in a row
+    that are not multiply it by growth_factor.  With the torch optimizer the boundary IS a torch.amp.GradScaler (`self.scaler`: unscale_
+    -> clip -> scaler.step -> scaler.update -> zero; scaler.step reads the found-inf flag back); with hip_optimizer the scale and its
+    tracker are device tensors of FlatAdamW (`optimizer.loss_scale`, `optimizer.growth_tracker`), the whole boundary stays the one call
+    and nothing is read back.  Losses are reported unscaled and `last_grad_norm` is the unscaled norm either way.  No collective is
+    added: the ranks sum their arenas before the boundary, so every rank sees the same non-finite norm and the same scale.
 
     cfg.hip_optimizer: the optimizer is optim.FlatAdamW over the arena - norm, clip, AdamW and the zeroing are ONE ofx_adamw_step call
     (two launches), and the division by the world size rides in it as grad_scale.  `last_grad_norm` is then the kernel's norm tensor and
@@ -204,11 +225,17 @@ class FlatGradTrainer:
         dev = self.grads.flat.device
         fused = c.fused_optimizer and dev.type == "cuda"
         self.hip_optimizer = bool(getattr(c, "hip_optimizer", False))
+        self.loss_scaling = bool(getattr(c, "loss_scaling", False))
+        self.scaler = None                                   # loss_scaling with the torch optimizer: the torch.amp.GradScaler
+        scaler_args = ({"init_scale": c.init_scale, "growth_factor": c.growth_factor, "backoff_factor": c.backoff_factor,
+                        "growth_interval": c.growth_interval} if self.loss_scaling else {})
         if self.hip_optimizer:
             from .optim import FlatAdamW                     # raises on a CPU arena: no quiet fall-back to torch's AdamW
-            self.optimizer = FlatAdamW(self.grads, lr=c.learning_rate, max_norm=c.max_grad_norm)
+            self.optimizer = FlatAdamW(self.grads, lr=c.learning_rate, max_norm=c.max_grad_norm, loss_scaling=self.loss_scaling, **scaler_args)
         else:
             self.optimizer = torch.optim.AdamW(self.grads.params, lr=c.learning_rate, **({"fused": True} if fused else {}))
+            if self.loss_scaling:
+                self.scaler = torch.amp.GradScaler(dev.type, **scaler_args)
         self.scheduler = torch.optim.lr_scheduler.OneCycleLR(
             optimizer=self.optimizer, max_lr=c.learning_rate, epochs=c.n_epochs,
             steps_per_epoch=math.ceil(steps_per_epoch / c.accumulation_steps), pct_start=c.pct_start, anneal_strategy="cos",
@@ -306,25 +333,37 @@ class FlatGradTrainer:
             flat.div_(world)
 
     def _backward_and_step(self, loss: torch.Tensor, step: int) -> None:
-        """(loss / accumulation_steps).backward(); on every accumulation_steps-th micro-batch or the epoch's last: mean over the
-        ranks, clip, optimizer and scheduler step, zero (cp_trainer:70-80 = cir_trainer:89-99)."""
+        """(loss / accumulation_steps).backward(), through the loss scale when cfg.loss_scaling (scaler.scale(loss).backward()); on every
+        accumulation_steps-th micro-batch or the epoch's last: mean over the ranks, clip, optimizer and scheduler step, zero
+        (cp_trainer:70-80 = cir_trainer:89-99)."""
         c = self.cfg
         boundary = (step + 1) % c.accumulation_steps == 0 or step + 1 == self.steps_per_epoch
         overlapped = boundary and self._arm_overlap()
-        (loss / c.accumulation_steps).backward()
+        loss = loss / c.accumulation_steps
+        if self.loss_scaling:
+            loss = self.optimizer.scale(loss) if self.hip_optimizer else self.scaler.scale(loss)
+        loss.backward()
         if boundary:
             self._boundary_step(overlapped)
 
     def _boundary_step(self, overlapped: bool) -> None:
         """The end of an accumulation window, on whatever the arena holds: mean over the ranks -> clip -> optimizer step -> scheduler
         step -> zero -> the model re-packs its operand copies on its next forward.  hip_optimizer: clip, step and zero are FlatAdamW's
-        one call; the scheduler steps even when that call skipped a non-finite gradient (class docstring)."""
+        one call; the scheduler steps even when that call skipped a non-finite gradient (class docstring).  loss_scaling: the arena holds
+        scale x the gradient; FlatAdamW's call unscales it and updates the scale itself, the torch form goes through the GradScaler."""
         self._reduce_mean(overlapped)
         if self.hip_optimizer:
             self.optimizer.grad_scale = 1.0 / self._world()
             self.optimizer.step()
             self.last_grad_norm, self.last_step_skipped = self.optimizer.grad_norm, self.optimizer.skipped
             self.scheduler.step()
+        elif self.scaler is not None:
+            self.scaler.unscale_(self.optimizer)
+            self.last_grad_norm = self.grads.clip_norm_(self.cfg.max_grad_norm)
+            self.scaler.step(self.optimizer)
+            self.scaler.update()
+            self.scheduler.step()
+            self.grads.zero_()
         else:
             self.last_grad_norm = self.grads.clip_norm_(self.cfg.max_grad_norm)
             self.optimizer.step()

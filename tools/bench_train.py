@@ -41,8 +41,11 @@ over the per-tensor views -> zero_, plus the div_ by the world size when there i
 (optim.FlatAdamW: one ofx_adamw_step call).  `boundary_bytes_*` are the bytes each form has to move, computed here from the arena's
 length n: 44 n (52 n with the world divide) and 36 n; `boundary_GBps_*` the resulting rates; `us_boundary_hip_norm_pass` /
 `us_boundary_hip_update_pass` the device times of the call's two kernels (torch.profiler, one step; absent if it records none).
-`ms_step_dp_hip` / `ms_step_dp_accum4_hip` are the trainer steps with CPTrainConfig(hip_optimizer=True).  The line is also written to
---boundary-out when given (profiles/optimizer_step_bench.json).
+`ms_step_dp_hip` / `ms_step_dp_accum4_hip` are the trainer steps with CPTrainConfig(hip_optimizer=True).  `ms_boundary_hip_scaled` is the
+loss-scaled call (FlatAdamW(loss_scaling=True): ofx_adamw_step_scaled, on the same gradient x 65536) timed BETWEEN two groups of the plain
+call, `ms_boundary_hip_plain_a` / `_plain_b`, the three alternating inside every repetition: the scaled call moves the same bytes, so the
+distance between the two plain groups (`boundary_plain_spread`) is the margin `boundary_scaled_over_plain` is read against.  The line is
+also written to --boundary-out when given (profiles/optimizer_step_bench.json).
 
 --eager also times the same step written with plain torch modules (nn.TransformerEncoder under bf16 autocast, what the
 reference's trainer executes) on the same GPU, for a like-for-like ratio.  Prints one JSON line.
@@ -134,7 +137,25 @@ def boundary_bench(params, world, reps, res):
                     res[name] = float(getattr(e, "device_time", 0.0) or getattr(e, "cuda_time", 0.0))
     except Exception as e:                                      # noqa: BLE001 - the per-kernel split is a diagnostic; the medians above are the result
         res["boundary_profile_error"] = repr(e)[:200]
-    del opt_t, opt_h, grads
+    # the loss-scaled call (ofx_adamw_step_scaled) between two groups of the plain call, all three alternating: the scaled call moves
+    # the same bytes, so what separates the two plain groups from each other is the margin it is judged by
+    opt_s = FlatAdamW(grads, lr=2e-5, max_norm=1.0, loss_scaling=True)
+    opt_s.grad_scale = 1.0 / world
+    fill_s = fill * opt_s.loss_scale                            # the arena a scaled backward leaves: the same gradient x 65536
+    ts = [[] for _ in range(3)]
+    for rep in range(5 + reps):
+        for i, (opt, src) in enumerate(((opt_h, fill), (opt_s, fill_s), (opt_h, fill))):
+            flat.copy_(src)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); opt.step(); b.record()
+            b.synchronize()
+            if rep >= 5:
+                ts[i].append(a.elapsed_time(b))
+    t_a, t_s, t_b = (float(np.median(t)) for t in ts)
+    res.update(ms_boundary_hip_plain_a=t_a, ms_boundary_hip_scaled=t_s, ms_boundary_hip_plain_b=t_b, boundary_scaled_over_plain=t_s / min(t_a, t_b),
+               boundary_plain_spread=abs(t_a - t_b) / min(t_a, t_b), boundary_scaled_skipped=int(opt_s.skipped),
+               boundary_scaled_scale=float(opt_s.loss_scale))
+    del opt_t, opt_h, opt_s, grads
 
 
 def eager_set_rank_loss(batch_y, batch_y_hat, batch_negative_samples, batch_negative_mask, margin=2.0):
